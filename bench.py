@@ -19,11 +19,16 @@ Multi-GPU: ONE logical list of `chunks_per_gpu x N` chunks is part
 ranges (c-blosc_amd/multigpu.py: chunk_range); chunks are independent, so there is no data-path
 collective - the only exchange is the all_gather of the per-chunk cbytes table over RCCL
 (gather_cbytes, backend "nccl", also with a communicator of size 1), timed separately as
-`consolidation_ms`.  The JSON line also carries per-direction rates, per-kernel HIP-event times, the
-roofline of the dominant kernel, decompression of chunks written by the reference itself (the drop-in
-direction) and the reference's own multi-threaded CPU path on this box's host cores.
+`consolidation_ms`.
 
-Run:  python bench.py [--config C --gpus N --steps K --warmup W]
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, `ratio`).
+With `--full` it also measures and checks everything else, as separate runs after the timed steps: per-direction rates,
+per-kernel HIP-event times, the roofline of the dominant kernel, bit-exact verification against the reference, the
+consolidation exchanges, decompression of chunks written by the reference itself (the drop-in direction), the short
+legs of the other configurations, the stock ABI on host buffers and the reference's own multi-threaded CPU path on
+the host's cores.  `--dump-outputs DIR` writes what the last timed step computed to DIR/*.npy (see dump_outputs).
+
+Run:  python bench.py [--config C --gpus N --steps K --warmup W --full --dump-outputs DIR]
       N > 1: `python bench.py --gpus N` starts the N ranks itself (it re-executes itself under torch.distributed.run, one process
       per GPU, the way the reference's entry point starts its own workers - blosc/blosc.c:1890-1949 init_threads); launched under
       torch.distributed.run by somebody else (RANK / WORLD_SIZE in the environment) it is one of those ranks.
@@ -357,14 +362,64 @@ def cpu_baseline(chunk_host, typesize, clevel, shuffle, cname, budget_s=20.0):
                       f"from its own sources; mean over >= 3 passes per arm, about {budget_s:.0f} s in total"}
 
 
+DUMP_SEED = 20240601
+DUMP_BUDGET = 56 << 20     # bytes of .npy payload at most (the limit is 64 MB)
+
+
+def dump_outputs(outdir, torch, comp, cbytes, back, csz):
+    """What a caller of the timed path receives from its last step, for comparing two builds output for output: this rank's
+    compressed chunks (comp[i][:cbytes[i]], None when the step only decompresses) and decompressed chunks (back[i]).  The chunks
+    are too large to write whole, so every chunk is written as a fixed, seeded sample of its bytes plus two sums over all of them:
+        cbytes.npy                float64 [nchunks]      compressed size of every chunk
+        compressed_head.npy       float32 [nchunks, H]   first H bytes of every compressed chunk (header, block starts), -1 past its end
+        compressed_sample.npy     float32 [nchunks, S]   compressed bytes at positions floor(u * cbytes[i]), u seeded in [0, 1)
+        compressed_sums.npy       float64 [nchunks, 2]   sum of the chunk's bytes b[j], and of b[j] * (j mod 65521 + 1), both mod 2^52
+        decompressed_sample.npy   float32 [nchunks, S]   decompressed bytes at positions floor(u * csz)
+        decompressed_sums.npy     float64 [nchunks, 2]   the two sums over every decompressed byte
+    The sample positions depend on the seed, the chunk count and the sizes only, so equal arguments give equal files."""
+    os.makedirs(outdir, exist_ok=True)
+    n, dev = back.shape[0], back.device
+    per_chunk = DUMP_BUDGET // n // 4 - 8                       # float32 values per chunk, with room for the sums and cbytes
+    H = min(1024, per_chunk // 8)
+    S = min(1 << 15, (per_chunk - H) // 2)
+    assert S > 0, f"{n} chunks: too many to sample within {DUMP_BUDGET} bytes"
+    rng = np.random.default_rng(DUMP_SEED)
+    u_c, u_d = rng.random((n, S)), rng.random((n, S))
+    weight = torch.arange(max(back.shape[1], 1 if comp is None else comp.shape[1]), device=dev, dtype=torch.int64) % 65521 + 1
+    mask = (1 << 52) - 1
+
+    def sums(rows, lengths):
+        out = np.empty((len(lengths), 2), np.float64)
+        for i, ln in enumerate(lengths):
+            b = rows[i, :ln].to(torch.int64)
+            out[i] = [int(b.sum().item()) & mask, int((b * weight[:ln]).sum().item()) & mask]
+        return out
+
+    def sample(rows, lengths, u):
+        pos = np.minimum(np.floor(u * np.asarray(lengths, np.float64)[:, None]).astype(np.int64), np.asarray(lengths)[:, None] - 1)
+        return rows.gather(1, torch.from_numpy(pos).to(dev)).cpu().numpy().astype(np.float32)
+
+    files = {"decompressed_sample": sample(back, [csz] * n, u_d), "decompressed_sums": sums(back, [csz] * n)}
+    if comp is not None:
+        head = comp[:, :H].cpu().numpy().astype(np.float32)
+        head[np.arange(H)[None, :] >= np.asarray(cbytes)[:, None]] = -1
+        files.update({"cbytes": np.asarray(cbytes, np.float64), "compressed_head": head,
+                      "compressed_sample": sample(comp, cbytes, u_c), "compressed_sums": sums(comp, cbytes)})
+    assert sum(a.nbytes for a in files.values()) <= 64_000_000
+    for name, a in files.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 class Rig:
     """everything one process sets up once: torch / RCCL, the library, the rank's share of the chunk list"""
     pass
 
 
-def measure(rig, name, cfg, steps, warmup, args, mixed=None, payload=False):
+def measure(rig, name, cfg, steps, warmup, args, mixed=None, payload=False, dump_dir=None):
     """One workload through the timed protocol of the contract: `warmup` untimed steps, then exactly `steps` steps between
-    barrier + synchronize pairs, MAX over ranks.  Returns the fields of the JSON line that belong to this workload."""
+    barrier + synchronize pairs, MAX over ranks.  Returns the fields of the JSON line that belong to this workload: the headline
+    fields only, unless args.full (then every other figure and check of the workload as well, each after the timed steps).
+    dump_dir: rank 0 writes what the last timed step computed there (dump_outputs)."""
     torch, dist, mod, lib, multigpu, dev = rig.torch, rig.dist, rig.mod, rig.lib, rig.multigpu, rig.dev
     world, rank = rig.world, rig.rank
     cname = cfg["codec"].encode()
@@ -386,7 +441,7 @@ def measure(rig, name, cfg, steps, warmup, args, mixed=None, payload=False):
 
     # the reference's own chunk of this data (drop-in direction; the only source of chunks for a codec the GPU cannot encode)
     ref_chunk = None
-    if os.path.exists(REFSO) and not mixed and not (args.no_stock and gpu_can_encode):
+    if os.path.exists(REFSO) and not mixed and (not gpu_can_encode or (args.full and not args.no_stock)):
         R = C.CDLL(REFSO)
         R.blosc_compress_ctx.argtypes = [C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_int]
         tmp = np.empty(csz + 16, np.uint8)
@@ -419,12 +474,10 @@ def measure(rig, name, cfg, steps, warmup, args, mixed=None, payload=False):
         step()
         if w == 0:
             torch.cuda.synchronize(); first_ms = (time.perf_counter() - tf) * 1e3
-    cbytes = [ref_chunk.size] * nchunks if decode_only else bc.results()
-    assert all(c > 0 for c in cbytes), cbytes[:4]
-    assert bd.results() == [csz] * nchunks, bd.results()[:4]
 
-    lib.blosc_gpu_profile(1)
-    lib.blosc_gpu_profile_reset()
+    if args.full:      # per-kernel HIP-event pairs over the timed steps (for the kernel table and the roofline)
+        lib.blosc_gpu_profile(1)
+        lib.blosc_gpu_profile_reset()
     sync_all()
     t0 = time.perf_counter()
     for _ in range(steps):
@@ -432,12 +485,34 @@ def measure(rig, name, cfg, steps, warmup, args, mixed=None, payload=False):
     sync_all()
     elapsed = time.perf_counter() - t0
     lib.blosc_gpu_profile(0)
+    cbytes = [ref_chunk.size] * nchunks if decode_only else bc.results()
+    assert all(c > 0 for c in cbytes), cbytes[:4]
+    assert bd.results() == [csz] * nchunks, bd.results()[:4]
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, torch, None if decode_only else comp, cbytes, back, csz)
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
-    per_rank_t = [torch.zeros_like(t) for _ in range(world)]
-    dist.all_gather(per_rank_t, t)
-    per_rank_gbps = [steps * total / float(x.item()) / 1e9 for x in per_rank_t]
+    if args.full:
+        per_rank_t = [torch.zeros_like(t) for _ in range(world)]
+        dist.all_gather(per_rank_t, t)
+        per_rank_gbps = [steps * total / float(x.item()) / 1e9 for x in per_rank_t]
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    what = "decompress pass of reference-written chunks (the GPU does not encode this codec)" if decode_only else "compress pass + decompress pass"
+    res = {
+        "value": world * steps * total / elapsed / 1e9, "unit": "GB/s", "steps": steps, "warmup": warmup,
+        "ms_per_step": elapsed / steps * 1e3,
+        "first_call_ms": first_ms,             # the first step of this workload in this process: cold queues (no cost feedback yet), arenas still growing
+        "config": {"workload": f"config #{name}: {FILTER_NAME[shuffle]} + {cfg['codec']} clevel={clevel} typesize={T}, "
+                               f"{nchunks} x {args.chunk_mib} MiB {'+'.join(datasets)} chunks per GPU ({total / 2**30:.0f} GiB), "
+                               f"step = {what}, device-resident",
+                   "name": name, "codec": cfg["codec"], "shuffle": shuffle, "typesize": T, "clevel": clevel,
+                   "chunks_per_gpu": nchunks, "chunks_total": rig.nchunks_total, "chunk_bytes": csz, "dataset": "+".join(datasets),
+                   "direction": "decompress" if decode_only else "compress+decompress"},
+        "ratio": nchunks * csz / float(sum(cbytes)),      # this rank's chunks (every rank holds the same data); --full: over the gathered table
+        "_host_chunk": host_chunk,
+    }
+    if not args.full:
+        return res
 
     # ---- one step WITHOUT the queue order learnt from the previous calls (blosc_gpu_profile(2): plain block order, what a first call on new data gets) ----
     lib.blosc_gpu_profile(2)
@@ -551,19 +626,9 @@ def measure(rig, name, cfg, steps, warmup, args, mixed=None, payload=False):
     roof["per_rank_frac"] = [round(float(x[0].item()), 4) for x in allr]
     if stock is not None:
         roof["decode_stock"]["per_rank_frac"] = [round(float(x[1].item()), 4) for x in allr]
-    what = "decompress pass of reference-written chunks (the GPU does not encode this codec)" if decode_only else "compress pass + decompress pass"
-    res = {
-        "value": world * steps * total / elapsed / 1e9, "unit": "GB/s", "steps": steps, "warmup": warmup,
-        "ms_per_step": elapsed / steps * 1e3,
-        "first_call_ms": first_ms,             # the first step of this workload in this process: cold queues (no cost feedback yet), arenas still growing
+    res.update({
         "sched_cold": {"ms_per_step": sched_cold_ms, "GBps": world * total / (sched_cold_ms / 1e3) / 1e9,      # one step in plain block order, arenas warm
                        "note": "all 128 chunks of the bench are the same 64 MiB (bench/bench.c:383) and the queue order is trained on them; this is the step without that"},
-        "config": {"workload": f"config #{name}: {FILTER_NAME[shuffle]} + {cfg['codec']} clevel={clevel} typesize={T}, "
-                               f"{nchunks} x {args.chunk_mib} MiB {'+'.join(datasets)} chunks per GPU ({total / 2**30:.0f} GiB), "
-                               f"step = {what}, device-resident",
-                   "name": name, "codec": cfg["codec"], "shuffle": shuffle, "typesize": T, "clevel": clevel,
-                   "chunks_per_gpu": nchunks, "chunks_total": rig.nchunks_total, "chunk_bytes": csz, "dataset": "+".join(datasets),
-                   "direction": "decompress" if decode_only else "compress+decompress"},
         "ratio": rig.nchunks_total * csz / sum_cb_global,
         "decompress": {"GBps_kernels": total / t_d / 1e9, "roofline_frac_path": (total + sum_cb) / t_d / 1e9 / HBM_PEAK_GBPS},
         "decompress_stock_chunks": stock,
@@ -575,10 +640,9 @@ def measure(rig, name, cfg, steps, warmup, args, mixed=None, payload=False):
         "kernels": prof,
         "roofline": roof,
         "verified": verified,
-    }
+    })
     if not decode_only:
         res["compress"] = {"GBps_kernels": total / t_c / 1e9, "roofline_frac_path": (total + sum_cb) / t_c / 1e9 / HBM_PEAK_GBPS}
-    res["_host_chunk"] = host_chunk
     return res
 
 
@@ -594,6 +658,18 @@ def _r(x, nd=4):
     if isinstance(x, list):
         return [_r(v, nd) for v in x]
     return x
+
+
+METRIC = "compress+decompress GB/s (uncompressed) at 1/2/4/8 GPUs vs HBM roofline; ratio"
+
+
+def headline_line(res, world):
+    """The line of a plain run: the headline fields of assemble()'s line that the timed steps themselves give."""
+    out = {"metric": METRIC, "value": res["value"], "unit": res["unit"], "n_gpus": world, "steps": res["steps"], "warmup": res["warmup"],
+           "ms_per_step": res["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+           "config": {kk: res["config"][kk] for kk in ("workload", "name", "chunks_per_gpu", "chunks_total", "chunk_bytes")},
+           "ratio": res["ratio"]}
+    return json.dumps(_r(out))
 
 
 def assemble(res, world, cpu, extra, mixed, args):
@@ -623,7 +699,7 @@ def assemble(res, world, cpu, extra, mixed, args):
     stock = res.get("decompress_stock_chunks")
     k = res["kernels"]
     out = {
-        "metric": "compress+decompress GB/s (uncompressed) at 1/2/4/8 GPUs vs HBM roofline; ratio",
+        "metric": METRIC,
         "value": res["value"], "unit": res["unit"], "n_gpus": world, "steps": res["steps"], "warmup": res["warmup"],
         "ms_per_step": res["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "u8", "data": "synthetic",
@@ -773,6 +849,9 @@ def main():
     ap.add_argument("--no-extra", action="store_true", help="default config only: skip the short legs for configs #3 / #4 and the mixed batch")
     ap.add_argument("--spawn", action="store_true", help="start the ranks through torch.distributed.run also when N = 1 (the N > 1 launch path on a one-GPU box)")
     ap.add_argument("--dry-gloo", action="store_true", help="no GPU: launch, partition, cbytes / payload exchanges and the JSON line over gloo on the CPU (tests)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure and check everything else: kernels, roofline, verification, "
+                                                        "consolidation, reference-written chunks, the other configurations, host ABI, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
     if args.gpus is None:
         args.gpus = int(os.environ["WORLD_SIZE"]) if "RANK" in os.environ and "WORLD_SIZE" in os.environ else 1
@@ -837,8 +916,15 @@ def main():
     rig.comp = torch.empty((rig.nchunks, rig.csz + 256), dtype=torch.uint8, device=dev)
     rig.back = torch.empty((rig.nchunks, rig.csz), dtype=torch.uint8, device=dev)
 
-    res = measure(rig, args.config, cfg, args.steps, args.warmup, args, payload=True)
+    res = measure(rig, args.config, cfg, args.steps, args.warmup, args, payload=True, dump_dir=args.dump_outputs)
     host_chunk = res.pop("_host_chunk")
+    if not args.full:
+        if rank == 0:
+            print(headline_line(res, world))
+            sys.stdout.flush()
+        rig.lib.blosc_init(); rig.lib.blosc_destroy()
+        dist.destroy_process_group()
+        return
     # ---- the other BASELINE.json configurations and a batch of mixed data, as short legs of the default run:
     #      each with its own roofline object (dominant kernel, algorithmic bytes, average launch) and its ratio next to stock's ----
     extra = None

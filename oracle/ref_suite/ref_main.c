@@ -1,4 +1,4 @@
-/* ref_main.c — process wrapper for the reference's test programs (tests/ref_suite/Makefile compiles each of them
+/* ref_main.c — process wrapper for the reference's test programs (oracle/ref_suite/Makefile compiles each of them
  * with -Dmain=ref_test_main).  Without arguments, or with the program's own arguments, it simply calls the test's
  * main.  With "--csv FILE [stride]" it calls the test's main once per row of the reference's parameter list (the
  * rows CMake turns into one ctest case each, tests/CMakeLists.txt:66-100), in ONE process: a HIP process start per
@@ -6,8 +6,22 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <sys/types.h>
+#include <unistd.h>
 
 extern int ref_test_main(int argc, char** argv);
+
+/* tests/test_nolock.c and tests/test_noinit.c call fork() four times in a row before they use the library: 2^4 = 16
+ * processes, every one of which opens the GPU, next to the process that started them.  A GPU machine is shared and takes
+ * at most 16 processes with the device open, so oracle/ref_suite/Makefile compiles these two with -Dfork=ref_bounded_fork:
+ * only the first REF_FORKS calls of the process tree fork (the counter is copied into each child), which makes 2^REF_FORKS
+ * processes; a later call creates none and returns 0, as fork() does in a child, so every process still runs the whole suite
+ * concurrently with the others. */
+#define REF_FORKS 2
+pid_t ref_bounded_fork(void) {
+  static int calls = 0;
+  return calls++ < REF_FORKS ? fork() : 0;
+}
 
 int main(int argc, char** argv) {
   if (argc >= 3 && strcmp(argv[1], "--csv") == 0) {

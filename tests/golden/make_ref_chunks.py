@@ -13,7 +13,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
-from helpers import DATASETS, ptr  # noqa: E402
+from helpers import DATASETS, ptr, save_golden_npz  # noqa: E402
 
 R = C.CDLL(os.path.join(HERE, "..", "..", "oracle", "_ref", "libblosc_ref.so"))
 R.blosc_compress_ctx.argtypes = [C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_int]
@@ -45,5 +45,5 @@ for k, (cname, shuffle, dname, n, T, clevel, nth, bs, sm) in enumerate(cases):
     meta.append(f"{cname},{shuffle},{dname},{n},{T},{clevel},{nth},{bs},{sm}")
 R.blosc_set_splitmode(4)
 out["meta"] = np.array(meta)
-np.savez_compressed(os.path.join(HERE, "ref_chunks.npz"), **out)
+save_golden_npz("ref_chunks.npz", out)
 print(len(cases), "chunks,", sum(v.size for k, v in out.items() if k != "meta"), "bytes")

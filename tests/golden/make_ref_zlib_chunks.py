@@ -6,7 +6,7 @@ import ctypes as C, os, sys
 import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__)); ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from helpers import DATASETS, ptr
+from helpers import DATASETS, ptr, save_golden_npz
 R = C.CDLL(os.path.join(ROOT, "oracle", "_ref", "libblosc_ref.so"))
 R.blosc_compress_ctx.argtypes = [C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_int]
 out = {}; meta = []
@@ -21,5 +21,5 @@ for dname in ("bench19", "linspace", "smallints", "zeros", "randwalk", "random")
         assert r > 0
         out[f"c{k}"] = buf[:r].copy(); meta.append(f"{dname},{n},{T},{clevel},{shuffle},{bs}"); k += 1
 out["meta"] = np.array(meta)
-np.savez_compressed(os.path.join(HERE, "ref_zlib_chunks.npz"), **out)
+save_golden_npz("ref_zlib_chunks.npz", out)
 print(k, "chunks,", sum(v.size for kk, v in out.items() if kk != "meta"), "bytes")

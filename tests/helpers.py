@@ -1,13 +1,48 @@
 """Data sets and small wrappers shared by the tests (SURVEY.md §8d inputs)."""
 import ctypes as C
+import glob
+import os
 
 import numpy as np
 
 CODECS = {"blosclz": 0, "lz4": 1}
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+GOLDEN_PART_BYTES = 900 << 10      # a committed file stays below 1 MiB: larger fixtures are stored in parts
 
 
 def ptr(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def golden_npz(name):
+    """tests/golden/<name> as one {key: array} mapping, read from its parts <stem>.part<k>.npz (see save_golden_npz)."""
+    stem = os.path.join(GOLDEN, name[:-len(".npz")] if name.endswith(".npz") else name)
+    parts = sorted(glob.glob(stem + ".part*.npz"), key=lambda p: int(p[len(stem) + len(".part"):-len(".npz")]))
+    if not parts:
+        raise FileNotFoundError(f"no parts of {name} under {GOLDEN}")
+    out = {}
+    for p in parts:
+        with np.load(p) as z:
+            out.update((k, z[k]) for k in z.files)
+    return out
+
+
+def save_golden_npz(name, arrays):
+    """Writes `arrays` as tests/golden/<stem>.part<k>.npz (compressed), each part below GOLDEN_PART_BYTES, in key order."""
+    stem = os.path.join(GOLDEN, name[:-len(".npz")] if name.endswith(".npz") else name)
+    for old in glob.glob(stem + ".part*.npz"):
+        os.remove(old)
+    parts, cur, cur_bytes = [], {}, 0
+    for k, v in arrays.items():
+        est = v.nbytes             # an upper bound of the compressed size
+        if cur and cur_bytes + est > GOLDEN_PART_BYTES:
+            parts.append(cur); cur, cur_bytes = {}, 0
+        cur[k] = v; cur_bytes += est
+    parts.append(cur)
+    for i, p in enumerate(parts):
+        np.savez_compressed(f"{stem}.part{i}.npz", **p)
+        assert os.path.getsize(f"{stem}.part{i}.npz") < (1 << 20), (name, i)
+    return len(parts)
 
 
 def bench19(nbytes):

@@ -93,3 +93,35 @@ def test_headline_line_assembly_stays_small():
         os.remove(os.path.join(ROOT, "gpurun_out", "bench_extra.json"))
     except OSError:
         pass
+
+
+def test_dump_outputs_on_host_tensors(tmp_path):
+    """bench.dump_outputs (what --dump-outputs writes) on host tensors shaped like a small run: float files only, under 64 MB, the same
+    files for the same inputs, sums over every byte, the compressed head padded with -1 past a chunk's end."""
+    import importlib.util
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n, csz = 6, 1 << 20
+    back = torch.from_numpy(np.random.default_rng(5).integers(0, 256, (n, csz), dtype=np.uint8))
+    comp = torch.from_numpy(np.random.default_rng(6).integers(0, 256, (n, csz + 256), dtype=np.uint8))
+    cbytes = [700, 5000, 90000, 17, 1024, csz]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), torch, comp, cbytes, back, csz)
+    files = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(files) == {"cbytes", "compressed_head", "compressed_sample", "compressed_sums", "decompressed_sample", "decompressed_sums"}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values()) and sum(a.nbytes for a in files.values()) <= 64_000_000
+    assert all(np.array_equal(a, np.load(tmp_path / "b" / (k + ".npy"))) for k, a in files.items())
+    w = np.arange(csz + 256) % 65521 + 1
+    for i in range(n):
+        row = back[i].numpy().astype(np.int64)
+        assert list(files["decompressed_sums"][i]) == [row.sum(), (row * w[:csz]).sum()]
+        crow = comp[i, :cbytes[i]].numpy().astype(np.int64)
+        assert list(files["compressed_sums"][i]) == [crow.sum(), (crow * w[:cbytes[i]]).sum()]
+        head = files["compressed_head"][i]
+        k = min(cbytes[i], head.size)
+        assert np.array_equal(head[:k], comp[i, :k].numpy()) and (head[k:] == -1).all()
+        assert set(np.unique(files["compressed_sample"][i])) <= set(np.unique(crow))
+    assert list(files["cbytes"]) == cbytes

@@ -12,7 +12,7 @@ import sys
 import numpy as np
 import pytest
 
-from helpers import DATASETS, header, orc_compress, orc_decompress, ptr, ref_compress, ref_decompress
+from helpers import DATASETS, golden_npz, header, orc_compress, orc_decompress, ptr, ref_compress, ref_decompress
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLANG = "/opt/rocm/lib/llvm/bin/clang++"
@@ -262,7 +262,7 @@ def test_reference_written_zstd_chunks_through_the_two_phase_path(emulib, oracle
     the engine's default Zstd path - k_zstd_entropy (set-up, Huffman streams, 16-bit sequence tables), k_zstd_seq (one lane per frame, the
     three-refill bit reader of round 3), k_zstd_exec with the unshuffle of the decoding wave - intact, and damaged with the oracle's verdict
     and bytes (the oracle is pinned to the reference on damaged frames, tests/test_oracle_zstd.py)."""
-    z = np.load(os.path.join(ROOT, "tests", "golden", "ref_zstd_chunks.npz"))
+    z = golden_npz("ref_zstd_chunks.npz")
     rng = np.random.default_rng(33 + SOAK)
     before = (C.c_ulonglong * 5)(); emulib.emu_zstd_path_counts(before)
     items = []
@@ -302,7 +302,7 @@ def test_reference_written_zlib_chunks_through_the_queued_kernel(emulib, oracle)
     """The committed chunks written by the real reference with zlib (tests/golden/ref_zlib_chunks.npz) through k_zlib_streams as the engine
     launches it since round 3 - per-XCD queues, the block unshuffled by the wave that completes its last stream - intact, and damaged
     with the oracle's verdict and bytes."""
-    z = np.load(os.path.join(ROOT, "tests", "golden", "ref_zlib_chunks.npz"))
+    z = golden_npz("ref_zlib_chunks.npz")
     rng = np.random.default_rng(34 + SOAK)
     items = []
     for k, m in enumerate(z["meta"]):
@@ -483,14 +483,14 @@ def test_fallback_switches(emulib, flip):
     assert p.returncode == 0 and "modes ok" in p.stdout, (flip, p.stdout[-2000:], p.stderr[-3000:])
 
 
-# ---- the reference's OWN test programs (tests/ref_suite/_bin, built unmodified from /root/reference/tests where that exists) linked at
+# ---- the reference's OWN test programs (oracle/_ref/ref_suite, built unmodified from the reference's tests where those exist) linked at
 #      run time against the emulated library: what tests/test_gpu_ref_suite.py does on the device, here for the programs that are quick
 #      enough at emulator speed ----
 @pytest.fixture(scope="module")
 def ref_programs(emulib, tmp_path_factory):
-    bindir = os.path.join(ROOT, "tests", "ref_suite", "_bin")
+    bindir = os.path.join(ROOT, "oracle", "_ref", "ref_suite")
     if not os.path.exists(os.path.join(bindir, "test_api")):
-        pytest.skip("tests/ref_suite/_bin is missing (built where /root/reference exists)")
+        pytest.skip("oracle/_ref/ref_suite is missing (built where the reference's sources exist)")
     libdir = tmp_path_factory.mktemp("libblosc_emu")
     os.symlink(os.path.join(ROOT, "tests", "tools", "libblosc_amd_emu.so"), os.path.join(libdir, "libblosc.so.1"))   # the stock SONAME
     env = dict(os.environ)

@@ -75,7 +75,7 @@ def test_bench_spawner_n1():
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--spawn", "--steps", "1", "--warmup", "1", "--chunks", "4",
-                        "--chunk-mib", "8", "--no-cpu-baseline", "--no-extra"], capture_output=True, text=True, timeout=600, env=env)
+                        "--chunk-mib", "8", "--no-cpu-baseline", "--no-extra", "--full"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -94,7 +94,7 @@ def test_bench_line_fits_the_drivers_tail():
     import subprocess
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--chunks", "4", "--chunk-mib", "8", "--cpu-seconds", "2"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--chunks", "4", "--chunk-mib", "8", "--cpu-seconds", "2", "--full"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     assert len(r.stderr) < 2048, r.stderr[-3000:]

@@ -1,10 +1,10 @@
 """GPU: the reference's OWN acceptance programs against the drop-in (SURVEY §2 "acceptance suite to re-run
 against the drop-in .so", §8b, §8f-1).
 
-tests/ref_suite/Makefile compiles /root/reference/tests/test_*.c, compat/filegen.c, bench/bench.c and
+oracle/ref_suite/Makefile compiles the reference's tests/test_*.c, compat/filegen.c, bench/bench.c and
 tests/fuzz/{fuzz_decompress,fuzz_compress,standalone}.c UNMODIFIED against include/blosc.h and links them with
-libblosc_amd.so (SONAME libblosc.so.1).  The binaries are built where /root/reference exists and travel to the GPU
-box like oracle/_ref; here they are only executed.  Deviations from a stock build are listed in INTEGRATION.md §7
+libblosc_amd.so (SONAME libblosc.so.1) into oracle/_ref/ref_suite.  The binaries are built where the reference's sources
+exist and travel to the GPU box with oracle/_ref; here they are only executed.  Deviations from a stock build are listed in INTEGRATION.md §7
 and asserted below (so a change in behaviour shows up either way).
 """
 import glob
@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "tests", "ref_suite", "_bin")
+BIN = os.path.join(ROOT, "oracle", "_ref", "ref_suite")
 COMPAT = os.path.join(ROOT, "tests", "golden", "compat")
 pytestmark = pytest.mark.gpu
 
@@ -26,9 +26,9 @@ pytestmark = pytest.mark.gpu
 def env(tmp_path_factory):
     if not os.path.exists(os.path.join(BIN, "test_api")):
         if os.path.isdir("/root/reference"):
-            subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "ref_suite")], stdout=subprocess.DEVNULL)
+            subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle", "ref_suite")], stdout=subprocess.DEVNULL)
         else:
-            pytest.skip("tests/ref_suite/_bin is missing: the binaries are built where /root/reference exists (`make -C tests/ref_suite`, "
+            pytest.skip("oracle/_ref/ref_suite is missing: the binaries are built where the reference's sources exist (`make -C oracle/ref_suite`, "
                         "also done by __graft_entry__.build()) and travel to the GPU box with the tree")
     # the binaries ask for libblosc.so.1 (the stock SONAME): serve the drop-in under that name
     libdir = tmp_path_factory.mktemp("libblosc")
@@ -49,6 +49,8 @@ def run(env, args, timeout=600, cwd=None):
 def test_minunit_program(env, prog):
     rc, out, err = run(env, [prog])
     assert rc == 0 and "ALL TESTS PASSED" in out, (rc, out[-2000:], err[-2000:])
+    if prog in ("test_nolock", "test_noinit"):      # the suite in 4 processes at once (oracle/ref_suite/ref_main.c: ref_bounded_fork): every one passes
+        assert out.count("ALL TESTS PASSED") == 4, (out[-3000:], err[-2000:])
 
 
 def test_bitshuffle_leftovers(env, tmp_path):

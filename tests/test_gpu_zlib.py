@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import deflate_builder as D
-from helpers import DATASETS, orc_decompress, ptr, ref_decompress
+from helpers import DATASETS, golden_npz, orc_decompress, ptr, ref_decompress
 from test_oracle_zlib import HANDBUILT
 
 pytestmark = pytest.mark.gpu
@@ -19,7 +19,7 @@ GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 
 
 def _chunks():
-    z = np.load(os.path.join(GOLDEN, "ref_zlib_chunks.npz"))
+    z = golden_npz("ref_zlib_chunks.npz")
     for k, m in enumerate(z["meta"]):
         dname, n, T, clevel, shuffle, bs = m.split(",")
         yield z[f"c{k}"], dname, int(n), int(T)
@@ -148,7 +148,7 @@ def test_corrupt_chunks_in_canary_padded_device_buffers(pkg, oracle, fixture):
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(41)
     PAD = 4096
-    z = np.load(os.path.join(GOLDEN, fixture))
+    z = golden_npz(fixture)
     metas = [m.split(",") for m in z["meta"]]
     for k in (0, 1, 2, 5, 9):
         good = z[f"c{k}"]; n = int(metas[k][1])

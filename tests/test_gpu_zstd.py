@@ -8,14 +8,14 @@ import os
 import numpy as np
 import pytest
 
-from helpers import DATASETS, orc_decompress, ptr
+from helpers import DATASETS, golden_npz, orc_decompress, ptr
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 
 
 def _chunks():
-    z = np.load(os.path.join(GOLDEN, "ref_zstd_chunks.npz"))
+    z = golden_npz("ref_zstd_chunks.npz")
     for k, m in enumerate(z["meta"]):
         dname, n, T, clevel, shuffle, bs = m.split(",")
         yield z[f"c{k}"], dname, int(n), int(T)
@@ -44,7 +44,7 @@ def test_device_batch_mixed_codecs(pkg, oracle):
     from helpers import orc_compress
     dev = torch.device("cuda:0")
     items = [(c, DATASETS[d](n)) for c, d, n, T in list(_chunks())[:8]]
-    zl = np.load(os.path.join(GOLDEN, "ref_zlib_chunks.npz"))
+    zl = golden_npz("ref_zlib_chunks.npz")
     for k in (0, 1, 4, 10, 15, 20):
         dname, n, T, clevel, shuffle, bs = zl["meta"][k].split(",")
         items.insert(2 * (k % 4), (zl[f"c{k}"], DATASETS[dname](int(n))))            # interleaved with the Zstd chunks

@@ -6,7 +6,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import DATASETS, orc_compress, orc_decompress, ptr
+from helpers import DATASETS, golden_npz, orc_compress, orc_decompress, ptr
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -22,7 +22,7 @@ def test_compat_vectors(oracle, fname):
 
 
 def test_reference_written_chunks(oracle):
-    z = np.load(os.path.join(GOLDEN, "ref_chunks.npz"))
+    z = golden_npz("ref_chunks.npz")
     meta = [m.split(",") for m in z["meta"]]
     assert len(meta) > 100
     for k, (cname, shuffle, dname, n, T, clevel, nth, bs, sm) in enumerate(meta):

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import deflate_builder as D
-from helpers import DATASETS, orc_decompress, ptr, ref_compress
+from helpers import DATASETS, golden_npz, orc_decompress, ptr, ref_compress
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 # verdicts of the reference's zlib for tests/deflate_builder.py: cases() (name -> bytes produced, 0 = rejected), recorded with
@@ -77,7 +77,7 @@ def test_compat_zlib_vectors(oracle, fname):
 
 
 def test_committed_reference_chunks(oracle):
-    z = np.load(os.path.join(GOLDEN, "ref_zlib_chunks.npz"))
+    z = golden_npz("ref_zlib_chunks.npz")
     meta = [m.split(",") for m in z["meta"]]
     assert len(meta) >= 24
     for k, (dname, n, T, clevel, shuffle, bs) in enumerate(meta):
@@ -130,7 +130,7 @@ def test_corrupt_streams_against_reference(oracle, ref):
 
 
 def test_truncated_and_corrupt_chunks_fail_cleanly(oracle):
-    z = np.load(os.path.join(GOLDEN, "ref_zlib_chunks.npz"))
+    z = golden_npz("ref_zlib_chunks.npz")
     chunk = z["c0"]; n = int(z["meta"][0].split(",")[1])
     rng = np.random.default_rng(3)
     for trial in range(300):

@@ -9,7 +9,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import DATASETS, orc_decompress, ptr, ref_compress
+from helpers import DATASETS, golden_npz, orc_decompress, ptr, ref_compress
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -22,7 +22,7 @@ def test_compat_zstd_vectors(oracle, fname):
 
 
 def test_committed_reference_chunks(oracle):
-    z = np.load(os.path.join(GOLDEN, "ref_zstd_chunks.npz"))
+    z = golden_npz("ref_zstd_chunks.npz")
     meta = [m.split(",") for m in z["meta"]]
     assert len(meta) >= 24
     for k, (dname, n, T, clevel, shuffle, bs) in enumerate(meta):
@@ -32,7 +32,7 @@ def test_committed_reference_chunks(oracle):
 
 
 def test_truncated_and_corrupt_frames_fail_cleanly(oracle):
-    z = np.load(os.path.join(GOLDEN, "ref_zstd_chunks.npz"))
+    z = golden_npz("ref_zstd_chunks.npz")
     chunk = z["c0"]; n = int(z["meta"][0].split(",")[1])
     rng = np.random.default_rng(3)
     for trial in range(300):

@@ -11,14 +11,14 @@ import tempfile
 import numpy as np
 import pytest
 
-from helpers import ptr
+from helpers import golden_npz, ptr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
 def _frames():
-    z = np.load(os.path.join(GOLDEN, "ref_zstd_chunks.npz"))
+    z = golden_npz("ref_zstd_chunks.npz")
     chunks = [z[f"c{k}"] for k in range(len(z["meta"]))]
     chunks += [np.fromfile(f, np.uint8) for f in sorted(glob.glob(os.path.join(GOLDEN, "compat", "*zstd*.cdata")))]
     for ch in chunks:

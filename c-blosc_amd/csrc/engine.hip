@@ -41,28 +41,58 @@ static std::atomic<bool> g_warned{false};
   } while (0)
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+struct Carver {   // layout helper: sub-allocations inside one arena
+  size_t off = 0; size_t take(size_t bytes, size_t align = 256) { off = align_up(off, align); size_t r = off; off += bytes; return r; }
+};
 
-// Experiment switches of the placement / scheduling studies (scripts/placement_*.py): read ONCE per process - a getenv on a production path races with a
-// concurrent setenv of the caller - and clamped: the skew shifts the arena's base inside its allocation, 0 .. 64 MiB.
-static size_t arena_skew_bytes() {
+// ---------------------------------------------------------------------------------------------
+// switches: every BLOSC_AMD_* name the engine reads (INTEGRATION.md has the users' table; BLOSC_AMD_SCHED is queue_order.h's)
+// ---------------------------------------------------------------------------------------------
+// Two readers.  switch_every_call: for what a test flips between two calls of one process.  SWITCH_ONCE: read at first use and kept -
+// a getenv on a production path races with a concurrent setenv of the caller.  SWITCH_SET: "set at all", whatever the value.
+constexpr long SWITCH_SET = -0x7fffffffL;
+static long switch_every_call(const char* name, long dflt) {
+  const char* e = getenv(name);
+  return dflt == SWITCH_SET ? (e != nullptr) : (e ? atol(e) : dflt);
+}
+#define SWITCH_ONCE(name, dflt) ([] { static const long v = switch_every_call(name, dflt); return v; }())
 #ifdef BAMD_ENV_EVERY_CALL      // (the placement scripts move the skew between re-allocations inside ONE process: make tune NAME=env DEFS=-DBAMD_ENV_EVERY_CALL)
-  const
+#define SWITCH_PLACEMENT switch_every_call
 #else
-  static const
+#define SWITCH_PLACEMENT SWITCH_ONCE
 #endif
-  size_t v = [] {
-    const char* sk = getenv("BLOSC_AMD_ARENA_SKEW_KIB");
-    long k = sk ? atol(sk) : 0;
-    if (k < 0) k = 0;
-    if (k > 65536) k = 65536;
-    return (size_t)k << 10;
-  }();
-  return v;
-}
-static bool debug_cost_enabled() {
-  static const bool v = getenv("BLOSC_AMD_DEBUG_COST") != nullptr;
-  return v;
-}
+#ifndef BAMD_LZ4HC_DEFAULT
+#define BAMD_LZ4HC_DEFAULT 1   // "lz4hc" without BLOSC_AMD_LZ4HC in the environment: 1 = LZ4HC-grade search, 0 = plain LZ4 match finder
+#endif
+#ifndef BAMD_ZSTD_TABLES_DEFAULT
+#define BAMD_ZSTD_TABLES_DEFAULT 1   // measured on MI355X (profiles/r03/r03a_encopts_bench_cfg4t.json): bench19 ratio 18.3 -> 23.8 for +5.6 % encode time
+#endif
+static bool is_on(long v) { return (int)v != 0; }      // every flag parses as atoi(...) != 0
+// -- once per process --
+static bool debug_cost_enabled()  { return is_on(SWITCH_ONCE("BLOSC_AMD_DEBUG_COST", SWITCH_SET)); }   // table-cache hits and decode plane costs on stderr
+static bool hosttime_on()         { return is_on(SWITCH_ONCE("BLOSC_AMD_HOSTTIME", 0)); }      // host time per phase of the batched calls, printed at release
+static bool table_cache_enabled() { return is_on(SWITCH_ONCE("BLOSC_AMD_TABLE_CACHE", 1)); }   // 0: every call builds and uploads its block table and queues
+static bool fuse_enabled()        { return is_on(SWITCH_ONCE("BLOSC_AMD_FUSE", 1)); }          // 0: (un)shuffle in kernels of their own (k_shuffle / k_unshuffle ...)
+static bool span_enabled()        { return is_on(SWITCH_ONCE("BLOSC_AMD_SPANS", 1)); }         // 0: decoded periodic planes go through the scratch like every other plane
+static bool periodic_enabled()    { return is_on(SWITCH_ONCE("BLOSC_AMD_PERIODIC", 1)); }      // 0: every plane goes through the match finder (no periodic-plane shortcut)
+// Zstd decode: 2 = two-phase path, 16 frames per wave, tables in a global scratch (k_zstd2.hip); 1 = the same with the tables in LDS (one wave
+// per CU); 0 = one wave per frame for everything (k_zstd_streams).  8 GiB of reference-written frames, mode 0 / 2: bench19 107 / 50 ms,
+// linspace 17.8 / 15.9, random walk 23.7 / 16.5 (profiles/r02/r02f_zstd_decode_modes.txt)
+static int zstd2_mode()           { return (int)SWITCH_ONCE("BLOSC_AMD_ZSTD2", 2); }
+static int contexts_wanted()      { return (int)SWITCH_ONCE("BLOSC_AMD_CONTEXTS", 8); }     // workspaces for concurrent callers, clamped to 1 .. kMaxCtx
+// placement experiment (scripts/placement_probe.py): the arenas' base this many KiB behind what hipMalloc returned, clamped to 0 .. 64 MiB
+static size_t arena_skew_bytes()  { const long k = SWITCH_PLACEMENT("BLOSC_AMD_ARENA_SKEW_KIB", 0); return (size_t)(k < 0 ? 0 : (k > 65536 ? 65536 : k)) << 10; }
+// -- every call --
+static bool debug_enabled()        { return is_on(switch_every_call("BLOSC_AMD_DEBUG", SWITCH_SET)); }      // arena allocations and the topology probe on stderr
+static bool single_queue_forced()  { return is_on(switch_every_call("BLOSC_AMD_SINGLE_QUEUE", 0)); }        // read by probe_topology, once per device set-up
+static bool lz4hc_search_enabled() { return is_on(switch_every_call("BLOSC_AMD_LZ4HC", BAMD_LZ4HC_DEFAULT)); }         // 0: "lz4hc" served by the plain LZ4 match finder
+static bool zstd_tables_enabled()  { return is_on(switch_every_call("BLOSC_AMD_ZSTD_TABLES", BAMD_ZSTD_TABLES_DEFAULT)); }   // 0: predefined sequence tables only
+static bool zstd_search_enabled(int clevel) { return is_on(switch_every_call("BLOSC_AMD_ZSTD_SEARCH", clevel >= 6)); } // LZ4HC-grade search in front of the Zstd writer
+static bool zlib_search_enabled()  { return is_on(switch_every_call("BLOSC_AMD_ZLIB_SEARCH", 1)); }         // ... in front of the zlib writer
+static bool zstd_huffman_enabled() { return is_on(switch_every_call("BLOSC_AMD_ZSTD_HUFFMAN", 0)); }        // Huffman-coded literals in Zstd frames
+static bool zlib_dynamic_enabled() { return is_on(switch_every_call("BLOSC_AMD_ZLIB_DYNAMIC", 1)); }        // 0: fixed Huffman codes
+// (the instrumented build's BLOSC_AMD_ENC_PROFILE / BLOSC_AMD_DEC_PROFILE / BLOSC_AMD_ZSTD_PROFILE name files, not values: StreamProfile below)
+
 struct DeviceArena {   // one grow-only device allocation carved up per call
   uint8_t* base = nullptr;
   uint8_t* raw = nullptr;   // what hipMalloc returned (base = raw + skew; BLOSC_AMD_ARENA_SKEW_KIB, a placement experiment: scripts/placement_probe.py)
@@ -75,7 +105,7 @@ struct DeviceArena {   // one grow-only device allocation carved up per call
     HIP_TRY(hipMalloc((void**)&raw, want + skew));
     base = raw + skew;
     cap = want;
-    if (getenv("BLOSC_AMD_DEBUG")) fprintf(stderr, "[blosc_amd] device arena %p, %zu MiB\n", (void*)base, want >> 20);
+    if (debug_enabled()) fprintf(stderr, "[blosc_amd] device arena %p, %zu MiB\n", (void*)base, want >> 20);
     return 0;
   }
   void release() { if (raw) (void)hipFree(raw); raw = base = nullptr; cap = 0; }
@@ -134,12 +164,58 @@ struct EngineState {
   // device from one call to the next (round 6).  A call that finds its own block table, fusion flags and SET of expensive planes (order_signature) equal to the ones the tables
   // were made from neither builds the queues nor uploads anything but its chunk descriptors: callers send equal-shaped chunks call after call
   // (bench/bench.c:383 does), and the host side of a call is time the device stands idle.  Buffers of their own: the call arena is overwritten by whatever call comes next.
+  //
+  // The protocol of a call, all of it here: begin() compares the call's key with the one the tables on the device were made from.  A miss
+  // marks the cache invalid, has the caller's builder fill `queues` (and `zqueues`), and reserves device and pinned room; upload() enqueues
+  // the copies; commit() - AFTER the call's synchronisation, when the uploads are known to have arrived - adopts the key.  A call that
+  // fails in between therefore leaves valid == false, and the next one builds again.
+  struct TableKey { std::vector<BlockDesc> blocks; std::vector<uint32_t> modes; std::vector<int> order; int nq = 0; };
   struct TableCache {
-    std::vector<BlockDesc> blocks; std::vector<uint32_t> modes; std::vector<int> order; int nq = 0;
-    DeviceArena tabs; size_t o_queues = 0, o_zqueues = 0, sh_at = 0; int32_t ntasks = 0; bool valid = false;
-    bool same(const std::vector<BlockDesc>& b, const std::vector<uint32_t>& m, const std::vector<int>& o, int q) const {
-      return valid && nq == q && blocks.size() == b.size() && modes == m && order == o && (b.empty() || memcmp(blocks.data(), b.data(), b.size() * sizeof(BlockDesc)) == 0);
+    TableKey key; bool valid = false;
+    DeviceArena tabs; size_t o_queues = 0, o_zqueues = 0, sh_at = 0; int32_t ntasks = 0;      // the block table lies at tabs.base
+    bool hit = false;                                                                          // this call's begin()
+    std::vector<int32_t> queues, zqueues; size_t p_blocks = 0, p_queues = 0, p_zqueues = 0;    // a miss's tables on their way to the device
+    bool same(const TableKey& k) const {
+      return valid && key.nq == k.nq && key.blocks.size() == k.blocks.size() && key.modes == k.modes && key.order == k.order &&
+             (k.blocks.empty() || memcmp(key.blocks.data(), k.blocks.data(), k.blocks.size() * sizeof(BlockDesc)) == 0);
     }
+    // queue_words / zqueue_words: device room of the two queue tables (0: as long as what `build` made)
+    template <class Build>
+    int begin(const char* what, const TableKey& k, size_t queue_words, size_t zqueue_words, Carver& pin, Build&& build) {
+      hit = table_cache_enabled() && same(k);
+      if (debug_cost_enabled()) fprintf(stderr, "[blosc_amd] %s: block table and queues %s\n", what, hit ? "still on the device" : "built and uploaded");
+      if (hit) return 0;
+      valid = false;
+      queues.clear(); zqueues.clear();
+      build(*this);
+      const size_t nblk = k.blocks.size();
+      Carver tcv;
+      tcv.take(sizeof(BlockDesc) * (nblk ? nblk : 1));
+      o_queues = tcv.take(sizeof(int32_t) * (queue_words ? queue_words : queues.size()));
+      if (zqueue_words) o_zqueues = tcv.take(sizeof(int32_t) * zqueue_words);
+      if (tabs.ensure(tcv.off)) return -1;
+      p_blocks = pin.take(sizeof(BlockDesc) * (nblk ? nblk : 1));
+      p_queues = pin.take(sizeof(int32_t) * queues.size());
+      p_zqueues = pin.take(sizeof(int32_t) * (zqueues.size() + 1));
+      return 0;
+    }
+    int upload(const TableKey& k, uint8_t* P, hipStream_t stream) {      // P: the pinned arena `pin` of begin() was carved for
+      if (hit) return 0;
+      const struct { size_t dev, pin; const void* from; size_t bytes; } up[3] = {
+        {0, p_blocks, k.blocks.data(), sizeof(BlockDesc) * k.blocks.size()},
+        {o_queues, p_queues, queues.data(), sizeof(int32_t) * queues.size()},
+        {o_zqueues, p_zqueues, zqueues.data(), sizeof(int32_t) * zqueues.size()}};
+      for (const auto& u : up) {
+        if (!u.bytes) continue;
+        memcpy(P + u.pin, u.from, u.bytes);
+        HIP_TRY(hipMemcpyAsync(tabs.base + u.dev, P + u.pin, u.bytes, hipMemcpyHostToDevice, stream));
+      }
+      return 0;
+    }
+    void commit(TableKey& k) { if (!hit) { std::swap(key, k); valid = true; } }
+    BlockDesc* d_blocks() const { return (BlockDesc*)tabs.base; }
+    const int32_t* d_qoff() const { return (const int32_t*)(tabs.base + o_queues); }        // qoff[9], then the queue lists
+    const int32_t* d_zqoff() const { return (const int32_t*)(tabs.base + o_zqueues); }
     void drop() { valid = false; tabs.release(); }
   } enc_tabs, dec_tabs;
   hipStream_t own = nullptr;   // host-buffer calls that name no stream run here (non-blocking: see the contexts below)
@@ -181,8 +257,7 @@ static int ctx_count() {
 #ifdef BAMD_WAVE_EMU
   return 1;                                // the wavefront emulator (tests/tools) runs one launch at a time
 #else
-  static const int n = [] { const char* e = getenv("BLOSC_AMD_CONTEXTS"); int v = e ? atoi(e) : kMaxCtx; return v < 1 ? 1 : (v > kMaxCtx ? kMaxCtx : v); }();
-  return n;
+  return std::min(std::max(contexts_wanted(), 1), kMaxCtx);
 #endif
 }
 static std::mutex g_pick_mu;                // context selection is serialised: a probing thread never makes another one miss "its" context
@@ -222,7 +297,7 @@ __global__ void k_probe_xcc(uint32_t* hist) {
   if (threadIdx.x == 0) atomicAdd(&hist[__builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u], 1u);
 }
 static void probe_topology(EngineState& st) {
-  st.single_queue = getenv("BLOSC_AMD_SINGLE_QUEUE") && atoi(getenv("BLOSC_AMD_SINGLE_QUEUE")) != 0;
+  st.single_queue = single_queue_forced();
   if (st.single_queue) return;
   uint32_t* d = nullptr; uint32_t h[16] = {0};
   bool ok = hipMalloc((void**)&d, sizeof h) == hipSuccess && hipMemset(d, 0, sizeof h) == hipSuccess;
@@ -234,7 +309,7 @@ static void probe_topology(EngineState& st) {
   for (int x = 0; ok && x < 16; x++) ok = h[x] == (x < 8 ? 8u : 0u);
   if (!ok) {
     st.single_queue = true;
-    if (getenv("BLOSC_AMD_DEBUG")) fprintf(stderr, "blosc_amd: workgroups are not dealt round-robin to 8 XCDs here; using one task queue and unfused filters\n");
+    if (debug_enabled()) fprintf(stderr, "blosc_amd: workgroups are not dealt round-robin to 8 XCDs here; using one task queue and unfused filters\n");
   }
 }
 
@@ -289,7 +364,7 @@ static int ensure_device(EngineState& st) {
   // which has no in-kernel hand-off at all, whatever the probe above saw.
   if (!st.single_queue && !(have_props && (strncmp(pr.gcnArchName, "gfx950", 6) == 0 || strncmp(pr.gcnArchName, "gfx942", 6) == 0))) {
     st.single_queue = true;
-    if (getenv("BLOSC_AMD_DEBUG")) fprintf(stderr, "blosc_amd: %s is not on the allow-list of the relaxed in-kernel hand-off; using one task queue and unfused filters\n", have_props ? pr.gcnArchName : "(unknown device)");
+    if (debug_enabled()) fprintf(stderr, "blosc_amd: %s is not on the allow-list of the relaxed in-kernel hand-off; using one task queue and unfused filters\n", have_props ? pr.gcnArchName : "(unknown device)");
   }
   st.enc_cost_valid = st.dec_cost_valid = false;
   st.device_ok = true;
@@ -306,10 +381,18 @@ static hipEvent_t prof_event(EngineState& st) {
 // (where do the ~0.4 ms per call outside the kernels go?)
 struct HostTime { double t[2][6] = {}; long calls[2] = {}; };
 static HostTime g_ht;
-static bool hosttime_on() { static const bool on = getenv("BLOSC_AMD_HOSTTIME") && atoi(getenv("BLOSC_AMD_HOSTTIME")) != 0; return on; }
 static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 static std::mutex g_ht_mu;     // several contexts run at once: the accumulators are shared
-#define HT_MARK(dir, i) do { if (hosttime_on()) { const double t_ = now_ms(); { std::lock_guard<std::mutex> l_(g_ht_mu); g_ht.t[dir][i] += t_ - ht_last; } ht_last = t_; } } while (0)
+struct HostPhases {            // one batched call's clock: mark(i) books the time since the last mark (or the constructor) on phase i
+  const int dir; double last = 0.0;
+  explicit HostPhases(int dir_) : dir(dir_) { if (hosttime_on()) { last = now_ms(); std::lock_guard<std::mutex> l(g_ht_mu); g_ht.calls[dir]++; } }
+  void mark(int i) {
+    if (!hosttime_on()) return;
+    const double t = now_ms();
+    std::lock_guard<std::mutex> l(g_ht_mu);
+    g_ht.t[dir][i] += t - last; last = t;
+  }
+};
 struct ProfScope {
   EngineState& st; hipStream_t s; const char* name; hipEvent_t a{}, b{}; bool on;
   ProfScope(EngineState& st_, hipStream_t s_, const char* n) : st(st_), s(s_), name(n), on(g_prof.load(std::memory_order_relaxed)) {
@@ -333,14 +416,6 @@ __global__ void k_gather_headers(const uint8_t* const* __restrict__ srcs, uint8_
   out[i] = srcs[i >> 4][i & 15];
 }
 
-// ---------------------------------------------------------------------------------------------
-// layout helper: sub-allocations inside one arena
-// ---------------------------------------------------------------------------------------------
-struct Carver {
-  size_t off = 0;
-  size_t take(size_t bytes, size_t align = 256) { off = align_up(off, align); size_t r = off; off += bytes; return r; }
-};
-
 // grid of a persistent one-wave-per-workgroup kernel: as many waves as the device keeps resident
 static unsigned persistent_grid(const EngineState& st, size_t nitems, int waves_per_cu) {
   const int cus = st.cus > 0 ? st.cus : 256;
@@ -355,38 +430,15 @@ static dim3 grid1(size_t n, int per) { return dim3((unsigned)((n + per - 1) / pe
 // ---------------------------------------------------------------------------------------------
 // compress
 // ---------------------------------------------------------------------------------------------
-// BLOSC_AMD_FUSE=0 keeps the byte (un)shuffle in kernels of its own (k_shuffle / k_unshuffle) instead of
-// running it as work of the encode / decode kernels
-// BLOSC_AMD_SPANS=0: decoded periodic planes go through the scratch like every other plane
-static bool span_enabled() { static const bool on = !(getenv("BLOSC_AMD_SPANS") && atoi(getenv("BLOSC_AMD_SPANS")) == 0); return on; }
-// BLOSC_AMD_PERIODIC=0: every plane goes through the match finder (A/B switch for the periodic-plane shortcut of the fused shuffle)
-#ifndef BAMD_LZ4HC_DEFAULT
-#define BAMD_LZ4HC_DEFAULT 1   // "lz4hc" without BLOSC_AMD_LZ4HC in the environment: 1 = LZ4HC-grade search, 0 = plain LZ4 match finder
-#endif
-static bool lz4hc_search_enabled() { const char* e = getenv("BLOSC_AMD_LZ4HC"); return e ? atoi(e) != 0 : (BAMD_LZ4HC_DEFAULT != 0); }
-#ifndef BAMD_ZSTD_TABLES_DEFAULT
-#define BAMD_ZSTD_TABLES_DEFAULT 1   // measured on MI355X (profiles/r03/r03a_encopts_bench_cfg4t.json): bench19 ratio 18.3 -> 23.8 for +5.6 % encode time
-#endif
-static bool zstd_tables_enabled() { const char* e = getenv("BLOSC_AMD_ZSTD_TABLES"); return e ? atoi(e) != 0 : (BAMD_ZSTD_TABLES_DEFAULT != 0); }
-static bool env_flag(const char* name) { const char* e = getenv(name); return e && atoi(e) != 0; }
-static bool env_flag_or(const char* name, bool dflt) { const char* e = getenv(name); return e ? atoi(e) != 0 : dflt; }
-static bool periodic_enabled() { static const bool on = !(getenv("BLOSC_AMD_PERIODIC") && atoi(getenv("BLOSC_AMD_PERIODIC")) == 0); return on; }
-// BLOSC_AMD_ZSTD2: 2 (default) = two-phase path, 16 frames per wave, tables in a global scratch (k_zstd2.hip);
-// 1 = the same with the tables in LDS (one wave per CU); 0 = one wave per frame for everything (k_zstd_streams).
-// 8 GiB of reference-written frames, mode 0 / 2: bench19 107 / 50 ms, linspace 17.8 / 15.9, random walk 23.7 / 16.5
-// (profiles/r02/r02f_zstd_decode_modes.txt)
-static int zstd2_mode() { static const int m = getenv("BLOSC_AMD_ZSTD2") ? atoi(getenv("BLOSC_AMD_ZSTD2")) : 2; return m; }
 // typesizes whose byte (un)shuffle runs inside the codec kernels (enc_shuffle.h, k_decode.hip: unshuffle_block_wave); the others, and everything
 // under BLOSC_AMD_FUSE=0 / BLOSC_AMD_SINGLE_QUEUE=1, go through the stand-alone filter kernels
 static bool fused_typesize(int T) { return T >= 2 && T <= 32; }          // 2 / 4 / 8 / 16: register transposes; the others up to 32 (round 4): an LDS tile of the wave
 static bool fused_fast_typesize(int T) { return T == 8 || T == 4 || T == 2 || T == 16; }     // what the Zstd / zlib kernels' own-block unshuffle handles
 // bitshuffle chunks of these typesizes are (un)shuffled inside the codec kernels as well (round 4: bitshuffle_block_wave_T / bitunshuffle_block_wave)
 static bool bitunshuffle_fused_host(int T) { return T == 1 || T == 2 || T == 4 || T == 8; }      // 8: round 5 (float64 + bitshuffle is a mainstream caller setting)
-static bool fuse_enabled() { static const bool on = !(getenv("BLOSC_AMD_FUSE") && atoi(getenv("BLOSC_AMD_FUSE")) == 0); return on; }
 
 // the stream a call runs on: the caller's, or - host buffers and no stream named - the context's own
 // What the queue builders make of the cost feedback for the stream counts of this batch's blocks: the part of a queue's identity that is not in the block table
-static bool table_cache_enabled() { static const bool on = !(getenv("BLOSC_AMD_TABLE_CACHE") && atoi(getenv("BLOSC_AMD_TABLE_CACHE")) == 0); return on; }
 static void order_signature(const std::vector<BlockDesc>& blocks, const uint32_t* cost, bool valid, std::vector<int>& sig) {
   bool seen[257] = {false};
   for (const BlockDesc& b : blocks) seen[b.nstreams < 0 ? 0 : (b.nstreams > 256 ? 256 : b.nstreams)] = true;
@@ -410,231 +462,252 @@ static int call_stream(EngineState& st, bool host_buffers, hipStream_t* stream) 
   return 0;
 }
 
+static int filter_tile_count(int32_t elems, int per_tile) { const int t = (elems + per_tile - 1) / per_tile; return t < 1 ? 1 : t; }
+
+// Sub-offsets of the area that holds a call's per-chunk result (encode) / status (decode) words: the ticket words of the per-XCD queues
+// begin kTicketGap bytes behind the last of them; what follows the tickets is the direction's own (decode: one arrival counter per block)
+constexpr size_t kTicketGap = 32;
+constexpr size_t kEncTicketWords = 16;     // 8 of the task queues + 8 of the shuffle lists
+constexpr size_t kDecTicketWords = 8;
+static size_t ticket_offset(size_t nchunks) { return sizeof(int32_t) * nchunks + kTicketGap; }
+
+// Host-pointer calls: every live chunk's input and output get a 256-byte aligned slot in st.io, the inputs in front of the outputs.
+// add() per live chunk -> reserve() -> stage() per live chunk, in the same order -> (kernels) -> collect().  Device-pointer calls: all no-ops.
+struct HostStaging {
+  const bool host;
+  size_t in_bytes = 0, out_bytes = 0, in_at = 0, out_at = 0;
+  uint8_t *in_base = nullptr, *out_base = nullptr;
+  void add(size_t in, size_t out) { if (host) { in_bytes = align_up(in_bytes, 256) + in; out_bytes = align_up(out_bytes, 256) + out; } }
+  int reserve(DeviceArena& io) {
+    if (!host) return 0;
+    const size_t out_off = align_up(in_bytes + 256, 256);
+    if (io.ensure(out_off + out_bytes + 512)) return -1;
+    in_base = io.base; out_base = io.base + out_off; return 0;
+  }
+  // enqueues the copy of the chunk's input and points c.src / c.dst at its two slots
+  int stage(ChunkDesc& c, const void* src, size_t in, size_t out, hipStream_t stream) {
+    if (!host) return 0;
+    in_at = align_up(in_at, 256); out_at = align_up(out_at, 256);
+    HIP_TRY(hipMemcpyAsync(in_base + in_at, src, in, hipMemcpyHostToDevice, stream));
+    c.src = in_base + in_at; c.dst = out_base + out_at;
+    in_at += in; out_at += out; return 0;
+  }
+  // results[i] bytes of every live chunk with a positive result back to the caller's buffer, then waits for them
+  int collect(int n, const Job* jobs, const std::vector<ChunkDesc>& chunks, const std::vector<uint8_t>& live, const int* results, hipStream_t stream) {
+    if (!host) return 0;
+    for (int i = 0; i < n; i++)
+      if (live[(size_t)i] && results[i] > 0) HIP_TRY(hipMemcpyAsync(jobs[i].dst, chunks[(size_t)i].dst, (size_t)results[i], hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return 0;
+  }
+};
+
+// Instrumented build only (make prof; scripts/enc_phase.py, dec_phase.py, zstd_phase.py): a kernel writes 64 bytes per stream through one more,
+// last parameter.  BAMD_STREAM_PROFILE in front of the launch allocates and clears them where the switch names a file; at the end of the scope
+// it waits for the kernel, writes the file and frees them.  BAMD_PROF_ARG is that last argument.  The product build has neither.
+#ifdef BAMD_PROFILE_DECODE
+struct StreamProfile {
+  uint32_t* d = nullptr; const char* path; size_t bytes; hipStream_t stream;
+  StreamProfile(const char* switch_name, size_t nstr, hipStream_t s) : path(getenv(switch_name)), bytes(nstr * 64), stream(s) {
+    if (path && hipMalloc((void**)&d, bytes) == hipSuccess) (void)hipMemsetAsync(d, 0, bytes, stream);
+  }
+  ~StreamProfile() {
+    if (!d) return;
+    std::vector<uint32_t> h(bytes / 4);
+    (void)hipStreamSynchronize(stream); (void)hipMemcpy(h.data(), d, bytes, hipMemcpyDeviceToHost); (void)hipFree(d);
+    FILE* f = fopen(path, "wb");
+    if (f) { fwrite(h.data(), 4, h.size(), f); fclose(f); }
+  }
+};
+#define BAMD_STREAM_PROFILE(var, switch_name, nstr) StreamProfile var(switch_name, nstr, stream)
+#define BAMD_PROF_ARG(var) , var.d
+#else
+#define BAMD_STREAM_PROFILE(var, switch_name, nstr)
+#define BAMD_PROF_ARG(var)
+#endif
+
+// What the per-chunk loop of a compress call adds up: the tables and the sizes of the scratch areas
+struct EncodeBatch {
+  std::vector<ChunkDesc> chunks; std::vector<uint8_t> live;
+  EngineState::TableKey key;                         // key.blocks: the block table
+  size_t nstr = 0, filt_bytes = 0, stage_bytes = 0;  // (the stream table itself is made on the device: k_encode_plan)
+  int tiles_shuf = 0, tiles_bit = 0; bool any_shuf = false, any_bit = false;
+  explicit EncodeBatch(int n) : chunks((size_t)n), live((size_t)n, 0) {}
+};
+
+// Parameter checks and geometry of chunk i of n (blosc.c:1062-1145, :1148-1247).  false: nothing runs for it, *result is its outcome.
+static bool add_encode_chunk(const CompressParams& p, const Job& job, int i, int n, bool may_fuse, EncodeBatch& B, int* result) {
+  ChunkDesc& c = B.chunks[(size_t)i];
+  std::vector<BlockDesc>& blocks = B.key.blocks;
+  memset(&c, 0, sizeof c);
+  c.mode = CH_SKIP;
+  size_t nbytes = job.srcsize, destsize = job.dstsize, typesize = p.typesize;
+  const int codec = p.codec;
+  *result = 0;
+  if (nbytes > (size_t)kMaxBufferSize || destsize < (size_t)kMaxOverhead) return false;
+  if (destsize - kMaxOverhead > nbytes) destsize = nbytes + kMaxOverhead;
+  if (p.clevel < 0 || p.clevel > 9 || (p.doshuffle != 0 && p.doshuffle != 1 && p.doshuffle != 2) || typesize == 0) { *result = -10; return false; }
+  if (typesize > (size_t)kMaxTypeSize) typesize = 1;
+  if (codec != kBloscLZ && codec != kLZ4 && codec != kLZ4HC && codec != kZlib && codec != kZstd) { *result = -5; return false; }  // blosc.c:1197-1207 (Snappy: not built)
+  const int32_t T = (int32_t)typesize, nb = (int32_t)nbytes;
+  const int32_t bs = compute_blocksize(p.clevel, T, nb, p.forced_blocksize, codec, p.splitmode);
+  const int32_t leftover = nb % bs, nblocks = nb / bs + (leftover > 0 ? 1 : 0);
+  const bool memcpyed = (p.clevel == 0) || (nb < kMinBufferSize);
+  const int split = split_block(codec, T, bs, p.splitmode);
+  int flags = ((!split) << 4) | (codec_to_format(codec) << 5);
+  if (memcpyed) flags |= kFlagMemcpyed;
+  if (p.doshuffle == 1) flags |= kFlagShuffle;
+  if (p.doshuffle == 2) flags |= kFlagBitShuffle;
+  if (memcpyed && (size_t)nb + kMaxOverhead > destsize) return false;  // blosc.c:1254-1257
+
+  c.src = (const uint8_t*)job.src; c.dst = (uint8_t*)job.dst;
+  c.nbytes = nb; c.cbytes = (int32_t)destsize; c.blocksize = bs; c.typesize = T;
+  c.nblocks = nblocks; c.leftover = leftover; c.nsplits = split ? T : 1;
+  c.fmt = codec_to_format(codec); c.clevel = (codec == kLZ4HC) ? 9 : p.clevel; c.hdr_flags = flags;
+  c.mode = 0;
+  c.first_block = (int32_t)blocks.size(); c.first_stream = (int32_t)B.nstr;
+  if (memcpyed) c.mode |= CH_MEMCPYED;
+  else if (p.doshuffle == 1 && T > 1) { c.mode |= CH_SHUFFLE; if (fused_typesize(T) && fuse_enabled() && may_fuse) c.mode |= CH_FUSED_SHUF; }
+  else if (p.doshuffle == 2) { c.mode |= CH_BITSHUFFLE; if (bitunshuffle_fused_host(T) && fuse_enabled() && may_fuse) c.mode |= CH_FUSED_SHUF; }
+  const bool filtered = (c.mode & (CH_SHUFFLE | CH_BITSHUFFLE)) != 0;
+  if (filtered && !(c.mode & CH_FUSED_SHUF)) {       // (fused: shuffled by tasks of the encode kernel)
+    if (c.mode & CH_SHUFFLE) { B.any_shuf = true; B.tiles_shuf = std::max(B.tiles_shuf, filter_tile_count(bs / T, shuffle_tile_elems(T))); }
+    else { B.any_bit = true; B.tiles_bit = std::max(B.tiles_bit, filter_tile_count(bs / T, bitshuffle_tile_elems(T))); }
+  }
+  // blocks; their streams (in = the block's bytes in the filtered image or the source, out = its staging slot) are k_encode_plan's
+  if (blocks.capacity() < blocks.size() + (size_t)nblocks) blocks.reserve(std::max(blocks.size() + (size_t)nblocks, (size_t)(n - i) * (size_t)nblocks + blocks.size()));   // (equal chunks: one allocation)
+  for (int32_t j = 0; j < nblocks; j++) {
+    BlockDesc b;
+    b.chunk = i; b.blk = j; b.first_stream = (int32_t)B.nstr;
+    const bool last = (j == nblocks - 1) && leftover > 0;
+    b.nstreams = memcpyed ? 0 : ((split && !last) ? T : 1);
+    b.bsize = last ? leftover : bs; b.flags = 0;
+    B.nstr += (size_t)b.nstreams;
+    blocks.push_back(b);
+  }
+  if (!memcpyed) {
+    if (filtered) B.filt_bytes = align_up(B.filt_bytes, 256) + (size_t)nb;
+    B.stage_bytes = align_up(B.stage_bytes, 256) + (size_t)nb;
+  }
+  return true;
+}
+
 int engine_compress_batch(const CompressParams& p, int n, const Job* jobs, int* results, bool device_ptrs,
                           hipStream_t stream) {
   if (n <= 0) return 0;
-  CtxGuard ctx;
-  EngineState& st = *ctx.st;
+  CtxGuard ctx; EngineState& st = *ctx.st;
   if (ensure_device(st) || call_stream(st, !device_ptrs, &stream)) return -1;
-
-  double ht_last = hosttime_on() ? now_ms() : 0.0; if (hosttime_on()) { std::lock_guard<std::mutex> l_(g_ht_mu); g_ht.calls[0]++; }
-  std::vector<ChunkDesc> chunks((size_t)n);
-  std::vector<BlockDesc> blocks;
-  size_t nstr = 0;                                   // the stream table itself is made on the device (k_encode_plan)
-  std::vector<uint8_t> live((size_t)n, 0);
-  size_t filt_bytes = 0, stage_bytes = 0, io_src = 0, io_dst = 0;
-  int tiles_shuf = 0, tiles_bit = 0;
-  bool any_shuf = false, any_bit = false;
-
-  // ---- per-chunk parameter checks and geometry (blosc.c:1062-1145, :1148-1247) ----
+  HostPhases ht(0);
+  // ---- check and lay out the chunks ----
+  EncodeBatch B(n);
+  HostStaging io{!device_ptrs};
+  std::vector<ChunkDesc>& chunks = B.chunks;
   for (int i = 0; i < n; i++) {
-    ChunkDesc& c = chunks[(size_t)i];
-    memset(&c, 0, sizeof c);
-    c.mode = CH_SKIP;
-    size_t nbytes = jobs[i].srcsize, destsize = jobs[i].dstsize, typesize = p.typesize;
-    if (nbytes > (size_t)kMaxBufferSize) { results[i] = 0; continue; }
-    if (destsize < (size_t)kMaxOverhead) { results[i] = 0; continue; }
-    if (destsize - kMaxOverhead > nbytes) destsize = nbytes + kMaxOverhead;
-    if (p.clevel < 0 || p.clevel > 9) { results[i] = -10; continue; }
-    if (p.doshuffle != 0 && p.doshuffle != 1 && p.doshuffle != 2) { results[i] = -10; continue; }
-    if (typesize == 0) { results[i] = -10; continue; }
-    if (typesize > (size_t)kMaxTypeSize) typesize = 1;
-    const int codec = p.codec;
-    if (codec != kBloscLZ && codec != kLZ4 && codec != kLZ4HC && codec != kZlib && codec != kZstd) { results[i] = -5; continue; }  // blosc.c:1197-1207 (Snappy: not built)
-    const int32_t T = (int32_t)typesize, nb = (int32_t)nbytes;
-    const int32_t bs = compute_blocksize(p.clevel, T, nb, p.forced_blocksize, codec, p.splitmode);
-    int32_t nblocks = nb / bs;
-    const int32_t leftover = nb % bs;
-    if (leftover > 0) nblocks++;
-    int flags = 0;
-    bool memcpyed = (p.clevel == 0) || (nb < kMinBufferSize);
-    if (memcpyed) flags |= kFlagMemcpyed;
-    if (p.doshuffle == 1) flags |= kFlagShuffle;
-    if (p.doshuffle == 2) flags |= kFlagBitShuffle;
-    const int split = split_block(codec, T, bs, p.splitmode);
-    flags |= (!split) << 4;
-    flags |= codec_to_format(codec) << 5;
-    if (memcpyed && (size_t)nb + kMaxOverhead > destsize) { results[i] = 0; continue; }  // blosc.c:1254-1257
-
-    c.src = (const uint8_t*)jobs[i].src; c.dst = (uint8_t*)jobs[i].dst;
-    c.nbytes = nb; c.cbytes = (int32_t)destsize; c.blocksize = bs; c.typesize = T;
-    c.nblocks = nblocks; c.leftover = leftover; c.nsplits = split ? T : 1;
-    c.fmt = codec_to_format(codec); c.clevel = (codec == kLZ4HC) ? 9 : p.clevel; c.hdr_flags = flags;
-    c.mode = 0;
-    c.first_block = (int32_t)blocks.size(); c.first_stream = (int32_t)nstr;
-    if (memcpyed) c.mode |= CH_MEMCPYED;
-    else if (p.doshuffle == 1 && T > 1) { c.mode |= CH_SHUFFLE; if (fused_typesize(T) && fuse_enabled() && !st.single_queue) c.mode |= CH_FUSED_SHUF; }
-    else if (p.doshuffle == 2) { c.mode |= CH_BITSHUFFLE; if (bitunshuffle_fused_host(T) && fuse_enabled() && !st.single_queue) c.mode |= CH_FUSED_SHUF; }
-    live[(size_t)i] = 1;
-    results[i] = 0;
-    if (!device_ptrs) { io_src = align_up(io_src, 256) + (size_t)nb; io_dst = align_up(io_dst, 256) + destsize; }
-    const bool filtered = (c.mode & (CH_SHUFFLE | CH_BITSHUFFLE)) != 0;
-    if (filtered) {
-      const int32_t N = bs / T;
-      if (c.mode & CH_FUSED_SHUF) { /* shuffled by tasks of the encode kernel */ }
-      else if (c.mode & CH_SHUFFLE) { any_shuf = true; int t = (N + shuffle_tile_elems(T) - 1) / shuffle_tile_elems(T); if (t < 1) t = 1; if (t > tiles_shuf) tiles_shuf = t; }
-      else { any_bit = true; int t = (N + bitshuffle_tile_elems(T) - 1) / bitshuffle_tile_elems(T); if (t < 1) t = 1; if (t > tiles_bit) tiles_bit = t; }
-    }
-    // blocks; their streams (in = the block's bytes in the filtered image or the source, out = its staging slot) are k_encode_plan's
-    if (blocks.capacity() < blocks.size() + (size_t)nblocks) blocks.reserve(std::max(blocks.size() + (size_t)nblocks, (size_t)(n - i) * (size_t)nblocks + blocks.size()));   // (equal chunks: one allocation)
-    for (int32_t j = 0; j < nblocks; j++) {
-      BlockDesc b;
-      b.chunk = i; b.blk = j; b.first_stream = (int32_t)nstr;
-      const bool last = (j == nblocks - 1) && leftover > 0;
-      b.nstreams = memcpyed ? 0 : ((split && !last) ? T : 1);
-      b.bsize = last ? leftover : bs; b.flags = 0;
-      nstr += (size_t)b.nstreams;
-      blocks.push_back(b);
-    }
-    if (!memcpyed) {
-      if (filtered) filt_bytes = align_up(filt_bytes, 256) + (size_t)nb;
-      stage_bytes = align_up(stage_bytes, 256) + (size_t)nb;
-    }
+    B.live[(size_t)i] = add_encode_chunk(p, jobs[i], i, n, !st.single_queue, B, &results[i]);
+    if (B.live[(size_t)i]) io.add((size_t)chunks[(size_t)i].nbytes, (size_t)chunks[(size_t)i].cbytes);
   }
-
-  const size_t nblk = blocks.size();
-  HT_MARK(0, 0);     // per-chunk geometry + block / stream tables
-  // ---- device workspace ----
-  Carver cv;
-  const size_t o_chunks = cv.take(sizeof(ChunkDesc) * (size_t)n);
-  const size_t o_streams = cv.take(sizeof(StreamDesc) * (nstr ? nstr : 1));
-  const size_t o_blkoff = cv.take(sizeof(int32_t) * (nblk ? nblk : 1));
-  const size_t o_results = cv.take(sizeof(int32_t) * (size_t)n + 96);   // + the 8 ticket counters of the encode queues + the 8 of the shuffle lists
-  // the block table and the queues: still on the device from the last call of this geometry, or built and uploaded now (EngineState::TableCache)
+  const size_t nblk = B.key.blocks.size(), nstr = B.nstr;
+  ht.mark(0);     // per-chunk geometry + block / stream tables
+  // ---- tables: the block table and the queues, still on the device from the last call of this geometry or built and uploaded now ----
   EngineState::TableCache& tc = st.enc_tabs;
-  const int nq = st.single_queue ? 1 : 8;
-  std::vector<uint32_t> tmodes((size_t)n);
-  for (int i = 0; i < n; i++) tmodes[(size_t)i] = chunks[(size_t)i].mode & CH_FUSED_SHUF;
-  std::vector<int> tsig;
-  order_signature(blocks, st.enc_cost, st.enc_cost_valid, tsig);
-  const bool tabs_hit = table_cache_enabled() && tc.same(blocks, tmodes, tsig, nq);
-  if (debug_cost_enabled()) fprintf(stderr, "[blosc_amd] compress: block table and queues %s\n", tabs_hit ? "still on the device" : "built and uploaded");
-  std::vector<int32_t> queues; size_t sh_at = tc.sh_at;
-  Carver tcv;
-  const size_t t_blocks = tcv.take(sizeof(BlockDesc) * (nblk ? nblk : 1));
-  if (!tabs_hit) {
-    tc.valid = false;
-    build_encode_queues(blocks, chunks, st.enc_cost, st.enc_cost_valid, queues, nq, &sh_at);
-    tc.o_queues = tcv.take(sizeof(int32_t) * queues.size());
-    if (tc.tabs.ensure(tcv.off)) return -1;
-    tc.sh_at = sh_at; tc.ntasks = queues[8];
-  }
-  const size_t o_ready = cv.take(sizeof(uint32_t) * (nblk ? nblk : 1));
-  const size_t o_cost = cv.take(sizeof(uint32_t) * kCostWords);
-  const size_t o_filt = cv.take(filt_bytes + 256);
-  const size_t o_stage = cv.take(stage_bytes + 256);
-  // Zstd: the predefined FSE tables and one sequence scratch per persistent wave
+  B.key.nq = st.single_queue ? 1 : 8;
+  B.key.modes.resize((size_t)n);
+  for (int i = 0; i < n; i++) B.key.modes[(size_t)i] = chunks[(size_t)i].mode & CH_FUSED_SHUF;
+  order_signature(B.key.blocks, st.enc_cost, st.enc_cost_valid, B.key.order);
+  Carver pc;
+  if (tc.begin("compress", B.key, 0, 0, pc, [&](EngineState::TableCache& t) {
+        build_encode_queues(B.key.blocks, chunks, st.enc_cost, st.enc_cost_valid, t.queues, B.key.nq, &t.sh_at);
+        t.ntasks = t.queues[8];
+      })) return -1;
+  // ---- workspace ----
+  // "lz4hc": the LZ4HC-grade search of k_encode.hip (lz4hc_encode_wave), or the plain LZ4 match finder at its highest effort
   const bool zstd = p.codec == kZstd, zlibc = p.codec == kZlib;
-  // "lz4hc": the LZ4HC-grade search of k_encode.hip (lz4hc_encode_wave); BLOSC_AMD_LZ4HC=0 serves the name with the plain LZ4
-  // match finder at its highest effort instead (read per call, so that a test can compare the two in one process)
   const bool hc = p.codec == kLZ4HC && lz4hc_search_enabled();
-  // Zstd: sequence tables made per block (k_encode.hip: zt_make_tables) instead of the predefined ones; opt-in (BLOSC_AMD_ZSTD_TABLES=1)
-  // until it has been timed on the device, read per call
+  // Zstd: sequence tables made per block (k_encode.hip: zt_make_tables) instead of the predefined ones
   const bool ztab = zstd && zstd_tables_enabled();
-  // the LZ4HC-grade search in front of the Zstd writer (with per-block tables) / the zlib writer: BLOSC_AMD_ZSTD_SEARCH=1, BLOSC_AMD_ZLIB_SEARCH=1
+  // the LZ4HC-grade search in front of the Zstd writer (with per-block tables) / the zlib writer.
   // Defaults after the device timings of round 3 (profiles/r03/r03a_encopts_bench_*.json, 8 GiB bench19): Zstd - the search costs 2.6 x the
   // encode time (35.8 -> 94.9 ms) for ratio 23.8 -> 35.1, so it serves the upper clevels (the reference maps clevel >= 6 to its
   // lazy / optimal strategies, blosc.c:502-504 + clevels.h) and stays off at the default clevel; zlib - whoever names zlib wants its
   // ratio: search + dynamic codes give 73.4 (reference 47.4, fixed codes without search 40.5) at 57 ms per 8 GiB, still 150 GB/s.
-  const bool zsearch = (zstd && env_flag_or("BLOSC_AMD_ZSTD_SEARCH", p.clevel >= 6)) || (zlibc && env_flag_or("BLOSC_AMD_ZLIB_SEARCH", true));
-  // Huffman-coded literals (with the per-block tables, or tables + search): BLOSC_AMD_ZSTD_HUFFMAN=1 on top of either switch
-  const bool zhuf = zstd && (ztab || zsearch) && env_flag("BLOSC_AMD_ZSTD_HUFFMAN");
+  const bool zsearch = (zstd && zstd_search_enabled(p.clevel)) || (zlibc && zlib_search_enabled());
+  const bool zhuf = zstd && (ztab || zsearch) && zstd_huffman_enabled();      // Huffman-coded literals: on top of either switch
   const int enc_wpc_lz = (zstd || zlibc) ? ENC_WAVES_PER_CU : ENC_LZ_WAVES_PER_CU;
   const int enc_wpc = zsearch ? (160 * 1024) / (HC_TAB_BYTES + ZS_LDS_BYTES) : (hc ? HC_WAVES_PER_CU : enc_wpc_lz);   // what fits into a CU's LDS
-  const bool zdyn = zlibc && env_flag_or("BLOSC_AMD_ZLIB_DYNAMIC", true);      // zlib with dynamic Huffman codes: two passes, the tokens in the sequence scratch
+  const bool zdyn = zlibc && zlib_dynamic_enabled();      // zlib with dynamic Huffman codes: two passes, the tokens in the sequence scratch
   const size_t zwaves = (zstd || zdyn) ? (size_t)(st.cus > 0 ? st.cus : 256) * (size_t)enc_wpc : 0;
+  Carver cv;
+  const size_t o_chunks = cv.take(sizeof(ChunkDesc) * (size_t)n);
+  const size_t o_streams = cv.take(sizeof(StreamDesc) * (nstr ? nstr : 1));
+  const size_t o_blkoff = cv.take(sizeof(int32_t) * (nblk ? nblk : 1));
+  // results + tickets | block-ready flags | cost words: taken back to back, ONE fill clears the three of them
+  const size_t o_results = cv.take(ticket_offset((size_t)n) + sizeof(uint32_t) * kEncTicketWords);
+  const size_t o_ready = cv.take(sizeof(uint32_t) * (nblk ? nblk : 1));
+  const size_t o_cost = cv.take(sizeof(uint32_t) * kCostWords);
+  const size_t clear_bytes = cv.off - o_results;
+  const size_t o_filt = cv.take(B.filt_bytes + 256);
+  const size_t o_stage = cv.take(B.stage_bytes + 256);
+  // Zstd: the predefined FSE tables and one sequence scratch per persistent wave
   const size_t o_ctabs = cv.take(sizeof(zenc::CTabs) + 64);
   const size_t o_seqbufs = cv.take(zwaves * (zdyn ? (size_t)ZD_SCRATCH_U64 : (size_t)ZS_SEQCAP) * sizeof(uint64_t) + 64);
   if (st.dev.ensure(cv.off)) return -1;
   uint8_t* D = st.dev.base;
-  uint8_t *io_s = nullptr, *io_d = nullptr;
-  if (!device_ptrs) {
-    if (st.io.ensure(align_up(io_src + 256, 256) + io_dst + 512)) return -1;
-    io_s = st.io.base; io_d = st.io.base + align_up(io_src + 256, 256);
-  }
   if (zstd) {
-    static zenc::CTabs host_tabs;
-    static bool built = false;
+    static zenc::CTabs host_tabs; static bool built = false;
     if (!built) { zenc::build_predefined(host_tabs); built = true; }
     HIP_TRY(hipMemcpyAsync(D + o_ctabs, &host_tabs, sizeof host_tabs, hipMemcpyHostToDevice, stream));
   }
-  // ---- patch pointers ----
+  // ---- stage the inputs of a host-pointer call, point every chunk at its scratch ----
+  if (io.reserve(st.io)) return -1;
   {
-    size_t fo = 0, so = 0, is = 0, id = 0;
+    size_t fo = 0, so = 0;
     for (int i = 0; i < n; i++) {
-      if (!live[(size_t)i]) continue;
+      if (!B.live[(size_t)i]) continue;
       ChunkDesc& c = chunks[(size_t)i];
-      if (!device_ptrs) {
-        is = align_up(is, 256); id = align_up(id, 256);
-        HIP_TRY(hipMemcpyAsync(io_s + is, jobs[i].src, (size_t)c.nbytes, hipMemcpyHostToDevice, stream));
-        c.src = io_s + is; c.dst = io_d + id;
-        is += (size_t)c.nbytes; id += (size_t)c.cbytes;
-      }
+      if (io.stage(c, jobs[i].src, (size_t)c.nbytes, (size_t)c.cbytes, stream)) return -1;
       if (c.mode & CH_MEMCPYED) continue;
       const bool filtered = (c.mode & (CH_SHUFFLE | CH_BITSHUFFLE)) != 0;
       if (filtered) { fo = align_up(fo, 256); c.filt = D + o_filt + fo; fo += (size_t)c.nbytes; }
       so = align_up(so, 256); c.stage = D + o_stage + so; so += (size_t)c.nbytes;
     }
   }
-  HT_MARK(0, 1);     // queues, workspace, pointer patching
-  // ---- upload tables ----
-  Carver pc;
+  ht.mark(1);     // queues, workspace, pointer patching
+  // ---- upload the tables ----
   const size_t p_chunks = pc.take(sizeof(ChunkDesc) * (size_t)n);
-  const size_t p_blocks = pc.take(tabs_hit ? 0 : sizeof(BlockDesc) * (nblk ? nblk : 1));
   const size_t p_results = pc.take(sizeof(int32_t) * (size_t)n);
-  const size_t p_queues = pc.take(sizeof(int32_t) * queues.size());
   const size_t p_cost = pc.take(sizeof(uint32_t) * kCostWords);
   if (st.pin.ensure(pc.off)) return -1;
   uint8_t* P = st.pin.base;
-  uint8_t* TB = tc.tabs.base;
   memcpy(P + p_chunks, chunks.data(), sizeof(ChunkDesc) * (size_t)n);
-  if (!tabs_hit) {
-    if (nblk) memcpy(P + p_blocks, blocks.data(), sizeof(BlockDesc) * nblk);
-    memcpy(P + p_queues, queues.data(), sizeof(int32_t) * queues.size());
-    HIP_TRY(hipMemcpyAsync(TB + tc.o_queues, P + p_queues, sizeof(int32_t) * queues.size(), hipMemcpyHostToDevice, stream));
-    if (nblk) HIP_TRY(hipMemcpyAsync(TB + t_blocks, P + p_blocks, sizeof(BlockDesc) * nblk, hipMemcpyHostToDevice, stream));
-  }
-  // results + tickets | block-ready flags | cost words lie back to back in the workspace (taken in that order above): one fill for the three of them
-  HIP_TRY(hipMemsetAsync(D + o_results, 0, (o_cost + sizeof(uint32_t) * kCostWords) - o_results, stream));
+  if (tc.upload(B.key, P, stream)) return -1;
+  HIP_TRY(hipMemsetAsync(D + o_results, 0, clear_bytes, stream));
   HIP_TRY(hipMemcpyAsync(D + o_chunks, P + p_chunks, sizeof(ChunkDesc) * (size_t)n, hipMemcpyHostToDevice, stream));
-  uint32_t* d_ticket = (uint32_t*)(D + o_results + sizeof(int32_t) * (size_t)n + 32);
 
-  ChunkDesc* d_chunks = (ChunkDesc*)(D + o_chunks);
-  BlockDesc* d_blocks = (BlockDesc*)(TB + t_blocks);
-  StreamDesc* d_streams = (StreamDesc*)(D + o_streams);
-  int32_t* d_blkoff = (int32_t*)(D + o_blkoff);
-  int32_t* d_results = (int32_t*)(D + o_results);
-
-  HT_MARK(0, 2);     // table copies to pinned memory + upload enqueues
-  // ---- pipeline ----
-  if (nstr) hipLaunchKernelGGL(k_encode_plan, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, stream, d_chunks, d_blocks, d_streams, (int)nblk);
-  if (any_shuf && nblk) {
+  ChunkDesc* d_chunks = (ChunkDesc*)(D + o_chunks); BlockDesc* d_blocks = tc.d_blocks(); StreamDesc* d_streams = (StreamDesc*)(D + o_streams);
+  int32_t* d_blkoff = (int32_t*)(D + o_blkoff); int32_t* d_results = (int32_t*)(D + o_results);
+  uint32_t* d_ticket = (uint32_t*)(D + o_results + ticket_offset((size_t)n));
+  ht.mark(2);     // table copies to pinned memory + upload enqueues
+  // ---- launch ----
+  if (nstr) hipLaunchKernelGGL(k_encode_plan, grid1(nblk, 256), dim3(256), 0, stream, d_chunks, d_blocks, d_streams, (int)nblk);
+  if (B.any_shuf && nblk) {
     ProfScope ps(st, stream, "k_shuffle");
-    hipLaunchKernelGGL(k_shuffle, dim3((unsigned)nblk, (unsigned)tiles_shuf), dim3(FT_THREADS), 0, stream, d_chunks, d_blocks);
+    hipLaunchKernelGGL(k_shuffle, dim3((unsigned)nblk, (unsigned)B.tiles_shuf), dim3(FT_THREADS), 0, stream, d_chunks, d_blocks);
   }
-  if (any_bit && nblk) {
-    const bool bitfast = true;       // full tiles of typesize 1 / 2 / 4 / 8 through k_bitfilter_fast, the rest through the generic kernel
+  if (B.any_bit && nblk) {      // full tiles of typesize 1 / 2 / 4 / 8 through k_bitfilter_fast, the rest through the generic kernel
     ProfScope ps(st, stream, "k_bitshuffle");
-    if (bitfast) hipLaunchKernelGGL(k_bitfilter_fast<0>, dim3((unsigned)nblk, (unsigned)tiles_bit), dim3(FT_THREADS), 0, stream, d_chunks, d_blocks);
-    hipLaunchKernelGGL(k_bitshuffle, dim3((unsigned)nblk, (unsigned)tiles_bit), dim3(FT_THREADS), 0, stream, d_chunks, d_blocks, bitfast ? 1 : 0);
+    hipLaunchKernelGGL(k_bitfilter_fast<0>, dim3((unsigned)nblk, (unsigned)B.tiles_bit), dim3(FT_THREADS), 0, stream, d_chunks, d_blocks);
+    hipLaunchKernelGGL(k_bitshuffle, dim3((unsigned)nblk, (unsigned)B.tiles_bit), dim3(FT_THREADS), 0, stream, d_chunks, d_blocks, 1);
   }
   if (nstr) {
     ProfScope ps(st, stream, zstd ? "k_zstd_encode" : (zlibc ? "k_zlib_encode" : (hc ? "k_lz4hc_encode" : "k_encode_streams")));
-    const int32_t* d_qoff = (const int32_t*)(TB + tc.o_queues); const int32_t* d_qlist = d_qoff + 9;
+    const int32_t* d_qoff = tc.d_qoff(); const int32_t* d_qlist = d_qoff + 9; const int32_t* d_shoff = d_qoff + tc.sh_at;
     uint32_t* d_ready = (uint32_t*)(D + o_ready);
-    const size_t ntasks = (size_t)tc.ntasks;
-    const int32_t* d_shoff = d_qoff + sh_at;
     uint64_t* d_seqbufs = (zstd || zdyn) ? (uint64_t*)(D + o_seqbufs) : nullptr;
     const zenc::CTabs* d_ctabs = zstd ? (const zenc::CTabs*)(D + o_ctabs) : nullptr;
     const int detect = (!zstd && !zlibc && periodic_enabled()) ? 1 : 0;
-    const dim3 grid(persistent_grid(st, ntasks, enc_wpc)), block(64 * ENC_WAVES);
-#ifdef BAMD_PROFILE_DECODE
-    uint32_t* d_prof = nullptr;
-    if (getenv("BLOSC_AMD_ENC_PROFILE")) { (void)hipMalloc((void**)&d_prof, nstr * 64); (void)hipMemsetAsync(d_prof, 0, nstr * 64, stream); }
-#define BAMD_ENC_LAUNCH(MODE) hipLaunchKernelGGL(k_encode_streams_t<MODE>, grid, block, 0, stream, d_streams, d_ticket, d_qlist, d_qoff, d_shoff, d_chunks, d_blocks, d_ready, (uint32_t*)(D + o_cost), st.single_queue ? 1 : 0, d_seqbufs, d_ctabs, detect, d_prof)
-#else
-#define BAMD_ENC_LAUNCH(MODE) hipLaunchKernelGGL(k_encode_streams_t<MODE>, grid, block, 0, stream, d_streams, d_ticket, d_qlist, d_qoff, d_shoff, d_chunks, d_blocks, d_ready, (uint32_t*)(D + o_cost), st.single_queue ? 1 : 0, d_seqbufs, d_ctabs, detect)
-#endif
+    const dim3 grid(persistent_grid(st, (size_t)tc.ntasks, enc_wpc)), block(64 * ENC_WAVES);
+    BAMD_STREAM_PROFILE(prof, "BLOSC_AMD_ENC_PROFILE", nstr);
+#define BAMD_ENC_LAUNCH(MODE) hipLaunchKernelGGL(k_encode_streams_t<MODE>, grid, block, 0, stream, d_streams, d_ticket, d_qlist, d_qoff, d_shoff, d_chunks, d_blocks, d_ready, (uint32_t*)(D + o_cost), st.single_queue ? 1 : 0, d_seqbufs, d_ctabs, detect BAMD_PROF_ARG(prof))
     if (zstd && zsearch) { if (zhuf) BAMD_ENC_LAUNCH(ENC_ZSTD_HCH); else BAMD_ENC_LAUNCH(ENC_ZSTD_HC); }
     else if (zstd && ztab) { if (zhuf) BAMD_ENC_LAUNCH(ENC_ZSTD_TH); else BAMD_ENC_LAUNCH(ENC_ZSTD_T); }
     else if (zstd) BAMD_ENC_LAUNCH(ENC_ZSTD);
@@ -644,16 +717,6 @@ int engine_compress_batch(const CompressParams& p, int n, const Job* jobs, int* 
     else if (hc) BAMD_ENC_LAUNCH(ENC_HC);
     else BAMD_ENC_LAUNCH(ENC_LZ);
 #undef BAMD_ENC_LAUNCH
-#ifdef BAMD_PROFILE_DECODE
-    if (d_prof) {
-      std::vector<uint32_t> h(nstr * 16);
-      (void)hipStreamSynchronize(stream);
-      (void)hipMemcpy(h.data(), d_prof, nstr * 64, hipMemcpyDeviceToHost);
-      FILE* f = fopen(getenv("BLOSC_AMD_ENC_PROFILE"), "wb");
-      if (f) { fwrite(h.data(), 4, h.size(), f); fclose(f); }
-      (void)hipFree(d_prof);
-    }
-#endif
   }
   {
     ProfScope ps(st, stream, "k_chunk_scan");
@@ -666,23 +729,17 @@ int engine_compress_batch(const CompressParams& p, int n, const Job* jobs, int* 
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(P + p_results, d_results, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipMemcpyAsync(P + p_cost, D + o_cost, sizeof(uint32_t) * kCostWords, hipMemcpyDeviceToHost, stream));
-  HT_MARK(0, 3);     // kernel launches
+  ht.mark(3);     // kernel launches
+  // ---- collect ----
   HIP_TRY(hipStreamSynchronize(stream));
-  HT_MARK(0, 4);     // waiting for the device
+  ht.mark(4);     // waiting for the device
   prof_collect(st);
   if (nstr && check_done((const uint32_t*)(P + p_cost), (size_t)tc.ntasks, 0, "compress")) return -1;
-  if (!tabs_hit) { tc.blocks.swap(blocks); tc.modes.swap(tmodes); tc.order.swap(tsig); tc.nq = nq; tc.valid = true; }      // (only now: the uploads are known to have arrived)
+  tc.commit(B.key);
   if (nstr >= 4096) { memcpy(st.enc_cost, P + p_cost, sizeof st.enc_cost); st.enc_cost_valid = true; }   // small calls say little
   const int32_t* r = (const int32_t*)(P + p_results);
-  for (int i = 0; i < n; i++) if (live[(size_t)i]) results[i] = r[i];
-  if (!device_ptrs) {
-    for (int i = 0; i < n; i++) {
-      if (!live[(size_t)i] || results[i] <= 0) continue;
-      HIP_TRY(hipMemcpyAsync(jobs[i].dst, chunks[(size_t)i].dst, (size_t)results[i], hipMemcpyDeviceToHost, stream));
-    }
-    HIP_TRY(hipStreamSynchronize(stream));
-  }
-  return 0;
+  for (int i = 0; i < n; i++) if (B.live[(size_t)i]) results[i] = r[i];
+  return io.collect(n, jobs, chunks, B.live, results, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -776,10 +833,11 @@ static void add_decode_chunk(const Header& h, int fmt, int chunk_index, int32_t 
   }
 }
 
-// Deals whole blocks round-robin to 8 per-XCD queues; queue x lists the stream ids of its blocks.
-// Layout: qoff[9] (int32) followed by qlist[nstr].
+// Everything launch_decode hands to the kernels.  The device pointers into the call's workspace are set by decode_workspace(); the block
+// table and the queues (d_blocks, d_q*, d_zq*: the table cache's, or getitem's own) and the any_* / tiles_* of filter_tiles() by the caller.
 struct DecodeLaunch {
   ChunkDesc* d_chunks; BlockDesc* d_blocks; StreamDesc* d_streams; int32_t* d_status; uint32_t* d_ticket; uint32_t* d_blkdone;
+  size_t clear_bytes;                            // d_status .. the end of d_cost: cleared by clear_decode_counters() before every launch
   uint32_t* d_spans; uint8_t* d_pat;             // periodic spans of the fused unshuffle (k_decode.hip: SpanCtx)
   uint32_t* d_cost;                              // [256] cycles per plane index (scheduling feedback)
   uint32_t* d_zticket; bool any_zstd;            // Zstd frames: k_zstd_entropy + k_zstd_exec (two-phase), the rest through k_zstd_streams
@@ -788,11 +846,67 @@ struct DecodeLaunch {
   ZMeta* d_zmeta; ptrdiff_t zseq_delta;          // nullptr: everything through k_zstd_streams
   ZgLds* d_zgscr;                                // table scratch of the global two-phase variant (nullptr: not allocated)
   ZcTab* d_zctab;                                // its 16-bit sequence tables, one dense record per frame (k_zstd_seq; nullptr: the 32-bit ones inside d_zgscr)
-  const int32_t* d_qlist; const int32_t* d_qoff;   // per-XCD stream queues
+  const int32_t* d_qlist; const int32_t* d_qoff;   // per-XCD stream queues: qoff[9] followed by qlist[nstr]
   size_t nblk, nstr; int nchunks;
   bool any_shuf, any_bit, any_copy; int tiles_shuf, tiles_bit;
   size_t nstr_queued;                              // streams left to k_decode_streams
 };
+
+// The decode workspace in st.dev, for the batched call and for getitem.
+struct DecodeShape {
+  int nchunks; size_t nblk, nstr;
+  size_t filt_bytes;        // filter scratch of the shuffled / bitshuffled chunks
+  size_t zlit_bytes;        // literal scratch of the Zstd chunks (and as much again for the sequence triples of the two-phase path)
+  bool any_zstd, two_phase; // two_phase:           // Zstd frames may go through k_zstd_entropy / k_zstd_exec (zstd2_mode()); false: all of them through k_zstd_streams
+  size_t out_bytes;         // getitem only: the decoded blocks land in the workspace,
+  bool own_tables;          //               and so do its block table and queues (it bypasses the table cache)
+};
+struct DecodeAreas { uint8_t *filt, *zlit, *out, *blocks, *queues; };
+static int decode_workspace(EngineState& st, const DecodeShape& s, DecodeLaunch& L, DecodeAreas& A) {
+  const size_t n = (size_t)s.nchunks, nblk1 = s.nblk ? s.nblk : 1, nstr1 = s.nstr ? s.nstr : 1;
+  const int zstd2 = (s.any_zstd && s.two_phase) ? zstd2_mode() : 0;
+  const bool use_zctab = zstd2 == 2 && BAMD_ZSTD_SEQ_KERNEL && !BAMD_ZSTD_LDS_FSE;
+  Carver cv;
+  const size_t o_chunks = cv.take(sizeof(ChunkDesc) * n);
+  const size_t o_streams = cv.take(sizeof(StreamDesc) * nstr1);
+  // status words + tickets + per-block arrival counters | cost words: taken back to back, ONE fill clears them (clear_decode_counters)
+  const size_t o_blkdone = ticket_offset(n) + sizeof(uint32_t) * kDecTicketWords;
+  const size_t o_status = cv.take(o_blkdone + sizeof(uint32_t) * nblk1);
+  const size_t o_cost = cv.take(sizeof(uint32_t) * kCostWords);
+  L.clear_bytes = cv.off - o_status;
+  const size_t o_spans = cv.take(8 * nstr1);
+  const size_t o_pat = cv.take(span_enabled() ? (size_t)2048 * nstr1 : 256);
+  const size_t o_filt = cv.take(s.filt_bytes + 256);
+  const size_t o_zlit = cv.take(s.zlit_bytes + 256);
+  const size_t o_zseq = cv.take(s.zlit_bytes + 512);      // same layout as the literal scratch
+  const size_t o_zmeta = cv.take(s.any_zstd && s.two_phase ? sizeof(ZMeta) * nstr1 : 64);
+  const size_t o_zticket = cv.take(64);
+  const size_t o_zgscr = cv.take(zstd2 == 2 ? sizeof(ZgLds) * nstr1 : 64);
+  const size_t o_zctab = cv.take(use_zctab ? sizeof(ZcTab) * nstr1 : 64);
+  const size_t o_out = cv.take(s.out_bytes ? s.out_bytes + 256 : 0);
+  const size_t o_blocks = cv.take(s.own_tables ? sizeof(BlockDesc) * nblk1 : 0);
+  const size_t o_queues = cv.take(s.own_tables ? sizeof(int32_t) * (9 + nstr1) : 0);
+  if (st.dev.ensure(cv.off)) return -1;
+  uint8_t* D = st.dev.base;
+  A = DecodeAreas{D + o_filt, D + o_zlit, D + o_out, D + o_blocks, D + o_queues};
+  L.d_chunks = (ChunkDesc*)(D + o_chunks); L.d_streams = (StreamDesc*)(D + o_streams);
+  L.d_status = (int32_t*)(D + o_status);
+  L.d_ticket = (uint32_t*)(D + o_status + ticket_offset(n));
+  L.d_blkdone = (uint32_t*)(D + o_status + o_blkdone);
+  L.d_cost = (uint32_t*)(D + o_cost);
+  L.d_spans = span_enabled() ? (uint32_t*)(D + o_spans) : nullptr; L.d_pat = D + o_pat;
+  L.d_zticket = (uint32_t*)(D + o_zticket);
+  L.d_zmeta = (s.any_zstd && s.two_phase) ? (ZMeta*)(D + o_zmeta) : nullptr; L.zseq_delta = (ptrdiff_t)o_zseq - (ptrdiff_t)o_zlit + 8;
+  L.d_zgscr = zstd2 == 2 ? (ZgLds*)(D + o_zgscr) : nullptr;
+  L.d_zctab = use_zctab ? (ZcTab*)(D + o_zctab) : nullptr;
+  L.nblk = s.nblk; L.nstr = s.nstr; L.nchunks = s.nchunks;
+  return 0;
+}
+static int clear_decode_counters(const DecodeLaunch& L, hipStream_t stream) {
+  HIP_TRY(hipMemsetAsync(L.d_status, 0, L.clear_bytes, stream));
+  if (L.any_zstd || L.any_zlib) HIP_TRY(hipMemsetAsync(L.d_zticket, 0, 64, stream));
+  return 0;
+}
 
 static int launch_decode(EngineState& st, const DecodeLaunch& L, hipStream_t stream) {
   if (L.nblk) {
@@ -803,21 +917,8 @@ static int launch_decode(EngineState& st, const DecodeLaunch& L, hipStream_t str
     if (L.nstr_queued) {
       ProfScope ps(st, stream, "k_decode_streams");
       const dim3 dgrid(persistent_grid(st, L.nstr_queued ? L.nstr_queued : 1, DEC_WAVES_PER_CU));
-#ifdef BAMD_PROFILE_DECODE
-      uint32_t* d_prof = nullptr;
-      if (getenv("BLOSC_AMD_DEC_PROFILE")) { (void)hipMalloc((void**)&d_prof, L.nstr * 64); (void)hipMemsetAsync(d_prof, 0, L.nstr * 64, stream); }
-      hipLaunchKernelGGL(k_decode_streams, dgrid, dim3(64 * DEC_WAVES), 0, stream, L.d_streams, L.d_status, L.d_ticket, L.d_qlist, L.d_qoff, L.d_chunks, L.d_blocks, L.d_blkdone, L.d_spans, L.d_pat, L.d_cost, st.single_queue ? 1 : 0, d_prof);
-      if (d_prof) {
-        std::vector<uint32_t> h(L.nstr * 16);
-        (void)hipStreamSynchronize(stream);
-        (void)hipMemcpy(h.data(), d_prof, L.nstr * 64, hipMemcpyDeviceToHost);
-        FILE* f = fopen(getenv("BLOSC_AMD_DEC_PROFILE"), "wb");
-        if (f) { fwrite(h.data(), 4, h.size(), f); fclose(f); }
-        (void)hipFree(d_prof);
-      }
-#else
-      hipLaunchKernelGGL(k_decode_streams, dgrid, dim3(64 * DEC_WAVES), 0, stream, L.d_streams, L.d_status, L.d_ticket, L.d_qlist, L.d_qoff, L.d_chunks, L.d_blocks, L.d_blkdone, L.d_spans, L.d_pat, L.d_cost, st.single_queue ? 1 : 0);
-#endif
+      BAMD_STREAM_PROFILE(prof, "BLOSC_AMD_DEC_PROFILE", L.nstr);
+      hipLaunchKernelGGL(k_decode_streams, dgrid, dim3(64 * DEC_WAVES), 0, stream, L.d_streams, L.d_status, L.d_ticket, L.d_qlist, L.d_qoff, L.d_chunks, L.d_blocks, L.d_blkdone, L.d_spans, L.d_pat, L.d_cost, st.single_queue ? 1 : 0 BAMD_PROF_ARG(prof));
     }
     // single-block frames through k_zstd_entropy (16 frames per wave) + k_zstd_exec (zstd2_mode above); every other frame
     // shape is left to k_zstd_streams.
@@ -846,23 +947,9 @@ static int launch_decode(EngineState& st, const DecodeLaunch& L, hipStream_t str
     }
     if (L.any_zstd) {
       ProfScope ps(st, stream, "k_zstd_streams");
-#ifdef BAMD_PROFILE_DECODE
-      uint32_t* d_zprof = nullptr;
-      if (getenv("BLOSC_AMD_ZSTD_PROFILE")) { (void)hipMalloc((void**)&d_zprof, L.nstr * 64); (void)hipMemsetAsync(d_zprof, 0, L.nstr * 64, stream); }
+      BAMD_STREAM_PROFILE(zprof, "BLOSC_AMD_ZSTD_PROFILE", L.nstr);
       hipLaunchKernelGGL(k_zstd_streams, dim3(persistent_grid(st, L.nstr, ZSTD_WAVES_PER_CU)), dim3(64), 0, stream, L.d_streams, (int)L.nstr, L.d_status,
-                         L.d_zticket, L.d_chunks, L.d_blocks, L.d_cost + 257, d_taken, d_zprof);
-      if (d_zprof) {
-        std::vector<uint32_t> h(L.nstr * 16);
-        (void)hipStreamSynchronize(stream);
-        (void)hipMemcpy(h.data(), d_zprof, L.nstr * 64, hipMemcpyDeviceToHost);
-        FILE* f = fopen(getenv("BLOSC_AMD_ZSTD_PROFILE"), "wb");
-        if (f) { fwrite(h.data(), 4, h.size(), f); fclose(f); }
-        (void)hipFree(d_zprof);
-      }
-#else
-      hipLaunchKernelGGL(k_zstd_streams, dim3(persistent_grid(st, L.nstr, ZSTD_WAVES_PER_CU)), dim3(64), 0, stream, L.d_streams, (int)L.nstr, L.d_status,
-                         L.d_zticket, L.d_chunks, L.d_blocks, L.d_cost + 257, d_taken);
-#endif
+                         L.d_zticket, L.d_chunks, L.d_blocks, L.d_cost + 257, d_taken BAMD_PROF_ARG(zprof));
     }
     if (L.any_zlib) {
       ProfScope ps(st, stream, "k_zlib_streams");
@@ -873,11 +960,10 @@ static int launch_decode(EngineState& st, const DecodeLaunch& L, hipStream_t str
       ProfScope ps(st, stream, "k_unshuffle");
       hipLaunchKernelGGL(k_unshuffle, dim3((unsigned)L.nblk, (unsigned)L.tiles_shuf), dim3(FT_THREADS), 0, stream, L.d_chunks, L.d_blocks);
     }
-    if (L.any_bit) {
-      const bool bitfast = true;       // full tiles of typesize 1 / 2 / 4 / 8 through k_bitfilter_fast, the rest through the generic kernel
+    if (L.any_bit) {      // full tiles of typesize 1 / 2 / 4 / 8 through k_bitfilter_fast, the rest through the generic kernel
       ProfScope ps(st, stream, "k_bitunshuffle");
-      if (bitfast) hipLaunchKernelGGL(k_bitfilter_fast<1>, dim3((unsigned)L.nblk, (unsigned)L.tiles_bit), dim3(FT_THREADS), 0, stream, L.d_chunks, L.d_blocks);
-      hipLaunchKernelGGL(k_bitunshuffle, dim3((unsigned)L.nblk, (unsigned)L.tiles_bit), dim3(FT_THREADS), 0, stream, L.d_chunks, L.d_blocks, bitfast ? 1 : 0);
+      hipLaunchKernelGGL(k_bitfilter_fast<1>, dim3((unsigned)L.nblk, (unsigned)L.tiles_bit), dim3(FT_THREADS), 0, stream, L.d_chunks, L.d_blocks);
+      hipLaunchKernelGGL(k_bitunshuffle, dim3((unsigned)L.nblk, (unsigned)L.tiles_bit), dim3(FT_THREADS), 0, stream, L.d_chunks, L.d_blocks, 1);
     }
   }
   if (L.any_copy) {
@@ -888,169 +974,110 @@ static int launch_decode(EngineState& st, const DecodeLaunch& L, hipStream_t str
   return 0;
 }
 
-
-static void filter_tiles(ChunkDesc& c, bool& any_shuf, bool& any_bit, int& tiles_shuf, int& tiles_bit, bool may_fuse) {
+// which filter work of chunk c runs inside the codec kernels (mode bits), and how many tiles the stand-alone filter kernels need for the rest
+static void filter_tiles(ChunkDesc& c, DecodeLaunch& L, bool may_fuse) {
   const int32_t T = c.typesize, N = c.blocksize / T;
   // (Zstd chunks: only unsplit ones - the wave that decodes a block's one stream unshuffles it, k_decode.hip: fused_unshuffle_own_block;
   //  zlib chunks: split ones too, k_zlib_streams has per-XCD queues and the hand-off of the LZ4 kernel)
   const bool zfmt = c.fmt == FMT_ZSTD || c.fmt == FMT_ZLIB;
   if ((c.mode & CH_SHUFFLE) && fuse_enabled() && may_fuse && (zfmt ? (fused_fast_typesize(T) && (c.fmt == FMT_ZLIB || c.nsplits == 1)) : fused_typesize(T))) { c.mode |= CH_FUSED_UNSHUF; return; }
   if (c.mode & CH_SHUFFLE) {
-    any_shuf = true;
-    int t = (N + shuffle_tile_elems(T) - 1) / shuffle_tile_elems(T); if (t < 1) t = 1;
-    if (t > tiles_shuf) tiles_shuf = t;
+    L.any_shuf = true;
+    L.tiles_shuf = std::max(L.tiles_shuf, filter_tile_count(N, shuffle_tile_elems(T)));
   } else if ((c.mode & CH_BITSHUFFLE) && bitunshuffle_fused_host(T) && fuse_enabled() && may_fuse && !zfmt) {
     c.mode |= CH_FUSED_BITUNSH;      // round 4: the decode kernel bit-unshuffles every block when its last stream is done (k_decode.hip: bitunshuffle_block_wave)
   } else if (c.mode & CH_BITSHUFFLE) {
-    any_bit = true;
-    int t = (N + bitshuffle_tile_elems(T) - 1) / bitshuffle_tile_elems(T); if (t < 1) t = 1;
-    if (t > tiles_bit) tiles_bit = t;
+    L.any_bit = true;
+    L.tiles_bit = std::max(L.tiles_bit, filter_tile_count(N, bitshuffle_tile_elems(T)));
   }
 }
 
 int engine_decompress_batch(int n, const Job* jobs, int* results, bool device_ptrs, hipStream_t stream) {
   if (n <= 0) return 0;
-  CtxGuard ctx;
-  EngineState& st = *ctx.st;
+  CtxGuard ctx; EngineState& st = *ctx.st;
   if (ensure_device(st) || call_stream(st, !device_ptrs, &stream)) return -1;
-
-  double ht_last = hosttime_on() ? now_ms() : 0.0; if (hosttime_on()) { std::lock_guard<std::mutex> l_(g_ht_mu); g_ht.calls[1]++; }
+  HostPhases ht(1);
   std::vector<Header> hdrs;
   if (fetch_headers(st, n, jobs, device_ptrs, stream, hdrs)) return -1;
-  HT_MARK(1, 0);     // header gather (kernel + copy + sync)
-
+  ht.mark(0);     // header gather (kernel + copy + sync)
+  // ---- check and lay out the chunks ----
   std::vector<ChunkDesc> chunks((size_t)n);
-  std::vector<BlockDesc> blocks;
   std::vector<uint8_t> live((size_t)n, 0);
-  size_t nstr = 0, nstr_z = 0, nstr_zlib = 0, filt_bytes = 0, zlit_bytes = 0, io_src = 0, io_dst = 0;      // nstr_z: streams of Zstd / zlib chunks (their own kernels')
+  EngineState::TableKey key;                         // (modes stays empty: the decode queues are made of the block table and the plane order alone)
+  std::vector<BlockDesc>& blocks = key.blocks;
+  HostStaging io{!device_ptrs};
+  size_t nstr = 0, nstr_z = 0, nstr_zlib = 0, filt_bytes = 0, zlit_bytes = 0;      // nstr_z: streams of Zstd / zlib chunks (their own kernels')
   DecodeLaunch L{};
   for (int i = 0; i < n; i++) {
     ChunkDesc& c = chunks[(size_t)i];
+    const Header& h = hdrs[(size_t)i];
     memset(&c, 0, sizeof c);
     c.mode = CH_SKIP;
     int res = -1, fmt = 0;
-    if (!classify_for_decompress(hdrs[(size_t)i], jobs[i].srcsize, jobs[i].dstsize, &res, &fmt)) { results[i] = res; continue; }
-    add_decode_chunk(hdrs[(size_t)i], fmt, i, 0, hdrs[(size_t)i].nbytes / hdrs[(size_t)i].blocksize + ((hdrs[(size_t)i].nbytes % hdrs[(size_t)i].blocksize) ? 1 : 0),
-                     c, blocks, nstr);
+    if (!classify_for_decompress(h, jobs[i].srcsize, jobs[i].dstsize, &res, &fmt)) { results[i] = res; continue; }
+    add_decode_chunk(h, fmt, i, 0, h.nbytes / h.blocksize + ((h.nbytes % h.blocksize) ? 1 : 0), c, blocks, nstr);
     c.src = (const uint8_t*)jobs[i].src; c.dst = (uint8_t*)jobs[i].dst;
     live[(size_t)i] = 1;
     results[i] = c.nbytes;
     if (c.mode & CH_MEMCPYED) L.any_copy = true;
-    filter_tiles(c, L.any_shuf, L.any_bit, L.tiles_shuf, L.tiles_bit, !st.single_queue);
+    filter_tiles(c, L, !st.single_queue);
     if (c.mode & (CH_SHUFFLE | CH_BITSHUFFLE)) filt_bytes = align_up(filt_bytes, 256) + (size_t)c.nblocks * filt_block_stride(c);
     if (c.fmt == FMT_ZSTD && !(c.mode & CH_MEMCPYED)) { L.any_zstd = true; zlit_bytes = align_up(zlit_bytes, 256) + (size_t)c.nbytes; }
     if (c.fmt == FMT_ZLIB && !(c.mode & CH_MEMCPYED)) L.any_zlib = true;
     if (c.fmt == FMT_ZSTD || c.fmt == FMT_ZLIB) nstr_z += nstr - (size_t)c.first_stream;     // (memcpyed chunks have no streams)
     if (c.fmt == FMT_ZLIB) nstr_zlib += nstr - (size_t)c.first_stream;
-    if (!device_ptrs) { io_src = align_up(io_src, 256) + (size_t)c.cbytes; io_dst = align_up(io_dst, 256) + (size_t)c.nbytes; }
+    io.add((size_t)c.cbytes, (size_t)c.nbytes);
   }
   const size_t nblk = blocks.size();
-  Carver cv;
-  const size_t o_chunks = cv.take(sizeof(ChunkDesc) * (size_t)n);
-  const size_t o_streams = cv.take(sizeof(StreamDesc) * (nstr ? nstr : 1));
-  const size_t o_status = cv.take(sizeof(int32_t) * (size_t)n + 64 + sizeof(uint32_t) * (nblk ? nblk : 1));   // + 8 tickets + per-block arrival counters
-  const size_t o_cost = cv.take(sizeof(uint32_t) * kCostWords);
-  const size_t o_spans = cv.take(8 * (nstr ? nstr : 1));
-  const size_t o_pat = cv.take(span_enabled() ? (size_t)2048 * (nstr ? nstr : 1) : 256);
-  const size_t o_filt = cv.take(filt_bytes + 256);
-  const size_t o_zlit = cv.take(zlit_bytes + 256);      // literal scratch of the Zstd chunks
-  const size_t o_zseq = cv.take(zlit_bytes + 512);      // sequence triples of the two-phase Zstd path, same layout as the literal scratch
-  const size_t o_zmeta = cv.take(L.any_zstd ? sizeof(ZMeta) * (nstr ? nstr : 1) : 64);
-  const size_t o_zticket = cv.take(64);
-  const size_t o_zgscr = cv.take((L.any_zstd && zstd2_mode() == 2) ? sizeof(ZgLds) * (nstr ? nstr : 1) : 64);
-  const bool use_zctab = L.any_zstd && zstd2_mode() == 2 && BAMD_ZSTD_SEQ_KERNEL && !BAMD_ZSTD_LDS_FSE;
-  const size_t o_zctab = cv.take(use_zctab ? sizeof(ZcTab) * (nstr ? nstr : 1) : 64);
-  if (st.dev.ensure(cv.off)) return -1;
-  uint8_t* D = st.dev.base;
-  uint8_t *io_s = nullptr, *io_d = nullptr;
-  if (!device_ptrs) {
-    if (st.io.ensure(align_up(io_src + 256, 256) + io_dst + 512)) return -1;
-    io_s = st.io.base; io_d = st.io.base + align_up(io_src + 256, 256);
-  }
+  // ---- workspace ----
+  DecodeAreas A;
+  if (decode_workspace(st, DecodeShape{n, nblk, nstr, filt_bytes, zlit_bytes, L.any_zstd, /*two_phase*/ true, /*out_bytes*/ 0, /*own_tables*/ false}, L, A)) return -1;
+  // ---- stage the inputs of a host-pointer call, point every chunk at its scratch ----
+  if (io.reserve(st.io)) return -1;
   {
-    size_t fo = 0, zo = 0, is = 0, id = 0;
+    size_t fo = 0, zo = 0;
     for (int i = 0; i < n; i++) {
       if (!live[(size_t)i]) continue;
       ChunkDesc& c = chunks[(size_t)i];
-      if (!device_ptrs) {
-        is = align_up(is, 256); id = align_up(id, 256);
-        HIP_TRY(hipMemcpyAsync(io_s + is, jobs[i].src, (size_t)c.cbytes, hipMemcpyHostToDevice, stream));
-        c.src = io_s + is; c.dst = io_d + id;
-        is += (size_t)c.cbytes; id += (size_t)c.nbytes;
-      }
-      if (c.mode & (CH_SHUFFLE | CH_BITSHUFFLE)) { fo = align_up(fo, 256); c.filt = D + o_filt + fo; fo += (size_t)c.nblocks * filt_block_stride(c); }
-      if (c.fmt == FMT_ZSTD && !(c.mode & CH_MEMCPYED)) { zo = align_up(zo, 256); c.stage = D + o_zlit + zo; zo += (size_t)c.nbytes; }
+      if (io.stage(c, jobs[i].src, (size_t)c.cbytes, (size_t)c.nbytes, stream)) return -1;
+      if (c.mode & (CH_SHUFFLE | CH_BITSHUFFLE)) { fo = align_up(fo, 256); c.filt = A.filt + fo; fo += (size_t)c.nblocks * filt_block_stride(c); }
+      if (c.fmt == FMT_ZSTD && !(c.mode & CH_MEMCPYED)) { zo = align_up(zo, 256); c.stage = A.zlit + zo; zo += (size_t)c.nbytes; }
     }
   }
-  // the block table and the queues: still on the device from the last call of this geometry, or built and uploaded now (EngineState::TableCache)
+  // ---- tables: the block table and the queues, still on the device from the last call of this geometry or built and uploaded now ----
   EngineState::TableCache& tc = st.dec_tabs;
-  const int nq = st.single_queue ? 1 : 8;
-  std::vector<uint32_t> tmodes;                      // (the decode queues are made of the block table and the plane order alone)
-  std::vector<int> tsig;
-  order_signature(blocks, st.dec_cost, st.dec_cost_valid, tsig);
-  const bool tabs_hit = table_cache_enabled() && tc.same(blocks, tmodes, tsig, nq);
-  if (debug_cost_enabled()) fprintf(stderr, "[blosc_amd] decompress: block table and queues %s\n", tabs_hit ? "still on the device" : "built and uploaded");
-  std::vector<int32_t> queues, zqueues;
-  Carver tcv;
-  const size_t t_blocks = tcv.take(sizeof(BlockDesc) * (nblk ? nblk : 1));
-  if (!tabs_hit) {
-    tc.valid = false;
-    build_xcd_queues(blocks, nstr, st.dec_cost, st.dec_cost_valid, queues, nq);
-    if (L.any_zlib) build_xcd_queues(blocks, nstr, nullptr, false, zqueues, nq, BLK_ZLIB);
-    tc.o_queues = tcv.take(sizeof(int32_t) * (9 + (nstr ? nstr : 1)));
-    tc.o_zqueues = tcv.take(sizeof(int32_t) * (9 + (nstr ? nstr : 1)));      // k_zlib_streams' queues
-    if (tc.tabs.ensure(tcv.off)) return -1;
-  }
-  uint8_t* TB = tc.tabs.base;
+  key.nq = st.single_queue ? 1 : 8;
+  order_signature(blocks, st.dec_cost, st.dec_cost_valid, key.order);
   Carver pc;
+  const size_t queue_words = 9 + (nstr ? nstr : 1);      // room for k_decode_streams' queues, and as much for k_zlib_streams'
+  if (tc.begin("decompress", key, queue_words, queue_words, pc, [&](EngineState::TableCache& t) {
+        build_xcd_queues(blocks, nstr, st.dec_cost, st.dec_cost_valid, t.queues, key.nq);
+        if (L.any_zlib) build_xcd_queues(blocks, nstr, nullptr, false, t.zqueues, key.nq, BLK_ZLIB);
+      })) return -1;
   const size_t p_chunks = pc.take(sizeof(ChunkDesc) * (size_t)n);
-  const size_t p_blocks = pc.take(tabs_hit ? 0 : sizeof(BlockDesc) * (nblk ? nblk : 1));
   const size_t p_status = pc.take(sizeof(int32_t) * (size_t)n);
-  const size_t p_queues = pc.take(sizeof(int32_t) * queues.size());
-  const size_t p_zqueues = pc.take(sizeof(int32_t) * (zqueues.size() + 1));
   const size_t p_cost = pc.take(sizeof(uint32_t) * kCostWords);
   if (st.pin.ensure(pc.off)) return -1;
   uint8_t* P = st.pin.base;
   memcpy(P + p_chunks, chunks.data(), sizeof(ChunkDesc) * (size_t)n);
-  HIP_TRY(hipMemcpyAsync(D + o_chunks, P + p_chunks, sizeof(ChunkDesc) * (size_t)n, hipMemcpyHostToDevice, stream));
-  if (!tabs_hit) {
-    if (nblk) memcpy(P + p_blocks, blocks.data(), sizeof(BlockDesc) * nblk);
-    memcpy(P + p_queues, queues.data(), sizeof(int32_t) * queues.size());
-    if (nblk) HIP_TRY(hipMemcpyAsync(TB + t_blocks, P + p_blocks, sizeof(BlockDesc) * nblk, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(TB + tc.o_queues, P + p_queues, sizeof(int32_t) * queues.size(), hipMemcpyHostToDevice, stream));
-    if (!zqueues.empty()) {
-      memcpy(P + p_zqueues, zqueues.data(), sizeof(int32_t) * zqueues.size());
-      HIP_TRY(hipMemcpyAsync(TB + tc.o_zqueues, P + p_zqueues, sizeof(int32_t) * zqueues.size(), hipMemcpyHostToDevice, stream));
-    }
-  }
-  // status words + tickets + arrival counters | cost words lie back to back in the workspace (taken in that order above): one fill
-  HIP_TRY(hipMemsetAsync(D + o_status, 0, (o_cost + sizeof(uint32_t) * kCostWords) - o_status, stream));
-
-  L.d_chunks = (ChunkDesc*)(D + o_chunks); L.d_blocks = (BlockDesc*)(TB + t_blocks);
-  L.d_streams = (StreamDesc*)(D + o_streams); L.d_status = (int32_t*)(D + o_status);
-  L.d_ticket = (uint32_t*)(D + o_status + sizeof(int32_t) * (size_t)n + 32);
-  L.d_blkdone = (uint32_t*)(D + o_status + sizeof(int32_t) * (size_t)n + 64);
-  L.d_qoff = (const int32_t*)(TB + tc.o_queues); L.d_qlist = L.d_qoff + 9;
-  L.d_zqoff = (const int32_t*)(TB + tc.o_zqueues); L.d_zqlist = L.d_zqoff + 9; L.nstr_zlib = nstr_zlib;
-  L.d_spans = span_enabled() ? (uint32_t*)(D + o_spans) : nullptr; L.d_pat = D + o_pat;
-  L.d_cost = (uint32_t*)(D + o_cost);
-  L.d_zticket = (uint32_t*)(D + o_zticket);
-  if (L.any_zstd || L.any_zlib) HIP_TRY(hipMemsetAsync(D + o_zticket, 0, 64, stream));
-  L.d_zmeta = L.any_zstd ? (ZMeta*)(D + o_zmeta) : nullptr; L.zseq_delta = (ptrdiff_t)o_zseq - (ptrdiff_t)o_zlit + 8;
-  L.d_zgscr = (L.any_zstd && zstd2_mode() == 2) ? (ZgLds*)(D + o_zgscr) : nullptr;
-  L.d_zctab = use_zctab ? (ZcTab*)(D + o_zctab) : nullptr;
-  L.nblk = nblk; L.nstr = nstr; L.nchunks = n;
+  HIP_TRY(hipMemcpyAsync(L.d_chunks, P + p_chunks, sizeof(ChunkDesc) * (size_t)n, hipMemcpyHostToDevice, stream));
+  if (tc.upload(key, P, stream) || clear_decode_counters(L, stream)) return -1;
+  L.d_blocks = tc.d_blocks();
+  L.d_qoff = tc.d_qoff(); L.d_qlist = L.d_qoff + 9;
+  L.d_zqoff = tc.d_zqoff(); L.d_zqlist = L.d_zqoff + 9; L.nstr_zlib = nstr_zlib;
   L.nstr_queued = nstr - nstr_z;
-  HT_MARK(1, 2);     // tables, queues, uploads
+  ht.mark(2);     // tables, queues, uploads
+  // ---- launch ----
   if (launch_decode(st, L, stream)) return -1;
-  HIP_TRY(hipMemcpyAsync(P + p_status, D + o_status, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(P + p_cost, D + o_cost, sizeof(uint32_t) * kCostWords, hipMemcpyDeviceToHost, stream));
-  HT_MARK(1, 3);     // kernel launches
+  HIP_TRY(hipMemcpyAsync(P + p_status, L.d_status, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(P + p_cost, L.d_cost, sizeof(uint32_t) * kCostWords, hipMemcpyDeviceToHost, stream));
+  ht.mark(3);     // kernel launches
+  // ---- collect ----
   HIP_TRY(hipStreamSynchronize(stream));
-  HT_MARK(1, 4);     // waiting for the device
+  ht.mark(4);     // waiting for the device
   prof_collect(st);
   if (nblk && check_done((const uint32_t*)(P + p_cost), nstr - nstr_z, L.any_zstd ? nstr : 0, "decompress", nstr_zlib)) return -1;
-  if (!tabs_hit) { tc.blocks.swap(blocks); tc.modes.swap(tmodes); tc.order.swap(tsig); tc.nq = nq; tc.valid = true; }      // (only now: the uploads are known to have arrived)
+  tc.commit(key);
   if (nstr >= 4096) { memcpy(st.dec_cost, P + p_cost, sizeof st.dec_cost); st.dec_cost_valid = true; }
   if (debug_cost_enabled()) {
     fprintf(stderr, "[blosc_amd] decode plane costs:");
@@ -1058,18 +1085,8 @@ int engine_decompress_batch(int n, const Job* jobs, int* results, bool device_pt
     fprintf(stderr, "\n");
   }
   const int32_t* stt = (const int32_t*)(P + p_status);
-  for (int i = 0; i < n; i++) {
-    if (!live[(size_t)i]) continue;
-    if (stt[i] < 0) results[i] = -1;       // blosc.c:1511-1514: every block-level error surfaces as -1
-  }
-  if (!device_ptrs) {
-    for (int i = 0; i < n; i++) {
-      if (!live[(size_t)i] || results[i] <= 0) continue;
-      HIP_TRY(hipMemcpyAsync(jobs[i].dst, chunks[(size_t)i].dst, (size_t)results[i], hipMemcpyDeviceToHost, stream));
-    }
-    HIP_TRY(hipStreamSynchronize(stream));
-  }
-  return 0;
+  for (int i = 0; i < n; i++) if (live[(size_t)i] && stt[i] < 0) results[i] = -1;       // blosc.c:1511-1514: every block-level error surfaces as -1
+  return io.collect(n, jobs, chunks, live, results, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1113,10 +1130,11 @@ int engine_getitem(const void* src, int start, int nitems, void* dest, bool src_
     dsrc = st.io.base;
   }
   if (h.flags & kFlagMemcpyed) {
-    HIP_TRY(hipMemcpyAsync(dest, dsrc + kMaxOverhead + lo, want, dst_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(dest, dsrc + kMaxOverhead + lo, want, out_kind, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return (int)want;
   }
+  // ---- lay out blocks [j0, j1) ----
   const int32_t j0 = (int32_t)(lo / bs), j1 = (int32_t)((hi + bs - 1) / bs);
   ChunkDesc c;
   std::vector<BlockDesc> blocks;
@@ -1124,66 +1142,47 @@ int engine_getitem(const void* src, int start, int nitems, void* dest, bool src_
   add_decode_chunk(h, fmt, 0, j0, j1, c, blocks, nstr);
   const size_t nblk = blocks.size();
   const size_t span = (size_t)(j1 - j0) * (size_t)bs;
-  Carver cv;
-  const size_t o_chunks = cv.take(sizeof(ChunkDesc));
-  const size_t o_blocks = cv.take(sizeof(BlockDesc) * nblk);
-  const size_t o_streams = cv.take(sizeof(StreamDesc) * nstr);
-  const size_t o_status = cv.take(sizeof(int32_t) + 64 + sizeof(uint32_t) * nblk);
-  const size_t o_queues = cv.take(sizeof(int32_t) * (9 + nstr));
-  const size_t o_cost = cv.take(sizeof(uint32_t) * kCostWords);
-  const size_t o_spans = cv.take(8 * nstr);
-  const size_t o_pat = cv.take(span_enabled() ? (size_t)2048 * nstr : 256);
-  const size_t o_out = cv.take(span + 256);
-  const size_t o_filt = cv.take(span + 256);   // room for the padded plane layout of a fused chunk
-  const size_t o_zlit = cv.take((fmt == FMT_ZSTD ? span : 0) + 256);
-  const size_t o_zticket = cv.take(64);
-  if (st.dev.ensure(cv.off)) return -1;
-  uint8_t* D = st.dev.base;
+  DecodeLaunch L{};
+  L.any_zstd = fmt == FMT_ZSTD; L.any_zlib = fmt == FMT_ZLIB;
+  filter_tiles(c, L, !st.single_queue);   // may set CH_FUSED_UNSHUF: before the upload
+  // ---- workspace (filter scratch: room for the padded plane layout of a fused chunk) ----
+  DecodeAreas A;
+  if (decode_workspace(st, DecodeShape{1, nblk, nstr, span, L.any_zstd ? span : 0, L.any_zstd, /*two_phase*/ false, /*out_bytes*/ span, /*own_tables*/ true}, L, A)) return -1;
   c.src = dsrc;
   // kernels address block j at base + j*blocksize: bias the bases so that block j0 lands at offset 0
-  c.dst = D + o_out - (size_t)j0 * bs;
-  c.stage = (fmt == FMT_ZSTD) ? D + o_zlit - (size_t)j0 * bs : nullptr;
-  DecodeLaunch L{};
-  filter_tiles(c, L.any_shuf, L.any_bit, L.tiles_shuf, L.tiles_bit, !st.single_queue);   // may set CH_FUSED_UNSHUF: before the upload
-  c.filt = (c.mode & (CH_SHUFFLE | CH_BITSHUFFLE)) ? D + o_filt - (size_t)j0 * filt_block_stride(c) : nullptr;   // (the block stride depends on the mode just chosen)
+  c.dst = A.out - (size_t)j0 * bs;
+  c.stage = L.any_zstd ? A.zlit - (size_t)j0 * bs : nullptr;
+  c.filt = (c.mode & (CH_SHUFFLE | CH_BITSHUFFLE)) ? A.filt - (size_t)j0 * filt_block_stride(c) : nullptr;   // (the block stride depends on the mode filter_tiles chose)
+  // ---- tables: its own, next to the workspace - a handful of blocks is not worth a place in the table cache ----
+  std::vector<int32_t> queues;     // (one chunk, one format: the zlib kernel's queues when it is a zlib chunk, k_decode_streams' otherwise)
+  build_xcd_queues(blocks, nstr, st.dec_cost, st.dec_cost_valid, queues, st.single_queue ? 1 : 8, L.any_zlib ? (uint32_t)BLK_ZLIB : 0u);
   Carver pc;
   const size_t p_chunks = pc.take(sizeof(ChunkDesc));
   const size_t p_blocks = pc.take(sizeof(BlockDesc) * nblk);
   const size_t p_status = pc.take(sizeof(int32_t));
   const size_t p_cost = pc.take(sizeof(uint32_t) * kCostWords);
-  std::vector<int32_t> queues;     // (one chunk, one format: the zlib kernel's queues when it is a zlib chunk, k_decode_streams' otherwise)
-  build_xcd_queues(blocks, nstr, st.dec_cost, st.dec_cost_valid, queues, st.single_queue ? 1 : 8, fmt == FMT_ZLIB ? (uint32_t)BLK_ZLIB : 0u);
   const size_t p_queues = pc.take(sizeof(int32_t) * queues.size());
   if (st.pin.ensure(pc.off)) return -1;
   uint8_t* P = st.pin.base;
-  memcpy(P + p_queues, queues.data(), sizeof(int32_t) * queues.size());
-  memcpy(P + p_chunks, &c, sizeof c);
-  memcpy(P + p_blocks, blocks.data(), sizeof(BlockDesc) * nblk);
-  HIP_TRY(hipMemcpyAsync(D + o_chunks, P + p_chunks, sizeof c, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(D + o_blocks, P + p_blocks, sizeof(BlockDesc) * nblk, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(D + o_queues, P + p_queues, sizeof(int32_t) * queues.size(), hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemsetAsync(D + o_status, 0, sizeof(int32_t) + 64 + sizeof(uint32_t) * nblk, stream));
-  L.d_chunks = (ChunkDesc*)(D + o_chunks); L.d_blocks = (BlockDesc*)(D + o_blocks);
-  L.d_streams = (StreamDesc*)(D + o_streams); L.d_status = (int32_t*)(D + o_status);
-  L.d_ticket = (uint32_t*)(D + o_status + 32);
-  L.d_blkdone = (uint32_t*)(D + o_status + 68);
-  L.d_qoff = (const int32_t*)(D + o_queues); L.d_qlist = L.d_qoff + 9;
-  L.d_spans = span_enabled() ? (uint32_t*)(D + o_spans) : nullptr; L.d_pat = D + o_pat;
-  L.d_cost = (uint32_t*)(D + o_cost);   // a handful of blocks: the plane costs are not fed back, only the task count is checked
-  HIP_TRY(hipMemsetAsync(D + o_cost, 0, sizeof(uint32_t) * kCostWords, stream));
-  L.any_zstd = fmt == FMT_ZSTD; L.any_zlib = fmt == FMT_ZLIB; L.d_zticket = (uint32_t*)(D + o_zticket);
+  memcpy(P + p_queues, queues.data(), sizeof(int32_t) * queues.size()); memcpy(P + p_chunks, &c, sizeof c); memcpy(P + p_blocks, blocks.data(), sizeof(BlockDesc) * nblk);
+  HIP_TRY(hipMemcpyAsync(L.d_chunks, P + p_chunks, sizeof c, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(A.blocks, P + p_blocks, sizeof(BlockDesc) * nblk, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(A.queues, P + p_queues, sizeof(int32_t) * queues.size(), hipMemcpyHostToDevice, stream));
+  if (clear_decode_counters(L, stream)) return -1;      // (a handful of blocks: the plane costs are not fed back, only the task count is checked)
+  L.d_blocks = (BlockDesc*)A.blocks;
+  L.d_qoff = (const int32_t*)A.queues; L.d_qlist = L.d_qoff + 9;
   L.d_zqoff = L.d_qoff; L.d_zqlist = L.d_qlist; L.nstr_zlib = L.any_zlib ? nstr : 0;
-  if (L.any_zstd || L.any_zlib) HIP_TRY(hipMemsetAsync(D + o_zticket, 0, 64, stream));
-  L.nblk = nblk; L.nstr = nstr; L.nchunks = 1; L.nstr_queued = (L.any_zstd || L.any_zlib) ? 0 : nstr;    // a handful of blocks: always through k_decode_streams (Zstd / zlib: their own kernels)
+  L.nstr_queued = (L.any_zstd || L.any_zlib) ? 0 : nstr;    // Zstd / zlib: their own kernels
+  // ---- launch, collect ----
   if (launch_decode(st, L, stream)) return -1;
-  HIP_TRY(hipMemcpyAsync(P + p_status, D + o_status, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(P + p_cost, D + o_cost, sizeof(uint32_t) * kCostWords, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(P + p_status, L.d_status, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(P + p_cost, L.d_cost, sizeof(uint32_t) * kCostWords, hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
   prof_collect(st);
   if (check_done((const uint32_t*)(P + p_cost), L.nstr_queued, L.any_zstd ? nstr : 0, "getitem", L.any_zlib ? nstr : 0)) return -1;
   const int32_t stt = *(const int32_t*)(P + p_status);
   if (stt < 0) return stt;                                                        // blosc.c:1689-1692: blosc_d's code is returned as is
-  HIP_TRY(hipMemcpyAsync(dest, D + o_out + (size_t)(lo - (int64_t)j0 * bs), want, out_kind, stream));
+  HIP_TRY(hipMemcpyAsync(dest, A.out + (size_t)(lo - (int64_t)j0 * bs), want, out_kind, stream));
   HIP_TRY(hipStreamSynchronize(stream));
   return (int)want;
 }
@@ -1220,11 +1219,7 @@ int engine_filter(int kind, size_t typesize, size_t blocksize, const void* src, 
   HIP_TRY(hipMemcpyAsync(D + o_chunk, &c, sizeof c, hipMemcpyHostToDevice, stream));
   HIP_TRY(hipMemcpyAsync(D + o_block, &b, sizeof b, hipMemcpyHostToDevice, stream));
   HIP_TRY(hipMemcpyAsync(D + o_in, src, blocksize, hipMemcpyHostToDevice, stream));
-  const int32_t N = bs / T;
-  int tiles;
-  if (kind < 2) tiles = (N + shuffle_tile_elems(T) - 1) / shuffle_tile_elems(T);
-  else tiles = (N + bitshuffle_tile_elems(T) - 1) / bitshuffle_tile_elems(T);
-  if (tiles < 1) tiles = 1;
+  const int tiles = filter_tile_count(bs / T, kind < 2 ? shuffle_tile_elems(T) : bitshuffle_tile_elems(T));
   const ChunkDesc* dc = (const ChunkDesc*)(D + o_chunk);
   const BlockDesc* db = (const BlockDesc*)(D + o_block);
   switch (kind) {

@@ -1,7 +1,7 @@
 """c-blosc_amd — Python-side loader for libblosc_amd.so (ctypes; test / bench plumbing only).
 
 The product is the C-ABI shared library built from ``csrc/`` (see ``include/blosc.h`` and
-``include/blosc_gpu.h``).  This module only locates it, declares argument types and offers small
+``include/blosc_gpu.h``, ``include/blosc_gpu_packed.h``).  This module only locates it, declares argument types and offers small
 numpy conveniences that mirror how the reference is driven from Python through ctypes
 (SURVEY.md §A.8).  There is no CPU implementation here: if the library is missing, ``load()``
 raises; if there is no GPU, the library's calls return errors.
@@ -29,6 +29,9 @@ GPU_SYMBOLS = [
     "blosc_gpu_compress_batch_host", "blosc_gpu_decompress_batch_host",
     "blosc_gpu_device_count", "blosc_gpu_partition", "blosc_gpu_compress_batch_multi", "blosc_gpu_decompress_batch_multi",
     "blosc_gpu_profile", "blosc_gpu_profile_reset", "blosc_gpu_profile_get",
+]
+PACKED_SYMBOLS = [      # include/blosc_gpu_packed.h
+    "blosc_gpu_packed_bound", "blosc_gpu_compress_packed", "blosc_gpu_decompress_packed", "blosc_gpu_cbuffer_sizes_batch",
 ]
 
 _lib = None
@@ -81,6 +84,8 @@ def load():
         L.blosc_gpu_compress_batch_multi.argtypes = [i, C.POINTER(i), i, i, sz, C.c_char_p, sz, i, C.POINTER(vp), C.POINTER(sz),
                                                      C.POINTER(vp), C.POINTER(sz), C.POINTER(i)]
         L.blosc_gpu_decompress_batch_multi.argtypes = [i, C.POINTER(i), i, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(i)]
+    if hasattr(L, "blosc_gpu_compress_packed"):
+        declare_packed(L)
     L.blosc_gpu_getitem.argtypes = [vp, i, i, vp, vp]
     L.blosc_gpu_profile.argtypes = [i]
     L.blosc_gpu_profile.restype = None
@@ -96,6 +101,17 @@ def load():
         L.blosc_amd_policy_split.argtypes = [i, i, i, i]
     _lib = L
     return L
+
+
+def declare_packed(L):
+    """argtypes of include/blosc_gpu_packed.h on a library handle (load() calls it; the CPU tests call it on their emulator build)."""
+    vp, sz, i = C.c_void_p, C.c_size_t, C.c_int
+    L.blosc_gpu_packed_bound.argtypes = [i, C.POINTER(sz), sz]
+    L.blosc_gpu_packed_bound.restype = sz
+    L.blosc_gpu_compress_packed.argtypes = [i, i, sz, C.c_char_p, sz, i, C.POINTER(vp), C.POINTER(sz), vp, sz, sz,
+                                            C.POINTER(sz), C.POINTER(i), vp]
+    L.blosc_gpu_decompress_packed.argtypes = [i, vp, sz, C.POINTER(sz), vp, sz, C.POINTER(sz), C.POINTER(i), vp]
+    L.blosc_gpu_cbuffer_sizes_batch.argtypes = [i, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), vp]
 
 
 # ---- numpy conveniences (host buffers through the stock entry points) --------------------------
@@ -139,6 +155,44 @@ class DeviceBatch:
     def decompress(self, stream=None, with_srcsize=True):
         return load().blosc_gpu_decompress_batch(self.n, self.src, self.ssz if with_srcsize else None, self.dst,
                                                  self.dsz, self.res, stream)
+
+    def results(self):
+        return list(self.res)
+
+
+class PackedBatch:
+    """Helper for the packed calls (include/blosc_gpu_packed.h): the whole batch in one device buffer, chunk i at its offset.
+
+    compress(): n sources -> one container; offsets() / results() give the offset table [n + 1] and the per-chunk cbytes.
+    decompress(): a container and its offset table -> one buffer of plain bytes (dest 0 / None: the size query).
+    The library handle may be given (an emulator build in the CPU tests); default: the product."""
+
+    def __init__(self, n, lib=None):
+        self.n = n
+        self.lib = lib if lib is not None else load()
+        self.off = (C.c_size_t * (n + 1))()
+        self.res = (C.c_int * n)()
+
+    def bound(self, sizes, align=1):
+        return self.lib.blosc_gpu_packed_bound(self.n, (C.c_size_t * self.n)(*sizes), align)
+
+    def compress(self, src_ptrs, src_sizes, dest, destsize, typesize, clevel=5, shuffle=1, cname=b"lz4", blocksize=0, align=1, stream=None):
+        return self.lib.blosc_gpu_compress_packed(clevel, shuffle, typesize, cname, blocksize, self.n, (C.c_void_p * self.n)(*src_ptrs),
+                                                  (C.c_size_t * self.n)(*src_sizes), dest, destsize, align, self.off, self.res, stream)
+
+    def decompress(self, container, containersize, offsets, dest, destsize, stream=None):
+        return self.lib.blosc_gpu_decompress_packed(self.n, container, containersize, (C.c_size_t * (self.n + 1))(*offsets), dest, destsize,
+                                                    self.off, self.res, stream)
+
+    def sizes(self, src_ptrs, stream=None):
+        """blosc_cbuffer_sizes of n device-resident chunks: three lists (nbytes, cbytes, blocksize)."""
+        out = [(C.c_size_t * self.n)() for _ in range(3)]
+        if self.lib.blosc_gpu_cbuffer_sizes_batch(self.n, (C.c_void_p * self.n)(*src_ptrs), out[0], out[1], out[2], stream) != 0:
+            raise RuntimeError("blosc_gpu_cbuffer_sizes_batch failed")
+        return [list(o) for o in out]
+
+    def offsets(self):
+        return list(self.off)
 
     def results(self):
         return list(self.res)

@@ -1,4 +1,4 @@
-// blosc_api.hip — the exported C ABI (include/blosc.h, include/blosc_gpu.h).
+// blosc_api.hip — the exported C ABI (include/blosc.h, include/blosc_gpu.h, include/blosc_gpu_packed.h).
 //
 // Host-side mirror of the reference's public layer (blosc/blosc.c:1282-1703, :1951-2317):
 // process globals, the per-call environment overrides, name/code tables and cbuffer introspection
@@ -12,6 +12,7 @@
 
 #include "../../include/blosc.h"
 #include "../../include/blosc_gpu.h"
+#include "../../include/blosc_gpu_packed.h"
 #include "blosc_format.h"
 #include "engine.h"
 
@@ -291,6 +292,78 @@ int blosc_gpu_decompress_batch(int nchunks, const void* const* src, const size_t
 int blosc_gpu_decompress_batch_host(int nchunks, const void* const* src, const size_t* srcsize, void* const* dest,
                                     const size_t* destsize, int* nbytes_out) {
   return decompress_batch(nchunks, src, srcsize, dest, destsize, nbytes_out, nullptr, false);
+}
+
+// ---- the batch in one device buffer (include/blosc_gpu_packed.h) ---------------------------------------
+static bool packed_align(size_t* align) {      // 0 means 1; a power of two up to 4096
+  if (*align == 0) *align = 1;
+  return *align <= 4096 && (*align & (*align - 1)) == 0;
+}
+size_t blosc_gpu_packed_bound(int nchunks, const size_t* nbytes, size_t align) {
+  if (nchunks <= 0 || !nbytes || !packed_align(&align)) return 0;
+  size_t total = 0;
+  for (int i = 0; i < nchunks; i++) total += (nbytes[i] + BLOSC_MAX_OVERHEAD + align - 1) / align * align;
+  return total;
+}
+
+int blosc_gpu_compress_packed(int clevel, int doshuffle, size_t typesize, const char* compressor, size_t blocksize,
+                              int nchunks, const void* const* src, const size_t* nbytes, void* dest, size_t destsize, size_t align,
+                              size_t* offsets_out, int* cbytes_out, void* stream) {
+  if (nchunks < 0 || !offsets_out || !packed_align(&align)) return -1;
+  if (nchunks == 0) { offsets_out[0] = 0; return 0; }
+  if (!src || !nbytes || !cbytes_out || (!dest && destsize)) return -1;
+  const int code = compressor ? blosc_compname_to_compcode(compressor) : g_compressor;
+  if (code < 0 || !codec_built(code)) {      // as blosc_gpu_compress_batch answers: every chunk -5, and none of them takes room
+    for (int i = 0; i < nchunks; i++) { cbytes_out[i] = -5; offsets_out[i] = 0; }
+    offsets_out[nchunks] = 0;
+    return 0;
+  }
+  Job* jobs = (Job*)malloc(sizeof(Job) * (size_t)nchunks);
+  if (!jobs) return -1;
+  // every chunk's own limit is the size at which blosc_compress_ctx cannot answer 0; where it goes is the engine's layout step
+  for (int i = 0; i < nchunks; i++) jobs[i] = Job{src[i], nullptr, nbytes[i], nbytes[i] + BLOSC_MAX_OVERHEAD};
+  CompressParams p{clevel, doshuffle, typesize, code, (int32_t)(blocksize ? blocksize : (size_t)g_force_blocksize), g_splitmode};
+  const PackedBuffer pk{dest, destsize, align, offsets_out};
+  int r = engine_compress_batch(p, nchunks, jobs, cbytes_out, true, (hipStream_t)stream, &pk);
+  free(jobs);
+  return r;
+}
+
+int blosc_gpu_decompress_packed(int nchunks, const void* container, size_t containersize, const size_t* offsets,
+                                void* dest, size_t destsize, size_t* dest_offsets_out, int* nbytes_out, void* stream) {
+  if (nchunks < 0 || !dest_offsets_out) return -1;
+  if (nchunks == 0) { dest_offsets_out[0] = 0; return 0; }
+  if (!container || !offsets || !nbytes_out) return -1;
+  for (int i = 0; i < nchunks; i++) if (offsets[i + 1] < offsets[i]) return -1;
+  if (offsets[nchunks] > containersize) return -1;
+  Job* jobs = (Job*)malloc(sizeof(Job) * (size_t)nchunks);
+  if (!jobs) return -1;
+  for (int i = 0; i < nchunks; i++) {
+    // what lies between two offsets is all a chunk may claim.  The engine reads srcsize 0 as "trust the header": a slot that cannot hold a
+    // header (an empty one too) is passed as 1 byte, which it rejects without reading it
+    const size_t span = offsets[i + 1] - offsets[i];
+    jobs[i] = Job{(const uint8_t*)container + offsets[i], nullptr, span < (size_t)BLOSC_MIN_HEADER_LENGTH ? 1 : span, 0};
+  }
+  const PackedBuffer pk{dest, dest ? destsize : 0, 0, dest_offsets_out};
+  int r = engine_decompress_batch(nchunks, jobs, nbytes_out, true, (hipStream_t)stream, &pk);
+  free(jobs);
+  return r;
+}
+
+int blosc_gpu_cbuffer_sizes_batch(int nchunks, const void* const* src, size_t* nbytes, size_t* cbytes, size_t* blocksize, void* stream) {
+  if (nchunks < 0 || (nchunks > 0 && !src)) return -1;
+  if (nchunks == 0) return 0;
+  Header* h = (Header*)malloc(sizeof(Header) * (size_t)nchunks);
+  if (!h) return -1;
+  const int r = engine_chunk_headers(nchunks, src, h, (hipStream_t)stream);
+  for (int i = 0; r == 0 && i < nchunks; i++) {
+    const bool known = h[i].version == BLOSC_VERSION_FORMAT;      // blosc_cbuffer_sizes: zeros for another format version (blosc.c:2117-2123)
+    if (nbytes) nbytes[i] = known ? (size_t)h[i].nbytes : 0;
+    if (cbytes) cbytes[i] = known ? (size_t)h[i].cbytes : 0;
+    if (blocksize) blocksize[i] = known ? (size_t)h[i].blocksize : 0;
+  }
+  free(h);
+  return r;
 }
 
 // ---- one call, all GPUs of the node (include/blosc_gpu.h) --------------------------------------------

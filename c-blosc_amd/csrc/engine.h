@@ -27,12 +27,28 @@ struct Job {
   size_t dstsize;
 };
 
+// The packed calls (include/blosc_gpu_packed.h): the whole batch lives in ONE device buffer, chunk i at base + offsets[i].
+// compress: the engine chooses the offsets from the chunks' sizes (multiples of `align`, a power of two) and writes what fits into `size`
+// bytes.  decompress: the chunks decode back to back, their slots sized by their headers; base == nullptr only sizes.
+// offsets: host array of n + 1 entries, written by the call.
+struct PackedBuffer {
+  void* base;
+  size_t size;
+  size_t align;           // compress only
+  size_t* offsets;
+};
+
 // All three return 0 when the batch was processed (per-chunk outcomes in results[], with exactly the
 // reference's return-value conventions) or a negative number when the device could not be
 // used at all (no GPU, out of memory, launch failure) — never a silent CPU fallback.
+// packed != nullptr (device pointers only): jobs[i].dst is ignored, jobs[i].dstsize is the chunk's own limit
 int engine_compress_batch(const CompressParams& p, int n, const Job* jobs, int* results, bool device_ptrs,
-                          hipStream_t stream);
-int engine_decompress_batch(int n, const Job* jobs, int* results, bool device_ptrs, hipStream_t stream);
+                          hipStream_t stream, const PackedBuffer* packed = nullptr);
+int engine_decompress_batch(int n, const Job* jobs, int* results, bool device_ptrs, hipStream_t stream,
+                            const PackedBuffer* packed = nullptr);
+// the parsed 16-byte headers of n device-resident chunks (one gather kernel, one synchronisation)
+struct Header;
+int engine_chunk_headers(int n, const void* const* src, Header* out, hipStream_t stream);
 int engine_getitem(const void* src, int start, int nitems, void* dest, bool src_on_device, bool dst_on_device,
                    hipStream_t stream);
 

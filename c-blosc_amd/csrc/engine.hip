@@ -593,8 +593,9 @@ static bool add_encode_chunk(const CompressParams& p, const Job& job, int i, int
 }
 
 int engine_compress_batch(const CompressParams& p, int n, const Job* jobs, int* results, bool device_ptrs,
-                          hipStream_t stream) {
+                          hipStream_t stream, const PackedBuffer* packed) {
   if (n <= 0) return 0;
+  if (packed && !device_ptrs) return -1;
   CtxGuard ctx; EngineState& st = *ctx.st;
   if (ensure_device(st) || call_stream(st, !device_ptrs, &stream)) return -1;
   HostPhases ht(0);
@@ -650,6 +651,7 @@ int engine_compress_batch(const CompressParams& p, int n, const Job* jobs, int* 
   // Zstd: the predefined FSE tables and one sequence scratch per persistent wave
   const size_t o_ctabs = cv.take(sizeof(zenc::CTabs) + 64);
   const size_t o_seqbufs = cv.take(zwaves * (zdyn ? (size_t)ZD_SCRATCH_U64 : (size_t)ZS_SEQCAP) * sizeof(uint64_t) + 64);
+  const size_t o_offsets = packed ? cv.take(sizeof(uint64_t) * ((size_t)n + 1)) : 0;      // packed: the offset table k_packed_layout writes
   if (st.dev.ensure(cv.off)) return -1;
   uint8_t* D = st.dev.base;
   if (zstd) {
@@ -676,6 +678,7 @@ int engine_compress_batch(const CompressParams& p, int n, const Job* jobs, int* 
   const size_t p_chunks = pc.take(sizeof(ChunkDesc) * (size_t)n);
   const size_t p_results = pc.take(sizeof(int32_t) * (size_t)n);
   const size_t p_cost = pc.take(sizeof(uint32_t) * kCostWords);
+  const size_t p_offsets = packed ? pc.take(sizeof(uint64_t) * ((size_t)n + 1)) : 0;
   if (st.pin.ensure(pc.off)) return -1;
   uint8_t* P = st.pin.base;
   memcpy(P + p_chunks, chunks.data(), sizeof(ChunkDesc) * (size_t)n);
@@ -718,9 +721,21 @@ int engine_compress_batch(const CompressParams& p, int n, const Job* jobs, int* 
     else BAMD_ENC_LAUNCH(ENC_LZ);
 #undef BAMD_ENC_LAUNCH
   }
-  {
+  if (!packed) {
     ProfScope ps(st, stream, "k_chunk_scan");
     hipLaunchKernelGGL(k_chunk_scan, dim3((unsigned)n), dim3(SCAN_THREADS), 0, stream, d_chunks, d_blocks, d_streams, d_blkoff, d_results);
+  } else {
+    // sizes first, then every chunk's place inside the caller's buffer (c.dst, or CH_SKIP where it ends), then what the scan writes itself
+    // when the place is known beforehand: header, bstarts - and the zeros between the chunks.  k_chunk_compact reads c.dst from the device table.
+    uint64_t* d_offsets = (uint64_t*)(D + o_offsets);
+    {
+      ProfScope ps(st, stream, "k_chunk_scan");
+      hipLaunchKernelGGL(k_chunk_scan_packed, dim3((unsigned)n), dim3(SCAN_THREADS), 0, stream, d_chunks, d_blocks, d_streams, d_blkoff, d_results);
+    }
+    ProfScope ps(st, stream, "k_packed_layout");
+    hipLaunchKernelGGL(k_packed_layout, dim3(1), dim3(SCAN_THREADS), 0, stream, d_chunks, d_results, n, (uint8_t*)packed->base, (uint64_t)packed->size,
+                       (uint64_t)packed->align, d_offsets);
+    hipLaunchKernelGGL(k_packed_headers, dim3((unsigned)n), dim3(SCAN_THREADS), 0, stream, d_chunks, d_blkoff, d_results, d_offsets, (uint64_t)packed->size);
   }
   if (nblk) {
     ProfScope ps(st, stream, "k_chunk_compact");
@@ -729,12 +744,14 @@ int engine_compress_batch(const CompressParams& p, int n, const Job* jobs, int* 
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(P + p_results, d_results, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipMemcpyAsync(P + p_cost, D + o_cost, sizeof(uint32_t) * kCostWords, hipMemcpyDeviceToHost, stream));
+  if (packed) HIP_TRY(hipMemcpyAsync(P + p_offsets, D + o_offsets, sizeof(uint64_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, stream));
   ht.mark(3);     // kernel launches
   // ---- collect ----
   HIP_TRY(hipStreamSynchronize(stream));
   ht.mark(4);     // waiting for the device
   prof_collect(st);
   if (nstr && check_done((const uint32_t*)(P + p_cost), (size_t)tc.ntasks, 0, "compress")) return -1;
+  if (packed) for (int i = 0; i <= n; i++) packed->offsets[i] = (size_t)((const uint64_t*)(P + p_offsets))[i];
   tc.commit(B.key);
   if (nstr >= 4096) { memcpy(st.enc_cost, P + p_cost, sizeof st.enc_cost); st.enc_cost_valid = true; }   // small calls say little
   const int32_t* r = (const int32_t*)(P + p_results);
@@ -992,14 +1009,55 @@ static void filter_tiles(ChunkDesc& c, DecodeLaunch& L, bool may_fuse) {
   }
 }
 
-int engine_decompress_batch(int n, const Job* jobs, int* results, bool device_ptrs, hipStream_t stream) {
+// The packed call's destinations: chunk i decodes into the h.nbytes bytes behind chunk i - 1's, a chunk whose header does not pass validation
+// takes none.  A valid chunk whose slot ends behind the caller's buffer gets a destination of size 0, i.e. -1 like blosc_decompress with a short one.
+// false: the caller only asked for the sizes (base == nullptr), results[] holds them.
+static bool place_packed_chunks(int n, const std::vector<Header>& hdrs, const PackedBuffer& pk, std::vector<Job>& jobs, int* results) {
+  constexpr size_t kAnySize = (size_t)INT32_MAX;      // validation alone: no header size exceeds it
+  size_t off = 0;
+  for (int i = 0; i < n; i++) {
+    const Header& h = hdrs[(size_t)i];
+    int res = -1, fmt = 0;
+    const bool valid = classify_for_decompress(h, jobs[(size_t)i].srcsize, kAnySize, &res, &fmt) == 1;
+    const size_t width = valid ? (size_t)h.nbytes : 0;
+    pk.offsets[i] = off;
+    jobs[(size_t)i].dst = pk.base ? (uint8_t*)pk.base + off : nullptr;
+    jobs[(size_t)i].dstsize = valid ? (off + width <= pk.size ? width : 0) : kAnySize;
+    if (!pk.base) results[i] = valid ? h.nbytes : res;
+    off += width;
+  }
+  pk.offsets[n] = off;
+  return pk.base != nullptr;
+}
+
+int engine_chunk_headers(int n, const void* const* src, Header* out, hipStream_t stream) {
   if (n <= 0) return 0;
+  CtxGuard ctx; EngineState& st = *ctx.st;
+  if (ensure_device(st)) return -1;
+  std::vector<Job> jobs((size_t)n);
+  for (int i = 0; i < n; i++) jobs[(size_t)i] = Job{src[i], nullptr, 0, 0};
+  std::vector<Header> hdrs;
+  if (fetch_headers(st, n, jobs.data(), true, stream, hdrs)) return -1;
+  std::copy(hdrs.begin(), hdrs.end(), out);
+  return 0;
+}
+
+int engine_decompress_batch(int n, const Job* jobs, int* results, bool device_ptrs, hipStream_t stream, const PackedBuffer* packed) {
+  if (n <= 0) return 0;
+  if (packed && !device_ptrs) return -1;
   CtxGuard ctx; EngineState& st = *ctx.st;
   if (ensure_device(st) || call_stream(st, !device_ptrs, &stream)) return -1;
   HostPhases ht(1);
   std::vector<Header> hdrs;
   if (fetch_headers(st, n, jobs, device_ptrs, stream, hdrs)) return -1;
   ht.mark(0);     // header gather (kernel + copy + sync)
+  // ---- the destinations: the caller's, or - packed - what the headers say ----
+  std::vector<Job> placed;
+  if (packed) {
+    placed.assign(jobs, jobs + n);
+    if (!place_packed_chunks(n, hdrs, *packed, placed, results)) return 0;
+    jobs = placed.data();
+  }
   // ---- check and lay out the chunks ----
   std::vector<ChunkDesc> chunks((size_t)n);
   std::vector<uint8_t> live((size_t)n, 0);

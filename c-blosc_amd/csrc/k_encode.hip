@@ -243,11 +243,14 @@ constexpr int SCAN_THREADS = 256;
 
 __device__ __forceinline__ void st_i32(gu8* p, int32_t v) { g_st_i32le(p, v); }
 
-__global__ __launch_bounds__(SCAN_THREADS) void k_chunk_scan(ChunkDesc* __restrict__ chunks,
-                                                            const BlockDesc* __restrict__ blocks,
-                                                            const StreamDesc* __restrict__ streams,
-                                                            int32_t* __restrict__ blk_off,   // [nblocks_total] out
-                                                            int32_t* __restrict__ results) { // [nchunks] out
+// PACKED (blosc_gpu_compress_packed): the chunk's place is chosen from its size, by k_packed_layout behind this kernel - sizes, block
+// offsets and fallbacks as below, but nothing is written to c.dst (header and bstarts: k_packed_headers)
+template <bool PACKED>
+__device__ __forceinline__ void chunk_scan(ChunkDesc* __restrict__ chunks,
+                                           const BlockDesc* __restrict__ blocks,
+                                           const StreamDesc* __restrict__ streams,
+                                           int32_t* __restrict__ blk_off,   // [nblocks_total] out
+                                           int32_t* __restrict__ results) { // [nchunks] out
   __shared__ int32_t part[SCAN_THREADS];
   __shared__ int32_t carry_s;
   const int cid = blockIdx.x, tid = threadIdx.x;
@@ -256,8 +259,10 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_chunk_scan(ChunkDesc* __restri
   gu8* d = as_global(c.dst);
   if (c.mode & CH_MEMCPYED) {  // decided on the host (clevel 0 / nbytes < 128, blosc.c:1219-1229)
     if (tid == 0) {
-      d[0] = 2; d[1] = 1; d[2] = (uint8_t)c.hdr_flags; d[3] = (uint8_t)c.typesize;  // versionlz byte: see below
-      st_i32(d + 4, c.nbytes); st_i32(d + 8, c.blocksize); st_i32(d + 12, c.nbytes + 16);
+      if (!PACKED) {
+        d[0] = 2; d[1] = 1; d[2] = (uint8_t)c.hdr_flags; d[3] = (uint8_t)c.typesize;  // versionlz byte: see below
+        st_i32(d + 4, c.nbytes); st_i32(d + 8, c.blocksize); st_i32(d + 12, c.nbytes + 16);
+      }
       results[cid] = c.nbytes + 16;
     }
     return;
@@ -302,7 +307,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_chunk_scan(ChunkDesc* __restri
   uint32_t flags = (uint32_t)c.hdr_flags;
   if (total <= maxbytes) {
     res = total;
-    for (int j = tid; j < c.nblocks; j += SCAN_THREADS) st_i32(d + 16 + 4 * (size_t)j, blk_off[c.first_block + j]);
+    if (!PACKED) for (int j = tid; j < c.nblocks; j += SCAN_THREADS) st_i32(d + 16 + 4 * (size_t)j, blk_off[c.first_block + j]);
   } else if ((int64_t)c.nbytes + 16 <= (int64_t)maxbytes) {
     res = c.nbytes + 16;
     flags |= 0x2u;
@@ -312,12 +317,90 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_chunk_scan(ChunkDesc* __restri
     if (tid == 0) c.mode |= CH_SKIP;
   }
   if (tid == 0) {
-    d[0] = 2;                      // BLOSC_VERSION_FORMAT (blosc.h:29)
-    d[1] = 1;                      // codec format version, 1 for every codec (blosc.h:104-109)
-    d[2] = (uint8_t)flags; d[3] = (uint8_t)c.typesize;
-    st_i32(d + 4, c.nbytes); st_i32(d + 8, c.blocksize); st_i32(d + 12, res);
+    if (!PACKED) {
+      d[0] = 2;                      // BLOSC_VERSION_FORMAT (blosc.h:29)
+      d[1] = 1;                      // codec format version, 1 for every codec (blosc.h:104-109)
+      d[2] = (uint8_t)flags; d[3] = (uint8_t)c.typesize;
+      st_i32(d + 4, c.nbytes); st_i32(d + 8, c.blocksize); st_i32(d + 12, res);
+    }
     results[cid] = res;
   }
+}
+__global__ __launch_bounds__(SCAN_THREADS) void k_chunk_scan(ChunkDesc* __restrict__ chunks, const BlockDesc* __restrict__ blocks,
+                                                            const StreamDesc* __restrict__ streams, int32_t* __restrict__ blk_off,
+                                                            int32_t* __restrict__ results) {
+  chunk_scan<false>(chunks, blocks, streams, blk_off, results);
+}
+__global__ __launch_bounds__(SCAN_THREADS) void k_chunk_scan_packed(ChunkDesc* __restrict__ chunks, const BlockDesc* __restrict__ blocks,
+                                                                   const StreamDesc* __restrict__ streams, int32_t* __restrict__ blk_off,
+                                                                   int32_t* __restrict__ results) {
+  chunk_scan<true>(chunks, blocks, streams, blk_off, results);
+}
+
+// k_packed_layout: ONE workgroup walks the batch in tiles of its width, the running offset carried from tile to tile in 64 bits (a container
+// passes 4 GiB long before a batch passes a few thousand chunks).  Chunk i of size r_i = max(results[i], 0) starts at
+//   off_0 = 0,  off_(i+1) = align_up(off_i + r_i, align)      (every off_i is a multiple of align: a prefix sum of align_up(r_i, align))
+// and is written there if it ends inside the caller's buffer: c.dst = dest + off_i.  A chunk that does not gets CH_SKIP and result 0 - nothing of
+// it is written by the kernels behind this one - and still counts with its size, so offsets[nchunks] is what the whole batch needs.
+__global__ __launch_bounds__(SCAN_THREADS) void k_packed_layout(ChunkDesc* __restrict__ chunks, int32_t* __restrict__ results, int nchunks,
+                                                               uint8_t* dest, uint64_t destsize, uint64_t align /* power of two */,
+                                                               uint64_t* __restrict__ offsets) {   // [nchunks + 1] out
+  __shared__ uint64_t part[SCAN_THREADS];
+  __shared__ uint64_t carry_s;
+  const int tid = threadIdx.x;
+  if (tid == 0) carry_s = 0;
+  __syncthreads();
+  for (int base = 0; base < nchunks; base += SCAN_THREADS) {
+    const int i = base + tid;
+    uint64_t size = 0, mine = 0;
+    if (i < nchunks) {
+      const int32_t r = results[i];
+      size = r > 0 ? (uint64_t)r : 0;
+      mine = (size + align - 1) & ~(align - 1);
+    }
+    part[tid] = mine;
+    __syncthreads();
+    for (int o = 1; o < SCAN_THREADS; o <<= 1) {
+      uint64_t v = (tid >= o) ? part[tid - o] : 0;
+      __syncthreads();
+      part[tid] += v;
+      __syncthreads();
+    }
+    const uint64_t carry = carry_s;
+    if (i < nchunks) {
+      const uint64_t off = carry + part[tid] - mine;
+      offsets[i] = off;
+      ChunkDesc& c = chunks[i];
+      if (!(c.mode & CH_SKIP)) {
+        if (off + size <= destsize) c.dst = dest + off;
+        else { c.mode |= CH_SKIP; results[i] = 0; }
+      }
+    }
+    __syncthreads();
+    if (tid == SCAN_THREADS - 1) carry_s = carry + part[tid];
+    __syncthreads();
+  }
+  if (tid == 0) offsets[nchunks] = carry_s;
+}
+
+// k_packed_headers: one workgroup per chunk, behind the layout: header and bstarts of every chunk that has a place, and zeros from its end to
+// the next chunk's start (or to the end of the caller's buffer, where that comes first) - a container is a function of its input alone
+__global__ __launch_bounds__(SCAN_THREADS) void k_packed_headers(const ChunkDesc* __restrict__ chunks, const int32_t* __restrict__ blk_off,
+                                                                const int32_t* __restrict__ results, const uint64_t* __restrict__ offsets,
+                                                                uint64_t destsize) {
+  const int cid = blockIdx.x, tid = threadIdx.x;
+  const ChunkDesc& c = chunks[cid];
+  if (c.mode & CH_SKIP) return;
+  gu8* d = as_global(c.dst);
+  const int32_t res = results[cid];
+  const bool memcpyed = (c.mode & CH_MEMCPYED) != 0;      // decided on the host or by the scan
+  if (!memcpyed) for (int j = tid; j < c.nblocks; j += SCAN_THREADS) st_i32(d + 16 + 4 * (size_t)j, blk_off[c.first_block + j]);
+  if (tid == 0) {      // the 16 header bytes, as k_chunk_scan writes them
+    d[0] = 2; d[1] = 1; d[2] = (uint8_t)((uint32_t)c.hdr_flags | (memcpyed ? 0x2u : 0u)); d[3] = (uint8_t)c.typesize;
+    st_i32(d + 4, c.nbytes); st_i32(d + 8, c.blocksize); st_i32(d + 12, res);
+  }
+  const uint64_t next = offsets[cid + 1] < destsize ? offsets[cid + 1] : destsize;
+  for (uint64_t k = offsets[cid] + (uint64_t)res + (uint64_t)tid; k < next; k += SCAN_THREADS) d[k - offsets[cid]] = 0;
 }
 
 // k_chunk_compact: one workgroup per block; moves the block's streams to their final place.

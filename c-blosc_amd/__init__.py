@@ -1,7 +1,7 @@
 """c-blosc_amd — Python-side loader for libblosc_amd.so (ctypes; test / bench plumbing only).
 
 The product is the C-ABI shared library built from ``csrc/`` (see ``include/blosc.h`` and
-``include/blosc_gpu.h``, ``include/blosc_gpu_packed.h``).  This module only locates it, declares argument types and offers small
+``include/blosc_gpu.h``, ``include/blosc_gpu_packed.h``, ``include/blosc_gpu_getitem.h``).  This module only locates it, declares argument types and offers small
 numpy conveniences that mirror how the reference is driven from Python through ctypes
 (SURVEY.md §A.8).  There is no CPU implementation here: if the library is missing, ``load()``
 raises; if there is no GPU, the library's calls return errors.
@@ -32,6 +32,9 @@ GPU_SYMBOLS = [
 ]
 PACKED_SYMBOLS = [      # include/blosc_gpu_packed.h
     "blosc_gpu_packed_bound", "blosc_gpu_compress_packed", "blosc_gpu_decompress_packed", "blosc_gpu_cbuffer_sizes_batch",
+]
+GETITEM_SYMBOLS = [     # include/blosc_gpu_getitem.h
+    "blosc_gpu_getitem_batch", "blosc_gpu_getitem_packed",
 ]
 
 _lib = None
@@ -86,6 +89,8 @@ def load():
         L.blosc_gpu_decompress_batch_multi.argtypes = [i, C.POINTER(i), i, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(i)]
     if hasattr(L, "blosc_gpu_compress_packed"):
         declare_packed(L)
+    if hasattr(L, "blosc_gpu_getitem_batch"):
+        declare_getitem(L)
     L.blosc_gpu_getitem.argtypes = [vp, i, i, vp, vp]
     L.blosc_gpu_profile.argtypes = [i]
     L.blosc_gpu_profile.restype = None
@@ -112,6 +117,16 @@ def declare_packed(L):
                                             C.POINTER(sz), C.POINTER(i), vp]
     L.blosc_gpu_decompress_packed.argtypes = [i, vp, sz, C.POINTER(sz), vp, sz, C.POINTER(sz), C.POINTER(i), vp]
     L.blosc_gpu_cbuffer_sizes_batch.argtypes = [i, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), vp]
+
+
+def declare_getitem(L):
+    """argtypes of include/blosc_gpu_getitem.h on a library handle (load() calls it; the CPU tests call it on their emulator build)."""
+    vp, sz, i = C.c_void_p, C.c_size_t, C.c_int
+    ip = C.POINTER(i)
+    L.blosc_gpu_getitem_batch.argtypes = [i, C.POINTER(vp), i, ip, ip, ip, C.POINTER(vp), ip, vp]
+    L.blosc_gpu_getitem_packed.argtypes = [i, vp, sz, C.POINTER(sz), i, ip, ip, ip, vp, sz, C.POINTER(sz), ip, vp]
+    L.blosc_amd_getitem_pass_bytes.argtypes = [sz]      # (test hook)
+    L.blosc_amd_getitem_pass_bytes.restype = None
 
 
 # ---- numpy conveniences (host buffers through the stock entry points) --------------------------
@@ -190,6 +205,40 @@ class PackedBatch:
         if self.lib.blosc_gpu_cbuffer_sizes_batch(self.n, (C.c_void_p * self.n)(*src_ptrs), out[0], out[1], out[2], stream) != 0:
             raise RuntimeError("blosc_gpu_cbuffer_sizes_batch failed")
         return [list(o) for o in out]
+
+    def offsets(self):
+        return list(self.off)
+
+    def results(self):
+        return list(self.res)
+
+
+class ItemRanges:
+    """Helper for include/blosc_gpu_getitem.h: many item ranges of many chunks in one call; keeps the ctypes tables alive.
+
+    ranges: (chunk, start, nitems) triples.  batch(): chunk i at src_ptrs[i], range r to dst_ptrs[r].  packed(): the chunks in a container
+    with its offset table [n + 1], the slices back to back in one dest (dest 0 / None: the size query); offsets() is then the table
+    [nranges + 1].  results() gives blosc_getitem's return value per range.
+    The library handle may be given (an emulator build in the CPU tests); default: the product."""
+
+    def __init__(self, ranges, lib=None):
+        self.n = len(ranges)
+        self.lib = lib if lib is not None else load()
+        self.chunk = (C.c_int * self.n)(*[r[0] for r in ranges])
+        self.start = (C.c_int * self.n)(*[r[1] for r in ranges])
+        self.nitems = (C.c_int * self.n)(*[r[2] for r in ranges])
+        self.off = (C.c_size_t * (self.n + 1))()
+        self.res = (C.c_int * self.n)()
+
+    def batch(self, src_ptrs, dst_ptrs, stream=None):
+        nchunks = len(src_ptrs)
+        return self.lib.blosc_gpu_getitem_batch(nchunks, (C.c_void_p * nchunks)(*src_ptrs), self.n, self.chunk, self.start, self.nitems,
+                                                (C.c_void_p * self.n)(*dst_ptrs), self.res, stream)
+
+    def packed(self, container, containersize, offsets, dest, destsize, stream=None):
+        nchunks = len(offsets) - 1
+        return self.lib.blosc_gpu_getitem_packed(nchunks, container, containersize, (C.c_size_t * (nchunks + 1))(*offsets), self.n, self.chunk,
+                                                 self.start, self.nitems, dest, destsize, self.off, self.res, stream)
 
     def offsets(self):
         return list(self.off)

@@ -13,6 +13,7 @@
 #include "../../include/blosc.h"
 #include "../../include/blosc_gpu.h"
 #include "../../include/blosc_gpu_packed.h"
+#include "../../include/blosc_gpu_getitem.h"
 #include "blosc_format.h"
 #include "engine.h"
 
@@ -431,6 +432,51 @@ int blosc_gpu_getitem(const void* src, int start, int nitems, void* dest, void* 
   return engine_getitem(src, start, nitems, dest, true, true, (hipStream_t)stream);
 }
 
+// ---- many item ranges in one call (include/blosc_gpu_getitem.h) ---------------------------------------
+static ItemRange* item_ranges(int nranges, const int* chunk, const int* start, const int* nitems, void* const* dest) {
+  ItemRange* r = (ItemRange*)malloc(sizeof(ItemRange) * (size_t)(nranges > 0 ? nranges : 1));
+  for (int i = 0; r && i < nranges; i++) r[i] = ItemRange{chunk[i], start[i], nitems[i], dest ? dest[i] : nullptr};
+  return r;
+}
+int blosc_gpu_getitem_batch(int nchunks, const void* const* src, int nranges, const int* chunk, const int* start, const int* nitems,
+                            void* const* dest, int* result_out, void* stream) {
+  if (nchunks < 0 || nranges < 0) return -1;
+  if (nranges == 0) return 0;
+  if ((nchunks > 0 && !src) || !chunk || !start || !nitems || !dest || !result_out) return -1;
+  Job* jobs = (Job*)malloc(sizeof(Job) * (size_t)(nchunks > 0 ? nchunks : 1));
+  ItemRange* ranges = item_ranges(nranges, chunk, start, nitems, dest);
+  int r = -1;
+  if (jobs && ranges) {
+    for (int i = 0; i < nchunks; i++) jobs[i] = Job{src[i], nullptr, 0, 0};
+    r = engine_getitem_batch(nchunks, jobs, nranges, ranges, result_out, (hipStream_t)stream);
+  }
+  free(jobs); free(ranges);
+  return r;
+}
+int blosc_gpu_getitem_packed(int nchunks, const void* container, size_t containersize, const size_t* offsets,
+                             int nranges, const int* chunk, const int* start, const int* nitems,
+                             void* dest, size_t destsize, size_t* dest_offsets_out, int* result_out, void* stream) {
+  if (nchunks < 0 || nranges < 0 || !dest_offsets_out) return -1;
+  if (nranges == 0) { dest_offsets_out[0] = 0; return 0; }
+  if ((nchunks > 0 && (!container || !offsets)) || !chunk || !start || !nitems || !result_out) return -1;
+  for (int i = 0; i < nchunks; i++) if (offsets[i + 1] < offsets[i]) return -1;
+  if (nchunks > 0 && offsets[nchunks] > containersize) return -1;
+  Job* jobs = (Job*)malloc(sizeof(Job) * (size_t)(nchunks > 0 ? nchunks : 1));
+  ItemRange* ranges = item_ranges(nranges, chunk, start, nitems, nullptr);
+  int r = -1;
+  if (jobs && ranges) {
+    for (int i = 0; i < nchunks; i++) {
+      // as blosc_gpu_decompress_packed: the span between two offsets is all a chunk may claim; one that cannot hold a header is passed as 1 byte
+      const size_t span = offsets[i + 1] - offsets[i];
+      jobs[i] = Job{(const uint8_t*)container + offsets[i], nullptr, span < (size_t)BLOSC_MIN_HEADER_LENGTH ? 1 : span, 0};
+    }
+    const PackedBuffer pk{dest, dest ? destsize : 0, 0, dest_offsets_out};
+    r = engine_getitem_batch(nchunks, jobs, nranges, ranges, result_out, (hipStream_t)stream, &pk);
+  }
+  free(jobs); free(ranges);
+  return r;
+}
+
 // Filters as stand-alone calls on HOST buffers, same names and signatures as the symbols the
 // reference exports for its own shuffle tests (blosc/shuffle.h:34-61 under BLOSC_TESTING).  The
 // shuffle variants of the byte filter with a bitshuffle-only case (bsize < typesize: not applied,
@@ -488,6 +534,8 @@ __attribute__((visibility("default"))) int blosc_amd_policy_blocksize(int clevel
 __attribute__((visibility("default"))) int blosc_amd_policy_split(int codec, int typesize, int blocksize, int splitmode) {
   return split_block(codec, typesize, blocksize, splitmode);
 }
+// test hook for the pass logic of the batched getitem (tests/test_gpu_getitem_ranges.py, tests/test_emu_getitem_ranges.py): 0 = the default bound
+__attribute__((visibility("default"))) void blosc_amd_getitem_pass_bytes(size_t bytes) { engine_getitem_pass_bytes(bytes); }
 
 void blosc_gpu_profile(int enable) { engine_prof_enable(enable); }
 void blosc_gpu_profile_reset(void) { engine_prof_reset(); }

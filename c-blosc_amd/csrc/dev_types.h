@@ -89,6 +89,18 @@ struct StreamDesc {
   int32_t result;       // encode: compressed size (0 = store raw).  decode: bytes produced or <0
 };
 
+// One entry of k_getitem_gather's range table (k_decode.hip; include/blosc_gpu_getitem.h): nbytes bytes from src - a slot of decoded blocks in
+// the workspace, or the payload of a MEMCPYED chunk - to the caller's dst, provided that none of the nstatus status words from status0 on
+// (one per block the range touches; none for a MEMCPYED chunk) is negative.
+struct GatherRange {
+  const uint8_t* src;
+  uint8_t* dst;
+  uint32_t nbytes;
+  int32_t status0;
+  int32_t nstatus;
+  int32_t pad_;
+};
+
 // Negative per-chunk status codes written by kernels (host maps them to the reference's
 // return values, blosc/blosc.c:762-782): -1 bad csize chain / bounds, -2 codec produced wrong size.
 enum : int32_t { ST_OK = 0, ST_BADCHAIN = -1, ST_BADCODEC = -2 };

@@ -51,6 +51,14 @@ struct Header;
 int engine_chunk_headers(int n, const void* const* src, Header* out, hipStream_t stream);
 int engine_getitem(const void* src, int start, int nitems, void* dest, bool src_on_device, bool dst_on_device,
                    hipStream_t stream);
+// Many item ranges of many device-resident chunks in one call (include/blosc_gpu_getitem.h).  chunks[i]: src and srcsize (0 = trust the
+// header) of chunk i.  Range r = items [start, start + nitems) of chunk `chunk`; results[r] is what blosc_getitem answers for it.
+// packed == nullptr: the slice goes to ranges[r].dst.  packed: the slices back to back in packed->base (size: its capacity; offsets:
+// nranges + 1 entries, written), ranges[r].dst is ignored; base == nullptr only sizes.
+struct ItemRange { int chunk, start, nitems; void* dst; };
+int engine_getitem_batch(int nchunks, const Job* chunks, int nranges, const ItemRange* ranges, int* results, hipStream_t stream,
+                         const PackedBuffer* packed = nullptr);
+void engine_getitem_pass_bytes(size_t bytes);   // test hook: decoded bytes per pass of engine_getitem_batch (0: the default, 256 MiB)
 
 // one block through one filter kernel, host buffers (test hook; kind 0..3 = shuffle, unshuffle, bitshuffle, bitunshuffle)
 int engine_filter(int kind, size_t typesize, size_t blocksize, const void* src, void* dst);

@@ -877,8 +877,9 @@ struct DecodeShape {
   bool any_zstd, two_phase; // two_phase:           // Zstd frames may go through k_zstd_entropy / k_zstd_exec (zstd2_mode()); false: all of them through k_zstd_streams
   size_t out_bytes;         // getitem only: the decoded blocks land in the workspace,
   bool own_tables;          //               and so do its block table and queues (it bypasses the table cache)
+  size_t extra_bytes = 0;   // getitem batch only: one more area, for all of its tables (it uploads them as one piece)
 };
-struct DecodeAreas { uint8_t *filt, *zlit, *out, *blocks, *queues; };
+struct DecodeAreas { uint8_t *filt, *zlit, *out, *blocks, *queues, *extra; };
 static int decode_workspace(EngineState& st, const DecodeShape& s, DecodeLaunch& L, DecodeAreas& A) {
   const size_t n = (size_t)s.nchunks, nblk1 = s.nblk ? s.nblk : 1, nstr1 = s.nstr ? s.nstr : 1;
   const int zstd2 = (s.any_zstd && s.two_phase) ? zstd2_mode() : 0;
@@ -903,9 +904,10 @@ static int decode_workspace(EngineState& st, const DecodeShape& s, DecodeLaunch&
   const size_t o_out = cv.take(s.out_bytes ? s.out_bytes + 256 : 0);
   const size_t o_blocks = cv.take(s.own_tables ? sizeof(BlockDesc) * nblk1 : 0);
   const size_t o_queues = cv.take(s.own_tables ? sizeof(int32_t) * (9 + nstr1) : 0);
+  const size_t o_extra = cv.take(s.extra_bytes);
   if (st.dev.ensure(cv.off)) return -1;
   uint8_t* D = st.dev.base;
-  A = DecodeAreas{D + o_filt, D + o_zlit, D + o_out, D + o_blocks, D + o_queues};
+  A = DecodeAreas{D + o_filt, D + o_zlit, D + o_out, D + o_blocks, D + o_queues, D + o_extra};
   L.d_chunks = (ChunkDesc*)(D + o_chunks); L.d_streams = (StreamDesc*)(D + o_streams);
   L.d_status = (int32_t*)(D + o_status);
   L.d_ticket = (uint32_t*)(D + o_status + ticket_offset(n));
@@ -1150,6 +1152,24 @@ int engine_decompress_batch(int n, const Job* jobs, int* results, bool device_pt
 // ---------------------------------------------------------------------------------------------
 // getitem (blosc/blosc.c:1574-1703): decode only the blocks overlapping [start, start+nitems)
 // ---------------------------------------------------------------------------------------------
+// the header checks of blosc_getitem in its order (blosc.c:1601-1632), for the single call and the batch: 1 = go on, else *res is the call's result
+static int classify_for_getitem(const Header& h, int* res, int* fmt) {
+  if (h.version != kVersionFormat) { *res = -9; return 0; }                      // blosc.c:1603-1604
+  if (h.blocksize <= 0 || h.blocksize > h.nbytes || h.blocksize > kMaxBlockSize || h.typesize <= 0) { *res = -1; return 0; }
+  *fmt = 0;
+  if (h.flags & kFlagMemcpyed) {
+    if (h.nbytes + kMaxOverhead != h.cbytes) { *res = -1; return 0; }
+    return 1;
+  }
+  const int f = (h.flags & 0xe0) >> 5;
+  if (f != FMT_BLOSCLZ && f != FMT_LZ4 && f != FMT_ZLIB && f != FMT_ZSTD) { *res = -5; return 0; }
+  if (h.versionlz != 1) { *res = -9; return 0; }
+  *fmt = f;
+  const int32_t nblocks = h.nbytes / h.blocksize + ((h.nbytes % h.blocksize) ? 1 : 0);
+  if (nblocks >= (h.cbytes - 16) / 4) { *res = -1; return 0; }                   // blosc.c:1630-1632 (sic: >=)
+  return 1;
+}
+
 int engine_getitem(const void* src, int start, int nitems, void* dest, bool src_dev, bool dst_dev, hipStream_t stream) {
   CtxGuard ctx;
   EngineState& st = *ctx.st;
@@ -1159,20 +1179,9 @@ int engine_getitem(const void* src, int start, int nitems, void* dest, bool src_
   if (fetch_headers(st, 1, &job, src_dev, stream, hdrs)) return -1;
   const Header h = hdrs[0];
   const int stop = start + nitems;
-  if (h.version != kVersionFormat) return -9;                                    // blosc.c:1603-1604
-  if (h.blocksize <= 0 || h.blocksize > h.nbytes || h.blocksize > kMaxBlockSize || h.typesize <= 0) return -1;
+  int fmt = 0, bad = -1;
+  if (!classify_for_getitem(h, &bad, &fmt)) return bad;
   const int32_t T = h.typesize, bs = h.blocksize;
-  const int32_t nblocks = h.nbytes / bs + ((h.nbytes % bs) ? 1 : 0);
-  int fmt = 0;
-  if (h.flags & kFlagMemcpyed) {
-    if (h.nbytes + kMaxOverhead != h.cbytes) return -1;
-  } else {
-    const int f = (h.flags & 0xe0) >> 5;
-    if (f != FMT_BLOSCLZ && f != FMT_LZ4 && f != FMT_ZLIB && f != FMT_ZSTD) return -5;
-    if (h.versionlz != 1) return -9;
-    fmt = f;
-    if (nblocks >= (h.cbytes - 16) / 4) return -1;                               // blosc.c:1630-1632 (sic: >=)
-  }
   if (start < 0 || (int64_t)start * T > h.nbytes) { fprintf(stderr, "`start` out of bounds"); return -1; }
   if (stop < 0 || (int64_t)stop * T > h.nbytes) { fprintf(stderr, "`start`+`nitems` out of bounds"); return -1; }
   const int64_t lo = (int64_t)start * T, hi = (int64_t)stop * T;
@@ -1243,6 +1252,246 @@ int engine_getitem(const void* src, int start, int nitems, void* dest, bool src_
   HIP_TRY(hipMemcpyAsync(dest, A.out + (size_t)(lo - (int64_t)j0 * bs), want, out_kind, stream));
   HIP_TRY(hipStreamSynchronize(stream));
   return (int)want;
+}
+
+// ---------------------------------------------------------------------------------------------
+// getitem, batched (include/blosc_gpu_getitem.h): many item ranges of many device-resident chunks in one call
+// ---------------------------------------------------------------------------------------------
+// engine_getitem costs a header fetch, a decode pipeline for a handful of blocks, two synchronisations and a copy PER RANGE.  Here:
+//   1. one header fetch for the distinct chunks the ranges name, then every range is validated on the host (engine_getitem's checks);
+//   2. per chunk the union of the blocks its valid ranges touch, cut into maximal runs of consecutive blocks.  A run decodes into one
+//      slot of the workspace (bases biased like engine_getitem's, so a range that crosses blocks reads one contiguous piece), and a
+//      block is decoded once however many ranges touch it.  Ranges of MEMCPYED chunks are served straight from src + 16;
+//   3. one table upload and one launch_decode for all runs, formats mixed as in engine_decompress_batch;
+//   4. k_getitem_gather (k_decode.hip) writes every slice, after reading the verdict of the blocks the slice depends on;
+//   5. status and cost words come back, one synchronisation.
+// Verdicts.  The decode kernels keep one status word per ChunkDesc, and blosc_getitem answers the code of the FIRST block (in block order) that
+// does not decode, whatever happens to blocks the range does not touch.  So every block of a run enters the tables as a ChunkDesc of its own
+// (add_decode_chunk with the interval [j, j + 1)): the status word the kernels already set is then per block, at 88 bytes of table per block
+// decoded, and no kernel changes.  One word per run would blame a range for a neighbour's block.
+// Passes.  The slots of one launch hold at most kGetitemPassBytes of decoded blocks (the filter scratch and the Zstd literal scratch take as
+// much again each); a call that touches more runs as several passes - whole chunks are dealt to passes in the order the ranges name them, a
+// single chunk beyond the bound is a pass of its own - each with its own launch and synchronisation.  The number of passes depends on the
+// bytes decoded alone, never on the number of ranges.
+constexpr size_t kGetitemPassBytes = (size_t)256 << 20;
+static std::atomic<size_t> g_getitem_pass_bytes{kGetitemPassBytes};
+void engine_getitem_pass_bytes(size_t bytes) { g_getitem_pass_bytes.store(bytes ? bytes : kGetitemPassBytes); }      // test hook: the pass logic on small inputs
+
+namespace {
+struct BlockRun { int32_t j0, j1; size_t off; int32_t entry0; };      // blocks [j0, j1): where block j0 lies in the pass's slots, and its table entry
+struct RangeChunk {            // one distinct chunk the ranges name
+  int fmt = 0, verdict = -1, pass = 0;
+  bool usable = false, memcpyed = false;
+  std::vector<BlockRun> runs;  // the block intervals of its ranges as they come, then (merge_runs) the maximal runs in block order
+};
+struct PlacedRange { int slot = -1; int64_t lo = 0; uint32_t want = 0; int32_t j0 = 0, j1 = 0; uint8_t* dst = nullptr; };
+}  // namespace
+
+static size_t merge_runs(std::vector<BlockRun>& runs, size_t bs) {      // returns the bytes of their slots
+  std::sort(runs.begin(), runs.end(), [](const BlockRun& a, const BlockRun& b) { return a.j0 < b.j0; });
+  size_t m = 0, bytes = 0;
+  for (size_t i = 1; i < runs.size(); i++) {
+    if (runs[i].j0 <= runs[m].j1) runs[m].j1 = std::max(runs[m].j1, runs[i].j1);
+    else runs[++m] = runs[i];
+  }
+  if (!runs.empty()) runs.resize(m + 1);
+  for (const BlockRun& r : runs) bytes += align_up((size_t)(r.j1 - r.j0) * bs, 256);
+  return bytes;
+}
+
+// one pass: decodes the runs of the chunks dealt to `pass` and gathers the ranges of those chunks
+static int getitem_pass(EngineState& st, int pass, std::vector<RangeChunk>& uc, const std::vector<Header>& hdrs, const std::vector<Job>& jobs,
+                        int nranges, const std::vector<PlacedRange>& pr, int* results, hipStream_t stream) {
+  // ---- lay out the runs: one table entry per block ----
+  std::vector<ChunkDesc> entries; std::vector<BlockDesc> blocks;
+  size_t nstr = 0, nstr_z = 0, nstr_zlib = 0, span = 0;
+  bool any_filt = false;
+  DecodeLaunch L{};
+  for (size_t k = 0; k < uc.size(); k++) {
+    RangeChunk& u = uc[k];
+    if (u.pass != pass) continue;
+    const Header& h = hdrs[k];
+    for (BlockRun& r : u.runs) {
+      r.off = span; r.entry0 = (int32_t)entries.size();
+      span += align_up((size_t)(r.j1 - r.j0) * (size_t)h.blocksize, 256);
+      for (int32_t j = r.j0; j < r.j1; j++) {
+        ChunkDesc c;
+        const size_t s0 = nstr;
+        add_decode_chunk(h, u.fmt, (int)entries.size(), j, j + 1, c, blocks, nstr);
+        filter_tiles(c, L, !st.single_queue);
+        if (c.mode & (CH_SHUFFLE | CH_BITSHUFFLE)) any_filt = true;
+        if (c.fmt == FMT_ZSTD) L.any_zstd = true;
+        if (c.fmt == FMT_ZLIB) { L.any_zlib = true; nstr_zlib += nstr - s0; }
+        if (c.fmt == FMT_ZSTD || c.fmt == FMT_ZLIB) nstr_z += nstr - s0;
+        entries.push_back(c);
+      }
+    }
+  }
+  const size_t n = entries.size(), nblk = blocks.size();
+  // ---- the gather table: the ranges of this pass's chunks, in the caller's order ----
+  std::vector<GatherRange> gr((size_t)nranges);
+  std::vector<uint32_t> tile_first((size_t)nranges + 1, 0);
+  for (int r = 0; r < nranges; r++) {
+    GatherRange& g = gr[(size_t)r];
+    memset(&g, 0, sizeof g);
+    const PlacedRange& p = pr[(size_t)r];
+    uint32_t tiles = 0;
+    if (p.slot >= 0 && uc[(size_t)p.slot].pass == pass) { g.nbytes = p.want; g.dst = p.dst; tiles = (p.want + GI_TILE - 1) / GI_TILE; }
+    tile_first[(size_t)r + 1] = tile_first[(size_t)r] + tiles;
+  }
+  const uint32_t ntiles = tile_first[(size_t)nranges];
+  if (!nblk && !ntiles) return 0;
+  // ---- queues, as engine_decompress_batch builds them (a few blocks each time: not worth a place in the table cache) ----
+  const int nq = st.single_queue ? 1 : 8;
+  std::vector<int32_t> queues, zqueues;
+  build_xcd_queues(blocks, nstr, st.dec_cost, st.dec_cost_valid, queues, nq);
+  if (L.any_zlib) build_xcd_queues(blocks, nstr, nullptr, false, zqueues, nq, BLK_ZLIB);
+  // ---- workspace; every table of the pass in one piece, laid out alike in pinned and in device memory ----
+  Carver tv;
+  const size_t t_chunks = tv.take(sizeof(ChunkDesc) * (n ? n : 1));
+  const size_t t_blocks = tv.take(sizeof(BlockDesc) * (nblk ? nblk : 1));
+  const size_t t_queues = tv.take(sizeof(int32_t) * queues.size());
+  const size_t t_zqueues = tv.take(sizeof(int32_t) * (zqueues.size() + 1));
+  const size_t t_ranges = tv.take(sizeof(GatherRange) * (size_t)nranges);
+  const size_t t_tiles = tv.take(sizeof(uint32_t) * ((size_t)nranges + 1));
+  const size_t table_bytes = tv.off;
+  const size_t p_status = tv.take(sizeof(int32_t) * (n ? n : 1));      // (pinned only: what comes back)
+  const size_t p_cost = tv.take(sizeof(uint32_t) * kCostWords);
+  DecodeAreas A;
+  if (decode_workspace(st, DecodeShape{(int)n, nblk, nstr, any_filt ? span : 0, L.any_zstd ? span : 0, L.any_zstd, /*two_phase*/ false, /*out_bytes*/ span, /*own_tables*/ false,
+                                       table_bytes}, L, A)) return -1;
+  if (st.pin.ensure(tv.off)) return -1;
+  uint8_t* P = st.pin.base;
+  // kernels address block j at base + j * blocksize: bias the bases so that block r.j0 lands at the run's slot
+  for (size_t k = 0; k < uc.size(); k++) {
+    if (uc[k].pass != pass) continue;
+    const size_t bs = (size_t)hdrs[k].blocksize;
+    for (const BlockRun& r : uc[k].runs)
+      for (int32_t j = r.j0; j < r.j1; j++) {
+        ChunkDesc& c = entries[(size_t)(r.entry0 + (j - r.j0))];
+        c.src = (const uint8_t*)jobs[k].src;
+        c.dst = A.out + r.off - (size_t)r.j0 * bs;
+        c.stage = c.fmt == FMT_ZSTD ? A.zlit + r.off - (size_t)r.j0 * bs : nullptr;
+        c.filt = (c.mode & (CH_SHUFFLE | CH_BITSHUFFLE)) ? A.filt + r.off - (size_t)r.j0 * filt_block_stride(c) : nullptr;
+      }
+  }
+  for (int r = 0; r < nranges; r++) {
+    GatherRange& g = gr[(size_t)r];
+    if (!g.nbytes) continue;
+    const PlacedRange& p = pr[(size_t)r];
+    const RangeChunk& u = uc[(size_t)p.slot];
+    if (u.memcpyed) { g.src = (const uint8_t*)jobs[(size_t)p.slot].src + kMaxOverhead + p.lo; continue; }
+    // the run that holds block j0 (every block of the range lies in it: runs are unions of the ranges' intervals)
+    auto it = std::upper_bound(u.runs.begin(), u.runs.end(), p.j0, [](int32_t j, const BlockRun& b) { return j < b.j0; });
+    const BlockRun& run = *(it - 1);
+    g.src = A.out + run.off + (size_t)(p.lo - (int64_t)run.j0 * hdrs[(size_t)p.slot].blocksize);
+    g.status0 = run.entry0 + (p.j0 - run.j0); g.nstatus = p.j1 - p.j0;
+  }
+  memcpy(P + t_chunks, entries.data(), sizeof(ChunkDesc) * n);
+  memcpy(P + t_blocks, blocks.data(), sizeof(BlockDesc) * nblk);
+  memcpy(P + t_queues, queues.data(), sizeof(int32_t) * queues.size());
+  memcpy(P + t_zqueues, zqueues.data(), sizeof(int32_t) * zqueues.size());
+  memcpy(P + t_ranges, gr.data(), sizeof(GatherRange) * (size_t)nranges);
+  memcpy(P + t_tiles, tile_first.data(), sizeof(uint32_t) * ((size_t)nranges + 1));
+  HIP_TRY(hipMemcpyAsync(A.extra, P, table_bytes, hipMemcpyHostToDevice, stream));
+  L.d_chunks = (ChunkDesc*)(A.extra + t_chunks); L.d_blocks = (BlockDesc*)(A.extra + t_blocks);
+  L.d_qoff = (const int32_t*)(A.extra + t_queues); L.d_qlist = L.d_qoff + 9;
+  L.d_zqoff = (const int32_t*)(A.extra + t_zqueues); L.d_zqlist = L.d_zqoff + 9; L.nstr_zlib = nstr_zlib;
+  L.nstr_queued = nstr - nstr_z;
+  // ---- launch, collect ----
+  if (nblk) {
+    if (clear_decode_counters(L, stream) || launch_decode(st, L, stream)) return -1;
+    HIP_TRY(hipMemcpyAsync(P + p_status, L.d_status, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(P + p_cost, L.d_cost, sizeof(uint32_t) * kCostWords, hipMemcpyDeviceToHost, stream));
+  }
+  if (ntiles) {
+    ProfScope ps(st, stream, "k_getitem_gather");
+    hipLaunchKernelGGL(k_getitem_gather, dim3(persistent_grid(st, ntiles, GI_WAVES_PER_CU)), dim3(GI_THREADS), 0, stream,
+                       (const GatherRange*)(A.extra + t_ranges), (const uint32_t*)(A.extra + t_tiles), nranges, (const int32_t*)L.d_status);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipStreamSynchronize(stream));
+  prof_collect(st);
+  if (!nblk) return 0;
+  if (check_done((const uint32_t*)(P + p_cost), nstr - nstr_z, L.any_zstd ? nstr : 0, "getitem batch", nstr_zlib)) return -1;
+  if (nstr >= 4096) { memcpy(st.dec_cost, P + p_cost, sizeof st.dec_cost); st.dec_cost_valid = true; }      // (partial decodes of a few blocks say little)
+  const int32_t* stt = (const int32_t*)(P + p_status);
+  for (int r = 0; r < nranges; r++) {
+    const GatherRange& g = gr[(size_t)r];
+    for (int32_t k = 0; k < g.nstatus; k++)
+      if (stt[g.status0 + k] < 0) { results[r] = stt[g.status0 + k]; break; }      // blosc.c:1689-1692: blosc_d's code of the first block that fails
+  }
+  return 0;
+}
+
+int engine_getitem_batch(int nchunks, const Job* chunks, int nranges, const ItemRange* ranges, int* results, hipStream_t stream,
+                         const PackedBuffer* packed) {
+  if (packed) packed->offsets[0] = 0;
+  if (nranges <= 0) return 0;
+  CtxGuard ctx; EngineState& st = *ctx.st;
+  if (ensure_device(st)) return -1;
+  // ---- the headers of the distinct chunks the ranges name: one fetch ----
+  std::vector<int> slot_of((size_t)(nchunks > 0 ? nchunks : 0), -1);
+  std::vector<Job> jobs;
+  for (int r = 0; r < nranges; r++) {
+    const int ci = ranges[r].chunk;
+    if (ci < 0 || ci >= nchunks || slot_of[(size_t)ci] >= 0) continue;
+    slot_of[(size_t)ci] = (int)jobs.size();
+    jobs.push_back(chunks[ci]);
+  }
+  std::vector<Header> hdrs;
+  if (!jobs.empty() && fetch_headers(st, (int)jobs.size(), jobs.data(), true, stream, hdrs)) return -1;
+  std::vector<RangeChunk> uc(jobs.size());
+  for (size_t k = 0; k < uc.size(); k++) {
+    RangeChunk& u = uc[k];
+    const Header& h = hdrs[k];
+    const size_t srcsize = jobs[k].srcsize;      // packed: what lies between two offsets is all a chunk may claim
+    if (srcsize && srcsize < (size_t)kMaxOverhead) u.verdict = -1;
+    else if (!classify_for_getitem(h, &u.verdict, &u.fmt)) continue;
+    else if (srcsize && (h.cbytes < 0 || (size_t)h.cbytes > srcsize)) u.verdict = -1;
+    else { u.usable = true; u.memcpyed = (h.flags & kFlagMemcpyed) != 0; }
+  }
+  // ---- the ranges: engine_getitem's checks; packed: the slices back to back ----
+  std::vector<PlacedRange> pr((size_t)nranges);
+  size_t off = 0;
+  for (int r = 0; r < nranges; r++) {
+    if (packed) packed->offsets[r] = off;
+    results[r] = -1;
+    const int ci = ranges[r].chunk;
+    if (ci < 0 || ci >= nchunks) continue;
+    const int slot = slot_of[(size_t)ci];
+    RangeChunk& u = uc[(size_t)slot];
+    if (!u.usable) { results[r] = u.verdict; continue; }
+    const Header& h = hdrs[(size_t)slot];
+    const int32_t T = h.typesize, bs = h.blocksize;
+    const int start = ranges[r].start, stop = (int)((unsigned)start + (unsigned)ranges[r].nitems);
+    if (start < 0 || (int64_t)start * T > h.nbytes || stop < 0 || (int64_t)stop * T > h.nbytes) continue;      // blosc.c:1645-1653
+    const int64_t lo = (int64_t)start * T, hi = (int64_t)stop * T;
+    if (hi <= lo) { results[r] = 0; continue; }
+    PlacedRange& p = pr[(size_t)r];
+    p.want = (uint32_t)(hi - lo); p.lo = lo; p.dst = (uint8_t*)ranges[r].dst;
+    if (packed) {
+      if (packed->base && off + p.want > packed->size) continue;      // a slot that ends behind the caller's buffer: -1, nothing written, no room taken
+      p.dst = packed->base ? (uint8_t*)packed->base + off : nullptr;
+      off += p.want;
+    }
+    results[r] = (int)p.want;
+    p.slot = slot;
+    p.j0 = (int32_t)(lo / bs); p.j1 = (int32_t)((hi + bs - 1) / bs);
+    if (!u.memcpyed) u.runs.push_back(BlockRun{p.j0, p.j1, 0, 0});
+  }
+  if (packed) { packed->offsets[nranges] = off; if (!packed->base) return 0; }
+  // ---- runs per chunk, chunks dealt to passes ----
+  const size_t bound = g_getitem_pass_bytes.load();
+  size_t in_pass = 0; int pass = 0;
+  for (size_t k = 0; k < uc.size(); k++) {
+    const size_t bytes = merge_runs(uc[k].runs, (size_t)(hdrs[k].blocksize > 0 ? hdrs[k].blocksize : 1));
+    if (in_pass && in_pass + bytes > bound) { pass++; in_pass = 0; }
+    uc[k].pass = pass; in_pass += bytes;
+  }
+  for (int p = 0; p <= pass; p++)
+    if (getitem_pass(st, p, uc, hdrs, jobs, nranges, pr, results, stream)) return -1;
+  return 0;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 """c-blosc_amd — Python-side loader for libblosc_amd.so (ctypes; test / bench plumbing only).
 
 The product is the C-ABI shared library built from ``csrc/`` (see ``include/blosc.h`` and
-``include/blosc_gpu.h``, ``include/blosc_gpu_packed.h``, ``include/blosc_gpu_getitem.h``).  This module only locates it, declares argument types and offers small
+``include/blosc_gpu.h``, ``include/blosc_gpu_packed.h``, ``include/blosc_gpu_getitem.h``, ``include/blosc_gpu_checksum.h``).  This module only locates it, declares argument types and offers small
 numpy conveniences that mirror how the reference is driven from Python through ctypes
 (SURVEY.md §A.8).  There is no CPU implementation here: if the library is missing, ``load()``
 raises; if there is no GPU, the library's calls return errors.
@@ -36,6 +36,10 @@ PACKED_SYMBOLS = [      # include/blosc_gpu_packed.h
 GETITEM_SYMBOLS = [     # include/blosc_gpu_getitem.h
     "blosc_gpu_getitem_batch", "blosc_gpu_getitem_packed",
 ]
+CHECKSUM_SYMBOLS = [    # include/blosc_gpu_checksum.h
+    "blosc_gpu_checksum_batch", "blosc_gpu_checksum_packed",
+]
+CHECKSUM_ADLER32, CHECKSUM_CRC32 = 1, 2
 
 _lib = None
 
@@ -91,6 +95,8 @@ def load():
         declare_packed(L)
     if hasattr(L, "blosc_gpu_getitem_batch"):
         declare_getitem(L)
+    if hasattr(L, "blosc_gpu_checksum_batch"):
+        declare_checksum(L)
     L.blosc_gpu_getitem.argtypes = [vp, i, i, vp, vp]
     L.blosc_gpu_profile.argtypes = [i]
     L.blosc_gpu_profile.restype = None
@@ -127,6 +133,15 @@ def declare_getitem(L):
     L.blosc_gpu_getitem_packed.argtypes = [i, vp, sz, C.POINTER(sz), i, ip, ip, ip, vp, sz, C.POINTER(sz), ip, vp]
     L.blosc_amd_getitem_pass_bytes.argtypes = [sz]      # (test hook)
     L.blosc_amd_getitem_pass_bytes.restype = None
+
+
+def declare_checksum(L):
+    """argtypes of include/blosc_gpu_checksum.h on a library handle (load() calls it; the CPU tests call it on their emulator build)."""
+    vp, sz, i = C.c_void_p, C.c_size_t, C.c_int
+    L.blosc_gpu_checksum_batch.argtypes = [i, i, C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_uint), vp]
+    L.blosc_gpu_checksum_packed.argtypes = [i, i, vp, sz, C.POINTER(sz), C.POINTER(sz), C.POINTER(C.c_uint), vp]
+    L.blosc_amd_checksum_tile_bytes.argtypes = [sz]     # (test hook)
+    L.blosc_amd_checksum_tile_bytes.restype = None
 
 
 # ---- numpy conveniences (host buffers through the stock entry points) --------------------------
@@ -245,6 +260,31 @@ class ItemRanges:
 
     def results(self):
         return list(self.res)
+
+
+def checksums(kind, ptrs, sizes, lib=None, stream=None):
+    """zlib's adler32 (kind 1) / crc32 (kind 2) of the sizes[i] bytes at the device pointers ptrs[i], one call (include/blosc_gpu_checksum.h);
+    returns the digests as a list of ints.  The library handle may be given (an emulator build in the CPU tests); default: the product."""
+    L = lib if lib is not None else load()
+    n = len(ptrs)
+    out = (C.c_uint * max(n, 1))()
+    r = L.blosc_gpu_checksum_batch(kind, n, (C.c_void_p * max(n, 1))(*ptrs), (C.c_size_t * max(n, 1))(*sizes), out, stream)
+    if r != 0:
+        raise RuntimeError(f"blosc_gpu_checksum_batch answered {r}")
+    return list(out)[:n]
+
+
+def checksums_packed(kind, container, containersize, offsets, lengths=None, lib=None, stream=None):
+    """The same for the runs of one device buffer: run i = the first lengths[i] bytes at container + offsets[i] (lengths None: the whole span
+    up to offsets[i + 1]); offsets has one entry more than there are runs."""
+    L = lib if lib is not None else load()
+    n = len(offsets) - 1
+    out = (C.c_uint * max(n, 1))()
+    ln = (C.c_size_t * max(n, 1))(*lengths) if lengths is not None else None
+    r = L.blosc_gpu_checksum_packed(kind, n, container, containersize, (C.c_size_t * (n + 1))(*offsets), ln, out, stream)
+    if r != 0:
+        raise RuntimeError(f"blosc_gpu_checksum_packed answered {r}")
+    return list(out)[:n]
 
 
 def profile_get(name):

@@ -16,6 +16,11 @@ possible - what IS pinned: every chunk inside is an ordinary c-blosc chunk, read
     [offsets: (nchunks + max_app_chunks) x int64, from the start of the file, -1 = unused]
     chunk 0 [+ 4-byte checksum of the compressed chunk, little endian], chunk 1 ...
 
+`pack_device` / `unpack_device` are the same file from and to DEVICE memory: the plain data never crosses to the host.  A batch is
+compressed into one packed container (include/blosc_gpu_packed.h), its chunks are digested where they lie
+(include/blosc_gpu_checksum.h), and only the compressed bytes come down, in one copy; the reader uploads the file image once,
+verifies the digests on the device and decodes the image as a packed container straight into the caller's buffer.
+
 Only what the path needs: no metadata section is written (a file that has one is read past it), checksums none / adler32 /
 crc32.  There is no CPU implementation here: without the library and a GPU the calls fail.
 """
@@ -163,6 +168,156 @@ def unpack(lib, fh, batch_bytes=1 << 30, verify=True):
             raise BlpkError(f"decompression failed (rc {rc}, results {list(res)[:4]}...)")
         k0 = k1
     return out
+
+
+# ---- files from and to device memory ---------------------------------------------------------------------------------------------
+class TorchMem:
+    """Device memory and copies for pack_device / unpack_device out of torch (uint8 tensors on the current device).
+    alloc(n) -> (ptr, keepalive); to_host(ptr, n) -> numpy uint8 (ptr inside a buffer of alloc / to_device that is still alive);
+    to_device(numpy uint8) -> (ptr, keepalive).  Anything with these three methods serves (the CPU tests pass a numpy-backed one:
+    on the emulated library "device memory" is host memory)."""
+
+    def __init__(self):
+        import torch                                     # lazily: this module imports without it
+        import weakref
+        self.torch = torch
+        self.live = weakref.WeakSet()
+
+    def alloc(self, n):
+        t = self.torch.empty(max(int(n), 1), dtype=self.torch.uint8, device="cuda")
+        self.live.add(t)
+        return t.data_ptr(), t
+
+    def to_host(self, ptr, n):
+        for t in self.live:
+            base = t.data_ptr()
+            if base <= ptr and ptr + n <= base + t.numel():
+                return t[ptr - base:ptr - base + n].cpu().numpy()
+        raise BlpkError("to_host: not inside a buffer this object handed out")
+
+    def to_device(self, arr):
+        import warnings
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")              # a file image is a read-only array; it is only read
+            t = self.torch.from_numpy(arr).to("cuda")
+        self.live.add(t)
+        return t.data_ptr(), t
+
+
+def pack_device(lib, src_ptr, nbytes, fh, chunk_size=1 << 20, typesize=8, clevel=5, shuffle=1, cname=b"lz4", checksum=1,
+                batch_bytes=1 << 30, mem=None):
+    """Compress the `nbytes` bytes at the DEVICE pointer `src_ptr` into the open binary file `fh`: the file `pack` writes for the same
+    bytes and settings.  Per `batch_bytes` of source: blosc_gpu_compress_packed (align 1) into one device container,
+    blosc_gpu_checksum_packed over its chunks, ONE device-to-host copy of the used bytes, and the chunks and digests written from that
+    buffer.  Returns (nchunks, bytes written)."""
+    if not 0 <= checksum < len(CHECKSUMS):
+        raise BlpkError("unknown checksum")
+    if chunk_size <= 0 or chunk_size > (1 << 31) - 17:
+        raise BlpkError("chunk_size out of range")
+    mem = mem if mem is not None else TorchMem()
+    n = int(nbytes)
+    nchunks = (n + chunk_size - 1) // chunk_size if n else 0
+    last = n - (nchunks - 1) * chunk_size if nchunks else 0
+    start = fh.tell()
+    fh.write(pack_header(nchunks, chunk_size, last, typesize, checksum))
+    off_pos = fh.tell()
+    offsets = np.full(nchunks, -1, "<i8")
+    fh.write(offsets.tobytes())
+    per_batch = max(1, batch_bytes // chunk_size)
+    cont = keep = None; room = 0
+    for b0 in range(0, nchunks, per_batch):
+        b1 = min(nchunks, b0 + per_batch)
+        m = b1 - b0
+        sizes = [min(n, (k + 1) * chunk_size) - k * chunk_size for k in range(b0, b1)]
+        ssz = (C.c_size_t * m)(*sizes)
+        bound = lib.blosc_gpu_packed_bound(m, ssz, 1)
+        if cont is None or bound > room:
+            keep = None                                  # (the first batch is the largest: this runs once)
+            cont, keep = mem.alloc(bound); room = bound
+        off = (C.c_size_t * (m + 1))(); res = (C.c_int * m)()
+        srcs = (C.c_void_p * m)(*[src_ptr + k * chunk_size for k in range(b0, b1)])
+        rc = lib.blosc_gpu_compress_packed(clevel, shuffle, typesize, cname, 0, m, srcs, ssz, cont, room, 1, off, res, None)
+        if rc != 0 or any(r <= 0 for r in res):
+            raise BlpkError(f"compression failed (rc {rc}, results {list(res)[:4]}...)")
+        dig = (C.c_uint * m)()
+        if checksum:
+            rc = lib.blosc_gpu_checksum_packed(checksum, m, cont, room, off, (C.c_size_t * m)(*res), dig, None)
+            if rc != 0:
+                raise BlpkError(f"checksums failed (rc {rc})")
+        used = int(off[m])
+        body = memoryview(np.ascontiguousarray(mem.to_host(cont, used)))
+        digests = memoryview(np.asarray(dig, dtype="<u4").view(np.uint8))
+        for k in range(m):
+            offsets[b0 + k] = fh.tell() - start
+            fh.write(body[off[k]:off[k] + res[k]])
+            if checksum:
+                fh.write(digests[4 * k:4 * k + 4])
+    end = fh.tell()
+    fh.seek(off_pos); fh.write(offsets.tobytes()); fh.seek(end)
+    return nchunks, end - start
+
+
+def unpack_device(lib, fh, dest_ptr=None, destsize=0, verify=True, mem=None):
+    """Read a bloscpack file from the open binary file `fh` into the `destsize` bytes of DEVICE memory at `dest_ptr`; returns the plain
+    size (dest_ptr None: the size query, nothing is uploaded or decoded).  The file image is uploaded once; blosc_gpu_checksum_packed
+    digests the chunks in it, the digests are compared with the stored ones on the host, and blosc_gpu_decompress_packed decodes the same
+    image - a chunk's span to the next one is its bytes plus the digest, which that call takes as padding.  Header, table and chunk
+    headers get `unpack`'s checks.  A file without an offset table, or whose table does not rise strictly, is `unpack`'s."""
+    raw = fh.read()
+    h = unpack_header(raw)
+    pos = HEADER_LENGTH
+    if h["metadata"]:
+        if len(raw) < pos + METADATA_HEADER_LENGTH:
+            raise BlpkError("truncated metadata header")
+        max_meta = struct.unpack("<I", raw[pos + 16:pos + 20])[0]
+        dlen = {0: 0, 1: 4, 2: 4, 3: 16, 4: 20, 5: 28, 6: 32, 7: 48, 8: 64}.get(raw[pos + 9])
+        if dlen is None:
+            raise BlpkError("metadata checksum kind")
+        pos += METADATA_HEADER_LENGTH + max_meta + dlen
+    nch = h["nchunks"]
+    dlen = 4 if h["checksum"] else 0
+    if not h["offsets"]:
+        raise BlpkError("no offset table: not a file for unpack_device, use unpack")
+    tot = nch + h["max_app_chunks"]
+    if len(raw) < pos + 8 * tot:
+        raise BlpkError("truncated offset table")
+    offs = [int(o) for o in np.frombuffer(raw, "<i8", tot, pos)[:nch]]
+    sizes = []; cbytes = []
+    for k, o in enumerate(offs):
+        if o < 0 or o + 16 > len(raw):
+            raise BlpkError(f"chunk {k}: offset outside the file")
+        nb, _bs, cb = struct.unpack_from("<iii", raw, o + 4)
+        if cb < 16 or o + cb + dlen > len(raw) or nb < 0:
+            raise BlpkError(f"chunk {k}: header sizes outside the file")
+        if k and o <= offs[k - 1]:
+            raise BlpkError(f"chunk {k}: the offset table does not rise: not a file for unpack_device, use unpack")
+        if k and offs[k - 1] + cbytes[-1] + dlen > o:
+            raise BlpkError(f"chunk {k - 1}: runs into chunk {k}")
+        sizes.append(nb); cbytes.append(cb)
+    total = int(sum(sizes))
+    if dest_ptr is None:
+        return total
+    if total > destsize:
+        raise BlpkError(f"destination of {destsize} bytes for {total}")
+    if nch == 0:
+        return 0
+    mem = mem if mem is not None else TorchMem()
+    image, keep = mem.to_device(np.frombuffer(raw, np.uint8))
+    table = (C.c_size_t * (nch + 1))(*offs, offs[-1] + cbytes[-1] + dlen)
+    if verify and dlen:
+        dig = (C.c_uint * nch)()
+        rc = lib.blosc_gpu_checksum_packed(h["checksum"], nch, image, len(raw), table, (C.c_size_t * nch)(*cbytes), dig, None)
+        if rc != 0:
+            raise BlpkError(f"checksums failed (rc {rc})")
+        for k in range(nch):
+            if dig[k] != struct.unpack_from("<I", raw, offs[k] + cbytes[k])[0]:
+                raise BlpkError(f"chunk {k}: checksum mismatch")
+    doff = (C.c_size_t * (nch + 1))(); res = (C.c_int * nch)()
+    rc = lib.blosc_gpu_decompress_packed(nch, image, len(raw), table, dest_ptr, destsize, doff, res, None)
+    if rc != 0 or any(r != s for r, s in zip(res, sizes)):
+        raise BlpkError(f"decompression failed (rc {rc}, results {list(res)[:4]}...)")
+    del keep
+    return total
 
 
 def pack_file(lib, src_path, dst_path, **kw):

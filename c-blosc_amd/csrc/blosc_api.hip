@@ -14,6 +14,7 @@
 #include "../../include/blosc_gpu.h"
 #include "../../include/blosc_gpu_packed.h"
 #include "../../include/blosc_gpu_getitem.h"
+#include "../../include/blosc_gpu_checksum.h"
 #include "blosc_format.h"
 #include "engine.h"
 
@@ -477,6 +478,40 @@ int blosc_gpu_getitem_packed(int nchunks, const void* container, size_t containe
   return r;
 }
 
+// ---- adler32 / crc32 of many runs (include/blosc_gpu_checksum.h) ---------------------------------------
+static const size_t kChecksumMaxRun = (size_t)INT32_MAX + 16;      // beyond the largest chunk
+static int checksum_runs(int kind, int nruns, Job* jobs, unsigned int* digest_out, void* stream) {
+  int r = -1;
+  if (jobs) {
+    bool ok = true;
+    for (int i = 0; i < nruns && ok; i++) ok = jobs[i].srcsize <= kChecksumMaxRun && (jobs[i].srcsize == 0 || jobs[i].src);
+    if (ok) r = engine_checksum_batch(kind, nruns, jobs, digest_out, (hipStream_t)stream);
+  }
+  free(jobs);
+  return r;
+}
+int blosc_gpu_checksum_batch(int kind, int nruns, const void* const* src, const size_t* nbytes, unsigned int* digest_out, void* stream) {
+  if (kind != BLOSC_GPU_CHECKSUM_ADLER32 && kind != BLOSC_GPU_CHECKSUM_CRC32) return -1;
+  if (nruns <= 0) return 0;
+  if (!src || !nbytes || !digest_out) return -1;
+  Job* jobs = (Job*)malloc(sizeof(Job) * (size_t)nruns);
+  for (int i = 0; jobs && i < nruns; i++) jobs[i] = Job{src[i], nullptr, nbytes[i], 0};
+  return checksum_runs(kind, nruns, jobs, digest_out, stream);
+}
+int blosc_gpu_checksum_packed(int kind, int nruns, const void* container, size_t containersize, const size_t* offsets,
+                              const size_t* length, unsigned int* digest_out, void* stream) {
+  if (kind != BLOSC_GPU_CHECKSUM_ADLER32 && kind != BLOSC_GPU_CHECKSUM_CRC32) return -1;
+  if (nruns <= 0) return 0;
+  if (!offsets || !digest_out) return -1;
+  for (int i = 0; i < nruns; i++)
+    if (offsets[i + 1] < offsets[i] || (length && length[i] > offsets[i + 1] - offsets[i])) return -1;
+  if (offsets[nruns] > containersize || (offsets[nruns] > offsets[0] && !container)) return -1;
+  Job* jobs = (Job*)malloc(sizeof(Job) * (size_t)nruns);
+  for (int i = 0; jobs && i < nruns; i++)
+    jobs[i] = Job{(const uint8_t*)container + offsets[i], nullptr, length ? length[i] : offsets[i + 1] - offsets[i], 0};
+  return checksum_runs(kind, nruns, jobs, digest_out, stream);
+}
+
 // Filters as stand-alone calls on HOST buffers, same names and signatures as the symbols the
 // reference exports for its own shuffle tests (blosc/shuffle.h:34-61 under BLOSC_TESTING).  The
 // shuffle variants of the byte filter with a bitshuffle-only case (bsize < typesize: not applied,
@@ -536,6 +571,9 @@ __attribute__((visibility("default"))) int blosc_amd_policy_split(int codec, int
 }
 // test hook for the pass logic of the batched getitem (tests/test_gpu_getitem_ranges.py, tests/test_emu_getitem_ranges.py): 0 = the default bound
 __attribute__((visibility("default"))) void blosc_amd_getitem_pass_bytes(size_t bytes) { engine_getitem_pass_bytes(bytes); }
+
+// test hook for the tile logic of the checksum calls (tests/test_emu_checksum.py): 0 = the default tile
+__attribute__((visibility("default"))) void blosc_amd_checksum_tile_bytes(size_t bytes) { engine_checksum_tile_bytes(bytes); }
 
 void blosc_gpu_profile(int enable) { engine_prof_enable(enable); }
 void blosc_gpu_profile_reset(void) { engine_prof_reset(); }

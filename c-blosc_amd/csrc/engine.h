@@ -60,6 +60,11 @@ int engine_getitem_batch(int nchunks, const Job* chunks, int nranges, const Item
                          const PackedBuffer* packed = nullptr);
 void engine_getitem_pass_bytes(size_t bytes);   // test hook: decoded bytes per pass of engine_getitem_batch (0: the default, 256 MiB)
 
+// zlib's adler32 (kind 1) / crc32 (kind 2) of n runs in device memory (include/blosc_gpu_checksum.h): runs[i].src and runs[i].srcsize;
+// an empty run's pointer is never read.  digests[] is written only when the call answers 0.
+int engine_checksum_batch(int kind, int n, const Job* runs, uint32_t* digests, hipStream_t stream);
+void engine_checksum_tile_bytes(size_t bytes);  // test hook: bytes per tile (a multiple of 16 up to 1 MiB; 0: the default, 256 KiB)
+
 // one block through one filter kernel, host buffers (test hook; kind 0..3 = shuffle, unshuffle, bitshuffle, bitunshuffle)
 int engine_filter(int kind, size_t typesize, size_t blocksize, const void* src, void* dst);
 

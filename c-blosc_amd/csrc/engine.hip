@@ -24,6 +24,7 @@
 #include "k_zstd.hip"
 #include "k_zstd2.hip"
 #include "k_zlib.hip"
+#include "k_checksum.hip"
 
 namespace bamd {
 
@@ -1491,6 +1492,71 @@ int engine_getitem_batch(int nchunks, const Job* chunks, int nranges, const Item
   }
   for (int p = 0; p <= pass; p++)
     if (getitem_pass(st, p, uc, hdrs, jobs, nranges, pr, results, stream)) return -1;
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// adler32 / crc32 of many runs (include/blosc_gpu_checksum.h, k_checksum.hip)
+// ---------------------------------------------------------------------------------------------
+static std::atomic<uint32_t> g_checksum_tile{CK_TILE_DEFAULT};
+void engine_checksum_tile_bytes(size_t bytes) {      // test hook: several tiles per run on small inputs
+  const size_t t = bytes ? (bytes > CK_TILE_MAX ? CK_TILE_MAX : bytes) & ~(size_t)15 : CK_TILE_DEFAULT;
+  g_checksum_tile.store((uint32_t)(t < 16 ? 16 : t));
+}
+
+// One upload (the run table, the prefix sum of the runs' tile counts, the crc32 constants), the tile kernel, the combine kernel, one
+// download of 4 bytes per run, one synchronisation - whatever the number of runs and their sizes.
+int engine_checksum_batch(int kind, int n, const Job* runs, uint32_t* digests, hipStream_t stream) {
+  if (n <= 0) return 0;
+  CtxGuard ctx; EngineState& st = *ctx.st;
+  if (ensure_device(st)) return -1;
+  const uint32_t tile = g_checksum_tile.load();
+  static uint32_t consts[CK_NCONST];
+  static std::once_flag consts_once;
+  std::call_once(consts_once, [] { ck_constants(consts); });
+  Carver tv;                                  // the same layout in the pinned arena and at the front of the device arena
+  const size_t o_runs = tv.take(sizeof(CkRun) * (size_t)n);
+  const size_t o_tile0 = tv.take(sizeof(uint64_t) * ((size_t)n + 1));
+  const size_t o_consts = tv.take(sizeof consts);
+  const size_t table_bytes = tv.off;
+  const size_t o_digests = tv.take(sizeof(uint32_t) * (size_t)n);
+  if (st.pin.ensure(tv.off)) return -1;
+  uint8_t* P = st.pin.base;
+  CkRun* hr = (CkRun*)(P + o_runs);
+  uint64_t* ht = (uint64_t*)(P + o_tile0);
+  uint64_t ntiles = 0;
+  for (int i = 0; i < n; i++) {
+    hr[i] = CkRun{(const uint8_t*)runs[i].src, (uint64_t)runs[i].srcsize};
+    ht[i] = ntiles;
+    ntiles += ((uint64_t)runs[i].srcsize + tile - 1) / tile;
+  }
+  ht[n] = ntiles;
+  memcpy(P + o_consts, consts, sizeof consts);
+  const size_t o_partials = tv.take(sizeof(uint32_t) * (size_t)(ntiles ? ntiles : 1));
+  if (st.dev.ensure(tv.off)) return -1;
+  uint8_t* D = st.dev.base;
+  HIP_TRY(hipMemcpyAsync(D, P, table_bytes, hipMemcpyHostToDevice, stream));
+  const CkRun* d_runs = (const CkRun*)(D + o_runs);
+  const uint64_t* d_tile0 = (const uint64_t*)(D + o_tile0);
+  const uint32_t* d_consts = (const uint32_t*)(D + o_consts);
+  uint32_t* d_partials = (uint32_t*)(D + o_partials);
+  uint32_t* d_digests = (uint32_t*)(D + o_digests);
+  if (ntiles) {
+    ProfScope ps(st, stream, "k_checksum_tiles");
+    const uint64_t want = (ntiles + CK_WAVES - 1) / CK_WAVES, most = (uint64_t)(st.cus > 0 ? st.cus : 256) * CK_WGS_PER_CU;
+    hipLaunchKernelGGL(k_checksum_tiles, dim3((unsigned)(want < most ? want : most)), dim3(CK_THREADS), 0, stream,
+                       kind, d_runs, d_tile0, (uint32_t)n, ntiles, tile, d_consts, d_partials);
+  }
+  {
+    ProfScope ps(st, stream, "k_checksum_combine");
+    hipLaunchKernelGGL(k_checksum_combine, grid1((size_t)n, CK_WAVES), dim3(CK_THREADS), 0, stream,
+                       kind, d_runs, d_tile0, (uint32_t)n, d_consts, d_partials, d_digests);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(P + o_digests, d_digests, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  prof_collect(st);
+  memcpy(digests, P + o_digests, sizeof(uint32_t) * (size_t)n);
   return 0;
 }
 

@@ -35,7 +35,11 @@ BLOSC_EXPORT int blosc_gpu_set_device(int device);
 /* Batched blosc_compress_ctx (blosc/blosc.h:245-248).  Chunk i: nbytes[i] bytes at src[i] ->
  * a chunk of at most destsize[i] bytes at dest[i]; cbytes_out[i] gets what blosc_compress_ctx
  * would return for it.  `compressor` NULL = the global compressor (blosc_set_compressor);
- * `blocksize` 0 = automatic.  Returns 0, or <0 if the device could not be used.  src / dest are DEVICE (or managed) memory. */
+ * `blocksize` 0 = automatic.  Returns 0, or <0 if the device could not be used.  src / dest are DEVICE (or managed) memory.
+ * src[i] and dest[i] may have any alignment (a slice of a byte tensor will do).  A chunk's outcome depends on its own destsize[i] alone:
+ * a destsize below the size of the chunk (and below nbytes[i] + 16, the room of the stored fallback) answers 0, as does any destsize
+ * below 16, which writes nothing at all.  No byte in front of dest[i] or at or behind dest[i] + destsize[i] is written, whatever the
+ * outcome, and a chunk that fits leaves the bytes behind its cbytes alone (tests/test_gpu_batch_bounds.py). */
 BLOSC_EXPORT int blosc_gpu_compress_batch(int clevel, int doshuffle, size_t typesize, const char* compressor,
                                           size_t blocksize, int nchunks, const void* const* src,
                                           const size_t* nbytes, void* const* dest, const size_t* destsize,
@@ -43,7 +47,10 @@ BLOSC_EXPORT int blosc_gpu_compress_batch(int clevel, int doshuffle, size_t type
 
 /* Batched blosc_decompress (blosc/blosc.h:280).  srcsize may be NULL (trust each header's
  * cbytes, as the reference does) or give the bytes available at src[i] (then a header claiming
- * more is rejected with -1).  nbytes_out[i] gets blosc_decompress's return value. */
+ * more is rejected with -1).  nbytes_out[i] gets blosc_decompress's return value.
+ * src[i] and dest[i] may have any alignment.  Exactly the chunk's nbytes are written at dest[i]: no byte in front of dest[i], none at or
+ * behind dest[i] + destsize[i], none between dest[i] + nbytes and dest[i] + destsize[i]; a destsize[i] below the chunk's nbytes answers
+ * -1 and writes nothing. */
 BLOSC_EXPORT int blosc_gpu_decompress_batch(int nchunks, const void* const* src, const size_t* srcsize,
                                             void* const* dest, const size_t* destsize, int* nbytes_out,
                                             void* stream);

@@ -1,7 +1,7 @@
 """c-blosc_amd — Python-side loader for libblosc_amd.so (ctypes; test / bench plumbing only).
 
 The product is the C-ABI shared library built from ``csrc/`` (see ``include/blosc.h`` and
-``include/blosc_gpu.h``, ``include/blosc_gpu_packed.h``, ``include/blosc_gpu_getitem.h``, ``include/blosc_gpu_checksum.h``).  This module only locates it, declares argument types and offers small
+``include/blosc_gpu.h``, ``include/blosc_gpu_packed.h``, ``include/blosc_gpu_params.h``, ``include/blosc_gpu_getitem.h``, ``include/blosc_gpu_checksum.h``).  This module only locates it, declares argument types and offers small
 numpy conveniences that mirror how the reference is driven from Python through ctypes
 (SURVEY.md §A.8).  There is no CPU implementation here: if the library is missing, ``load()``
 raises; if there is no GPU, the library's calls return errors.
@@ -39,7 +39,34 @@ GETITEM_SYMBOLS = [     # include/blosc_gpu_getitem.h
 CHECKSUM_SYMBOLS = [    # include/blosc_gpu_checksum.h
     "blosc_gpu_checksum_batch", "blosc_gpu_checksum_packed",
 ]
+PARAMS_SYMBOLS = [      # include/blosc_gpu_params.h
+    "blosc_gpu_compress_batch_params", "blosc_gpu_compress_packed_params",
+]
 CHECKSUM_ADLER32, CHECKSUM_CRC32 = 1, 2
+COMPCODES = {b"blosclz": 0, b"lz4": 1, b"lz4hc": 2, b"snappy": 3, b"zlib": 4, b"zstd": 5}      # include/blosc.h
+
+
+class CParams(C.Structure):
+    """blosc_gpu_cparams (include/blosc_gpu_params.h): one chunk's compression parameters"""
+    _fields_ = [("clevel", C.c_int), ("doshuffle", C.c_int), ("compcode", C.c_int), ("splitmode", C.c_int),
+                ("typesize", C.c_size_t), ("blocksize", C.c_size_t)]
+
+
+def cparams(typesize, clevel=5, shuffle=1, cname=b"lz4", blocksize=0, splitmode=0):
+    """A CParams from the arguments DeviceBatch.compress takes; cname: a name (bytes or str), a compcode, or None for the global compressor."""
+    if cname is None:
+        code = -1
+    elif isinstance(cname, int):
+        code = cname
+    else:
+        code = COMPCODES[cname.encode() if isinstance(cname, str) else cname]
+    return CParams(clevel, shuffle, code, splitmode, typesize, blocksize)
+
+
+def params_table(params):
+    """The host array of blosc_gpu_cparams a call takes, from a list of CParams (or of argument tuples / dicts of cparams())"""
+    rows = [p if isinstance(p, CParams) else (cparams(**p) if isinstance(p, dict) else cparams(*p)) for p in params]
+    return (CParams * max(len(rows), 1))(*rows)
 
 _lib = None
 
@@ -93,6 +120,8 @@ def load():
         L.blosc_gpu_decompress_batch_multi.argtypes = [i, C.POINTER(i), i, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(i)]
     if hasattr(L, "blosc_gpu_compress_packed"):
         declare_packed(L)
+    if hasattr(L, "blosc_gpu_compress_batch_params"):
+        declare_params(L)
     if hasattr(L, "blosc_gpu_getitem_batch"):
         declare_getitem(L)
     if hasattr(L, "blosc_gpu_checksum_batch"):
@@ -123,6 +152,13 @@ def declare_packed(L):
                                             C.POINTER(sz), C.POINTER(i), vp]
     L.blosc_gpu_decompress_packed.argtypes = [i, vp, sz, C.POINTER(sz), vp, sz, C.POINTER(sz), C.POINTER(i), vp]
     L.blosc_gpu_cbuffer_sizes_batch.argtypes = [i, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), vp]
+
+
+def declare_params(L):
+    """argtypes of include/blosc_gpu_params.h on a library handle (load() calls it; the CPU tests call it on their emulator build)."""
+    vp, sz, i = C.c_void_p, C.c_size_t, C.c_int
+    L.blosc_gpu_compress_batch_params.argtypes = [i, C.POINTER(CParams), C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(i), vp]
+    L.blosc_gpu_compress_packed_params.argtypes = [i, C.POINTER(CParams), C.POINTER(vp), C.POINTER(sz), vp, sz, sz, C.POINTER(sz), C.POINTER(i), vp]
 
 
 def declare_getitem(L):
@@ -182,6 +218,12 @@ class DeviceBatch:
         return load().blosc_gpu_compress_batch(clevel, shuffle, typesize, cname, blocksize, self.n, self.src,
                                                self.ssz, self.dst, self.dsz, self.res, stream)
 
+    def compress_params(self, params, stream=None, lib=None):
+        """chunk i with params[i] (include/blosc_gpu_params.h; params: see params_table), the whole batch in one call"""
+        assert len(params) == self.n
+        return (lib if lib is not None else load()).blosc_gpu_compress_batch_params(self.n, params_table(params), self.src, self.ssz, self.dst, self.dsz,
+                                                                                    self.res, stream)
+
     def decompress(self, stream=None, with_srcsize=True):
         return load().blosc_gpu_decompress_batch(self.n, self.src, self.ssz if with_srcsize else None, self.dst,
                                                  self.dsz, self.res, stream)
@@ -209,6 +251,12 @@ class PackedBatch:
     def compress(self, src_ptrs, src_sizes, dest, destsize, typesize, clevel=5, shuffle=1, cname=b"lz4", blocksize=0, align=1, stream=None):
         return self.lib.blosc_gpu_compress_packed(clevel, shuffle, typesize, cname, blocksize, self.n, (C.c_void_p * self.n)(*src_ptrs),
                                                   (C.c_size_t * self.n)(*src_sizes), dest, destsize, align, self.off, self.res, stream)
+
+    def compress_params(self, src_ptrs, src_sizes, params, dest, destsize, align=1, stream=None):
+        """chunk i with params[i] (include/blosc_gpu_params.h; params: see params_table) into one container in the caller's order"""
+        assert len(params) == self.n
+        return self.lib.blosc_gpu_compress_packed_params(self.n, params_table(params), (C.c_void_p * self.n)(*src_ptrs),
+                                                         (C.c_size_t * self.n)(*src_sizes), dest, destsize, align, self.off, self.res, stream)
 
     def decompress(self, container, containersize, offsets, dest, destsize, stream=None):
         return self.lib.blosc_gpu_decompress_packed(self.n, container, containersize, (C.c_size_t * (self.n + 1))(*offsets), dest, destsize,

@@ -1,4 +1,4 @@
-// blosc_api.hip — the exported C ABI (include/blosc.h, include/blosc_gpu.h, include/blosc_gpu_packed.h).
+// blosc_api.hip — the exported C ABI (include/blosc.h, include/blosc_gpu.h, include/blosc_gpu_packed.h, include/blosc_gpu_params.h).
 //
 // Host-side mirror of the reference's public layer (blosc/blosc.c:1282-1703, :1951-2317):
 // process globals, the per-call environment overrides, name/code tables and cbuffer introspection
@@ -13,6 +13,7 @@
 #include "../../include/blosc.h"
 #include "../../include/blosc_gpu.h"
 #include "../../include/blosc_gpu_packed.h"
+#include "../../include/blosc_gpu_params.h"
 #include "../../include/blosc_gpu_getitem.h"
 #include "../../include/blosc_gpu_checksum.h"
 #include "blosc_format.h"
@@ -169,7 +170,7 @@ static int compress_one(int clevel, int doshuffle, size_t typesize, size_t nbyte
   }
   Job job{src, dest, nbytes, destsize};
   int result = -1;
-  if (engine_compress_batch(p, 1, &job, &result, sd && dd, (hipStream_t)0) != 0) return -1;
+  if (engine_compress_batch(&p, false, 1, &job, &result, sd && dd, (hipStream_t)0) != 0) return -1;
   return result;
 }
 
@@ -261,7 +262,7 @@ static int compress_batch(int clevel, int doshuffle, size_t typesize, const char
   if (!jobs) return -1;
   for (int i = 0; i < nchunks; i++) jobs[i] = Job{src[i], dest[i], nbytes[i], destsize[i]};
   CompressParams p{clevel, doshuffle, typesize, code, (int32_t)(blocksize ? blocksize : (size_t)g_force_blocksize), g_splitmode};
-  int r = engine_compress_batch(p, nchunks, jobs, cbytes_out, device_ptrs, (hipStream_t)stream);
+  int r = engine_compress_batch(&p, false, nchunks, jobs, cbytes_out, device_ptrs, (hipStream_t)stream);
   free(jobs);
   return r;
 }
@@ -326,8 +327,56 @@ int blosc_gpu_compress_packed(int clevel, int doshuffle, size_t typesize, const 
   for (int i = 0; i < nchunks; i++) jobs[i] = Job{src[i], nullptr, nbytes[i], nbytes[i] + BLOSC_MAX_OVERHEAD};
   CompressParams p{clevel, doshuffle, typesize, code, (int32_t)(blocksize ? blocksize : (size_t)g_force_blocksize), g_splitmode};
   const PackedBuffer pk{dest, destsize, align, offsets_out};
-  int r = engine_compress_batch(p, nchunks, jobs, cbytes_out, true, (hipStream_t)stream, &pk);
+  int r = engine_compress_batch(&p, false, nchunks, jobs, cbytes_out, true, (hipStream_t)stream, &pk);
   free(jobs);
+  return r;
+}
+
+// ---- parameters per chunk (include/blosc_gpu_params.h) ---------------------------------------
+// The two calls above with a parameter set per chunk.  The engine checks every chunk's parameters by itself, in the reference's order
+// (sizes, then parameters: -10, then the codec: -5), so an unusable slot is the outcome of its chunk alone.
+static CompressParams* chunk_params(int nchunks, const blosc_gpu_cparams* params) {
+  CompressParams* p = (CompressParams*)malloc(sizeof(CompressParams) * (size_t)nchunks);
+  for (int i = 0; p && i < nchunks; i++) {
+    const blosc_gpu_cparams& c = params[i];
+    p[i] = CompressParams{c.clevel, c.doshuffle, c.typesize, c.compcode == -1 ? g_compressor : c.compcode,
+                          (int32_t)(c.blocksize ? c.blocksize : (size_t)g_force_blocksize), c.splitmode ? c.splitmode : g_splitmode};
+    // a code outside 0 ... 5 is "not built" like Snappy (the engine's tables are indexed by the codes it knows)
+    if (p[i].codec < 0 || p[i].codec > 5) p[i].codec = BLOSC_SNAPPY;
+    // a split mode that does not exist is a parameter error of its chunk: handed on as a filter the engine's parameter check rejects
+    // (the global mode of the single-parameter calls is never checked - as in the reference - so the check cannot live there)
+    if (c.splitmode < 0 || c.splitmode > BLOSC_FORWARD_COMPAT_SPLIT) p[i].doshuffle = -1;
+  }
+  return p;
+}
+int blosc_gpu_compress_batch_params(int nchunks, const blosc_gpu_cparams* params, const void* const* src, const size_t* nbytes,
+                                    void* const* dest, const size_t* destsize, int* cbytes_out, void* stream) {
+  if (nchunks <= 0) return 0;
+  if (!params || !src || !nbytes || !dest || !destsize || !cbytes_out) return -1;
+  Job* jobs = (Job*)malloc(sizeof(Job) * (size_t)nchunks);
+  CompressParams* p = chunk_params(nchunks, params);
+  int r = -1;
+  if (jobs && p) {
+    for (int i = 0; i < nchunks; i++) jobs[i] = Job{src[i], dest[i], nbytes[i], destsize[i]};
+    r = engine_compress_batch(p, true, nchunks, jobs, cbytes_out, true, (hipStream_t)stream);
+  }
+  free(jobs); free(p);
+  return r;
+}
+int blosc_gpu_compress_packed_params(int nchunks, const blosc_gpu_cparams* params, const void* const* src, const size_t* nbytes,
+                                     void* dest, size_t destsize, size_t align, size_t* offsets_out, int* cbytes_out, void* stream) {
+  if (nchunks < 0 || !offsets_out || !packed_align(&align)) return -1;
+  if (nchunks == 0) { offsets_out[0] = 0; return 0; }
+  if (!params || !src || !nbytes || !cbytes_out || (!dest && destsize)) return -1;
+  Job* jobs = (Job*)malloc(sizeof(Job) * (size_t)nchunks);
+  CompressParams* p = chunk_params(nchunks, params);
+  int r = -1;
+  if (jobs && p) {
+    for (int i = 0; i < nchunks; i++) jobs[i] = Job{src[i], nullptr, nbytes[i], nbytes[i] + BLOSC_MAX_OVERHEAD};      // (as blosc_gpu_compress_packed)
+    const PackedBuffer pk{dest, destsize, align, offsets_out};
+    r = engine_compress_batch(p, true, nchunks, jobs, cbytes_out, true, (hipStream_t)stream, &pk);
+  }
+  free(jobs); free(p);
   return r;
 }
 

@@ -42,7 +42,9 @@ struct PackedBuffer {
 // reference's return-value conventions) or a negative number when the device could not be
 // used at all (no GPU, out of memory, launch failure) — never a silent CPU fallback.
 // packed != nullptr (device pointers only): jobs[i].dst is ignored, jobs[i].dstsize is the chunk's own limit
-int engine_compress_batch(const CompressParams& p, int n, const Job* jobs, int* results, bool device_ptrs,
+// compress: per_chunk - chunk i is compressed with params[i] (include/blosc_gpu_params.h); otherwise every chunk with params[0].  A
+// parameter error (-10) or a codec that is not built (-5) is the outcome of its chunk alone.
+int engine_compress_batch(const CompressParams* params, bool per_chunk, int n, const Job* jobs, int* results, bool device_ptrs,
                           hipStream_t stream, const PackedBuffer* packed = nullptr);
 int engine_decompress_batch(int n, const Job* jobs, int* results, bool device_ptrs, hipStream_t stream,
                             const PackedBuffer* packed = nullptr);

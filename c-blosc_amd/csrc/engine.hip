@@ -170,10 +170,14 @@ struct EngineState {
   // marks the cache invalid, has the caller's builder fill `queues` (and `zqueues`), and reserves device and pinned room; upload() enqueues
   // the copies; commit() - AFTER the call's synchronisation, when the uploads are known to have arrived - adopts the key.  A call that
   // fails in between therefore leaves valid == false, and the next one builds again.
+  // modes[i], compress: chunk i's fusion flag and, above it, the encoder variant its streams go to (0: it has none) - batches that group
+  // differently have different queues
   struct TableKey { std::vector<BlockDesc> blocks; std::vector<uint32_t> modes; std::vector<int> order; int nq = 0; };
+  // compress: the task queues of one encoder variant inside `queues` (queue_order.h: build_encode_queues) - off[9] at q_at, shoff[9] at sh_at
+  struct EncGroup { int mode; size_t q_at, sh_at; int32_t ntasks; };
   struct TableCache {
     TableKey key; bool valid = false;
-    DeviceArena tabs; size_t o_queues = 0, o_zqueues = 0, sh_at = 0; int32_t ntasks = 0;      // the block table lies at tabs.base
+    DeviceArena tabs; size_t o_queues = 0, o_zqueues = 0; std::vector<EncGroup> groups;      // the block table lies at tabs.base
     bool hit = false;                                                                          // this call's begin()
     std::vector<int32_t> queues, zqueues; size_t p_blocks = 0, p_queues = 0, p_zqueues = 0;    // a miss's tables on their way to the device
     bool same(const TableKey& k) const {
@@ -527,13 +531,54 @@ struct StreamProfile {
 #define BAMD_PROF_ARG(var)
 #endif
 
+// The variant of k_encode_streams_t that serves a (codec, clevel), and what its launch needs.  The switches are read per call, as ever.
+struct EncVariant {
+  int mode = ENC_LZ; const char* name = "k_encode_streams";
+  int waves_per_cu = 0;            // what fits into a CU's LDS
+  bool zstd = false, zdyn = false; // Zstd: predefined FSE tables + one sequence scratch per persistent wave; zlib with dynamic codes: the token scratch
+  int detect = 0;                  // the periodic-plane shortcut of the shuffle tasks
+};
+static EncVariant encoder_variant(int codec, int clevel) {
+  EncVariant v;
+  // "lz4hc": the LZ4HC-grade search of k_encode.hip (lz4hc_encode_wave), or the plain LZ4 match finder at its highest effort
+  const bool zstd = codec == kZstd, zlibc = codec == kZlib;
+  const bool hc = codec == kLZ4HC && lz4hc_search_enabled();
+  // Zstd: sequence tables made per block (k_encode.hip: zt_make_tables) instead of the predefined ones
+  const bool ztab = zstd && zstd_tables_enabled();
+  // the LZ4HC-grade search in front of the Zstd writer (with per-block tables) / the zlib writer.
+  // Defaults after the device timings of round 3 (profiles/r03/r03a_encopts_bench_*.json, 8 GiB bench19): Zstd - the search costs 2.6 x the
+  // encode time (35.8 -> 94.9 ms) for ratio 23.8 -> 35.1, so it serves the upper clevels (the reference maps clevel >= 6 to its
+  // lazy / optimal strategies, blosc.c:502-504 + clevels.h) and stays off at the default clevel; zlib - whoever names zlib wants its
+  // ratio: search + dynamic codes give 73.4 (reference 47.4, fixed codes without search 40.5) at 57 ms per 8 GiB, still 150 GB/s.
+  const bool zsearch = (zstd && zstd_search_enabled(clevel)) || (zlibc && zlib_search_enabled());
+  const bool zhuf = zstd && (ztab || zsearch) && zstd_huffman_enabled();      // Huffman-coded literals: on top of either switch
+  const int enc_wpc_lz = (zstd || zlibc) ? ENC_WAVES_PER_CU : ENC_LZ_WAVES_PER_CU;
+  v.waves_per_cu = zsearch ? (160 * 1024) / (HC_TAB_BYTES + ZS_LDS_BYTES) : (hc ? HC_WAVES_PER_CU : enc_wpc_lz);
+  v.zstd = zstd;
+  v.zdyn = zlibc && zlib_dynamic_enabled();      // zlib with dynamic Huffman codes: two passes, the tokens in the sequence scratch
+  v.detect = (!zstd && !zlibc && periodic_enabled()) ? 1 : 0;
+  v.name = zstd ? "k_zstd_encode" : (zlibc ? "k_zlib_encode" : (hc ? "k_lz4hc_encode" : "k_encode_streams"));
+  if (zstd && zsearch) v.mode = zhuf ? ENC_ZSTD_HCH : ENC_ZSTD_HC;
+  else if (zstd && ztab) v.mode = zhuf ? ENC_ZSTD_TH : ENC_ZSTD_T;
+  else if (zstd) v.mode = ENC_ZSTD;
+  else if (zlibc && v.zdyn) v.mode = zsearch ? ENC_ZLIB_DYN_HC : ENC_ZLIB_DYN;
+  else if (zlibc && zsearch) v.mode = ENC_ZLIB_HC;
+  else if (zlibc) v.mode = ENC_ZLIB;
+  else if (hc) v.mode = ENC_HC;
+  else v.mode = ENC_LZ;
+  return v;
+}
+constexpr int kEncModes = 11;      // ENC_LZ ... ENC_ZLIB_DYN_HC
+
 // What the per-chunk loop of a compress call adds up: the tables and the sizes of the scratch areas
 struct EncodeBatch {
   std::vector<ChunkDesc> chunks; std::vector<uint8_t> live;
+  std::vector<uint8_t> variant;                      // per chunk: the encoder variant its streams go to; kEncModes: it has no streams
+  EncVariant variants[kEncModes]; bool present[kEncModes] = {false}; int ngroups = 0;
   EngineState::TableKey key;                         // key.blocks: the block table
   size_t nstr = 0, filt_bytes = 0, stage_bytes = 0;  // (the stream table itself is made on the device: k_encode_plan)
   int tiles_shuf = 0, tiles_bit = 0; bool any_shuf = false, any_bit = false;
-  explicit EncodeBatch(int n) : chunks((size_t)n), live((size_t)n, 0) {}
+  explicit EncodeBatch(int n) : chunks((size_t)n), live((size_t)n, 0), variant((size_t)n, (uint8_t)kEncModes) {}
 };
 
 // Parameter checks and geometry of chunk i of n (blosc.c:1062-1145, :1148-1247).  false: nothing runs for it, *result is its outcome.
@@ -593,7 +638,7 @@ static bool add_encode_chunk(const CompressParams& p, const Job& job, int i, int
   return true;
 }
 
-int engine_compress_batch(const CompressParams& p, int n, const Job* jobs, int* results, bool device_ptrs,
+int engine_compress_batch(const CompressParams* params, bool per_chunk, int n, const Job* jobs, int* results, bool device_ptrs,
                           hipStream_t stream, const PackedBuffer* packed) {
   if (n <= 0) return 0;
   if (packed && !device_ptrs) return -1;
@@ -604,61 +649,76 @@ int engine_compress_batch(const CompressParams& p, int n, const Job* jobs, int* 
   EncodeBatch B(n);
   HostStaging io{!device_ptrs};
   std::vector<ChunkDesc>& chunks = B.chunks;
+  // the encoder variant of every chunk that has streams: the chunks of one variant are one group, with one launch of its kernel.
+  // (codec, clevel) -> variant is looked up once per call, not per chunk: the switches behind it are environment reads
+  int8_t variant_of[6][10]; memset(variant_of, -1, sizeof variant_of);
   for (int i = 0; i < n; i++) {
+    const CompressParams& p = params[per_chunk ? i : 0];
     B.live[(size_t)i] = add_encode_chunk(p, jobs[i], i, n, !st.single_queue, B, &results[i]);
-    if (B.live[(size_t)i]) io.add((size_t)chunks[(size_t)i].nbytes, (size_t)chunks[(size_t)i].cbytes);
+    if (!B.live[(size_t)i]) continue;
+    io.add((size_t)chunks[(size_t)i].nbytes, (size_t)chunks[(size_t)i].cbytes);
+    if (chunks[(size_t)i].mode & CH_MEMCPYED) continue;
+    int8_t& m = variant_of[p.codec][p.clevel];      // (both in range: the chunk passed add_encode_chunk's checks)
+    if (m < 0) { const EncVariant v = encoder_variant(p.codec, p.clevel); m = (int8_t)v.mode; B.variants[v.mode] = v; }
+    B.variant[(size_t)i] = (uint8_t)m;
+    if (!B.present[m]) { B.present[m] = true; B.ngroups++; }
   }
   const size_t nblk = B.key.blocks.size(), nstr = B.nstr;
+  // One set of plane-cost words cannot describe two kernels: a call with more than one group runs in plain block order and leaves the
+  // feedback of the one-group calls around it alone
+  const bool feedback = B.ngroups <= 1;
+  const bool cost_valid = feedback && st.enc_cost_valid;
+  const size_t ngrp = (size_t)(B.ngroups > 0 ? B.ngroups : 1);
   ht.mark(0);     // per-chunk geometry + block / stream tables
   // ---- tables: the block table and the queues, still on the device from the last call of this geometry or built and uploaded now ----
   EngineState::TableCache& tc = st.enc_tabs;
   B.key.nq = st.single_queue ? 1 : 8;
   B.key.modes.resize((size_t)n);
-  for (int i = 0; i < n; i++) B.key.modes[(size_t)i] = chunks[(size_t)i].mode & CH_FUSED_SHUF;
-  order_signature(B.key.blocks, st.enc_cost, st.enc_cost_valid, B.key.order);
+  for (int i = 0; i < n; i++) B.key.modes[(size_t)i] = (chunks[(size_t)i].mode & CH_FUSED_SHUF) | (B.variant[(size_t)i] < kEncModes ? (uint32_t)(B.variant[(size_t)i] + 1) << 8 : 0u);
+  order_signature(B.key.blocks, st.enc_cost, cost_valid, B.key.order);
   Carver pc;
   if (tc.begin("compress", B.key, 0, 0, pc, [&](EngineState::TableCache& t) {
-        build_encode_queues(B.key.blocks, chunks, st.enc_cost, st.enc_cost_valid, t.queues, B.key.nq, &t.sh_at);
-        t.ntasks = t.queues[8];
+        // every group's queues behind one another in the one queue table; a one-group batch: the whole batch, as it always was
+        t.groups.clear();
+        std::vector<int32_t> q;
+        for (int m = 0; m < kEncModes; m++) {
+          if (!B.present[m]) continue;
+          size_t sh_at = 0;
+          build_encode_queues(B.key.blocks, chunks, st.enc_cost, cost_valid, q, B.key.nq, &sh_at, B.ngroups > 1 ? B.variant.data() : nullptr, m);
+          t.groups.push_back({m, t.queues.size(), t.queues.size() + sh_at, q[8]});
+          t.queues.insert(t.queues.end(), q.begin(), q.end());
+        }
       })) return -1;
   // ---- workspace ----
-  // "lz4hc": the LZ4HC-grade search of k_encode.hip (lz4hc_encode_wave), or the plain LZ4 match finder at its highest effort
-  const bool zstd = p.codec == kZstd, zlibc = p.codec == kZlib;
-  const bool hc = p.codec == kLZ4HC && lz4hc_search_enabled();
-  // Zstd: sequence tables made per block (k_encode.hip: zt_make_tables) instead of the predefined ones
-  const bool ztab = zstd && zstd_tables_enabled();
-  // the LZ4HC-grade search in front of the Zstd writer (with per-block tables) / the zlib writer.
-  // Defaults after the device timings of round 3 (profiles/r03/r03a_encopts_bench_*.json, 8 GiB bench19): Zstd - the search costs 2.6 x the
-  // encode time (35.8 -> 94.9 ms) for ratio 23.8 -> 35.1, so it serves the upper clevels (the reference maps clevel >= 6 to its
-  // lazy / optimal strategies, blosc.c:502-504 + clevels.h) and stays off at the default clevel; zlib - whoever names zlib wants its
-  // ratio: search + dynamic codes give 73.4 (reference 47.4, fixed codes without search 40.5) at 57 ms per 8 GiB, still 150 GB/s.
-  const bool zsearch = (zstd && zstd_search_enabled(p.clevel)) || (zlibc && zlib_search_enabled());
-  const bool zhuf = zstd && (ztab || zsearch) && zstd_huffman_enabled();      // Huffman-coded literals: on top of either switch
-  const int enc_wpc_lz = (zstd || zlibc) ? ENC_WAVES_PER_CU : ENC_LZ_WAVES_PER_CU;
-  const int enc_wpc = zsearch ? (160 * 1024) / (HC_TAB_BYTES + ZS_LDS_BYTES) : (hc ? HC_WAVES_PER_CU : enc_wpc_lz);   // what fits into a CU's LDS
-  const bool zdyn = zlibc && zlib_dynamic_enabled();      // zlib with dynamic Huffman codes: two passes, the tokens in the sequence scratch
-  const size_t zwaves = (zstd || zdyn) ? (size_t)(st.cus > 0 ? st.cus : 256) * (size_t)enc_wpc : 0;
   Carver cv;
   const size_t o_chunks = cv.take(sizeof(ChunkDesc) * (size_t)n);
   const size_t o_streams = cv.take(sizeof(StreamDesc) * (nstr ? nstr : 1));
   const size_t o_blkoff = cv.take(sizeof(int32_t) * (nblk ? nblk : 1));
   // results + tickets | block-ready flags | cost words: taken back to back, ONE fill clears the three of them
-  const size_t o_results = cv.take(ticket_offset((size_t)n) + sizeof(uint32_t) * kEncTicketWords);
+  // (every group has ticket words and cost words of its own: group k's are the k-th set)
+  const size_t o_results = cv.take(ticket_offset((size_t)n) + sizeof(uint32_t) * kEncTicketWords * ngrp);
   const size_t o_ready = cv.take(sizeof(uint32_t) * (nblk ? nblk : 1));
-  const size_t o_cost = cv.take(sizeof(uint32_t) * kCostWords);
+  const size_t o_cost = cv.take(sizeof(uint32_t) * kCostWords * ngrp);
   const size_t clear_bytes = cv.off - o_results;
   const size_t o_filt = cv.take(B.filt_bytes + 256);
   const size_t o_stage = cv.take(B.stage_bytes + 256);
-  // Zstd: the predefined FSE tables and one sequence scratch per persistent wave
-  const size_t o_ctabs = cv.take(sizeof(zenc::CTabs) + 64);
-  const size_t o_seqbufs = cv.take(zwaves * (zdyn ? (size_t)ZD_SCRATCH_U64 : (size_t)ZS_SEQCAP) * sizeof(uint64_t) + 64);
+  // Zstd: the predefined FSE tables and one sequence scratch per persistent wave - per group that wants them (Zstd, zlib with dynamic codes)
+  size_t o_ctabs[kEncModes] = {0}, o_seqbufs[kEncModes] = {0};
+  bool any_zstd = false;
+  for (const EngineState::EncGroup& g : tc.groups) {
+    const EncVariant& v = B.variants[g.mode];
+    const size_t zwaves = (v.zstd || v.zdyn) ? (size_t)(st.cus > 0 ? st.cus : 256) * (size_t)v.waves_per_cu : 0;
+    if (v.zstd) { o_ctabs[g.mode] = cv.take(sizeof(zenc::CTabs) + 64); any_zstd = true; }
+    if (zwaves) o_seqbufs[g.mode] = cv.take(zwaves * (v.zdyn ? (size_t)ZD_SCRATCH_U64 : (size_t)ZS_SEQCAP) * sizeof(uint64_t) + 64);
+  }
   const size_t o_offsets = packed ? cv.take(sizeof(uint64_t) * ((size_t)n + 1)) : 0;      // packed: the offset table k_packed_layout writes
   if (st.dev.ensure(cv.off)) return -1;
   uint8_t* D = st.dev.base;
-  if (zstd) {
+  if (any_zstd) {
     static zenc::CTabs host_tabs; static bool built = false;
     if (!built) { zenc::build_predefined(host_tabs); built = true; }
-    HIP_TRY(hipMemcpyAsync(D + o_ctabs, &host_tabs, sizeof host_tabs, hipMemcpyHostToDevice, stream));
+    for (const EngineState::EncGroup& g : tc.groups)
+      if (B.variants[g.mode].zstd) HIP_TRY(hipMemcpyAsync(D + o_ctabs[g.mode], &host_tabs, sizeof host_tabs, hipMemcpyHostToDevice, stream));
   }
   // ---- stage the inputs of a host-pointer call, point every chunk at its scratch ----
   if (io.reserve(st.io)) return -1;
@@ -678,7 +738,7 @@ int engine_compress_batch(const CompressParams& p, int n, const Job* jobs, int* 
   // ---- upload the tables ----
   const size_t p_chunks = pc.take(sizeof(ChunkDesc) * (size_t)n);
   const size_t p_results = pc.take(sizeof(int32_t) * (size_t)n);
-  const size_t p_cost = pc.take(sizeof(uint32_t) * kCostWords);
+  const size_t p_cost = pc.take(sizeof(uint32_t) * kCostWords * ngrp);
   const size_t p_offsets = packed ? pc.take(sizeof(uint64_t) * ((size_t)n + 1)) : 0;
   if (st.pin.ensure(pc.off)) return -1;
   uint8_t* P = st.pin.base;
@@ -689,7 +749,7 @@ int engine_compress_batch(const CompressParams& p, int n, const Job* jobs, int* 
 
   ChunkDesc* d_chunks = (ChunkDesc*)(D + o_chunks); BlockDesc* d_blocks = tc.d_blocks(); StreamDesc* d_streams = (StreamDesc*)(D + o_streams);
   int32_t* d_blkoff = (int32_t*)(D + o_blkoff); int32_t* d_results = (int32_t*)(D + o_results);
-  uint32_t* d_ticket = (uint32_t*)(D + o_results + ticket_offset((size_t)n));
+  uint32_t* d_tickets = (uint32_t*)(D + o_results + ticket_offset((size_t)n));
   ht.mark(2);     // table copies to pinned memory + upload enqueues
   // ---- launch ----
   if (nstr) hipLaunchKernelGGL(k_encode_plan, grid1(nblk, 256), dim3(256), 0, stream, d_chunks, d_blocks, d_streams, (int)nblk);
@@ -702,24 +762,28 @@ int engine_compress_batch(const CompressParams& p, int n, const Job* jobs, int* 
     hipLaunchKernelGGL(k_bitfilter_fast<0>, dim3((unsigned)nblk, (unsigned)B.tiles_bit), dim3(FT_THREADS), 0, stream, d_chunks, d_blocks);
     hipLaunchKernelGGL(k_bitshuffle, dim3((unsigned)nblk, (unsigned)B.tiles_bit), dim3(FT_THREADS), 0, stream, d_chunks, d_blocks, 1);
   }
-  if (nstr) {
-    ProfScope ps(st, stream, zstd ? "k_zstd_encode" : (zlibc ? "k_zlib_encode" : (hc ? "k_lz4hc_encode" : "k_encode_streams")));
-    const int32_t* d_qoff = tc.d_qoff(); const int32_t* d_qlist = d_qoff + 9; const int32_t* d_shoff = d_qoff + tc.sh_at;
+  // one launch per group: its own queues, ticket words, cost words and scratch; the tables of chunks, blocks and streams and the
+  // block-ready flags are the batch's (a group's queues name the blocks of its own chunks only)
+  for (size_t k = 0; nstr && k < tc.groups.size(); k++) {
+    const EngineState::EncGroup& g = tc.groups[k];
+    const EncVariant& v = B.variants[g.mode];
+    if (g.ntasks <= 0) continue;
+    ProfScope ps(st, stream, v.name);
+    const int32_t* d_qoff = tc.d_qoff() + g.q_at; const int32_t* d_qlist = d_qoff + 9; const int32_t* d_shoff = tc.d_qoff() + g.sh_at;
+    uint32_t* d_ticket = d_tickets + kEncTicketWords * k;
+    uint32_t* d_cost = (uint32_t*)(D + o_cost) + kCostWords * k;
     uint32_t* d_ready = (uint32_t*)(D + o_ready);
-    uint64_t* d_seqbufs = (zstd || zdyn) ? (uint64_t*)(D + o_seqbufs) : nullptr;
-    const zenc::CTabs* d_ctabs = zstd ? (const zenc::CTabs*)(D + o_ctabs) : nullptr;
-    const int detect = (!zstd && !zlibc && periodic_enabled()) ? 1 : 0;
-    const dim3 grid(persistent_grid(st, (size_t)tc.ntasks, enc_wpc)), block(64 * ENC_WAVES);
+    uint64_t* d_seqbufs = (v.zstd || v.zdyn) ? (uint64_t*)(D + o_seqbufs[g.mode]) : nullptr;
+    const zenc::CTabs* d_ctabs = v.zstd ? (const zenc::CTabs*)(D + o_ctabs[g.mode]) : nullptr;
+    const int detect = v.detect;
+    const dim3 grid(persistent_grid(st, (size_t)g.ntasks, v.waves_per_cu)), block(64 * ENC_WAVES);
     BAMD_STREAM_PROFILE(prof, "BLOSC_AMD_ENC_PROFILE", nstr);
-#define BAMD_ENC_LAUNCH(MODE) hipLaunchKernelGGL(k_encode_streams_t<MODE>, grid, block, 0, stream, d_streams, d_ticket, d_qlist, d_qoff, d_shoff, d_chunks, d_blocks, d_ready, (uint32_t*)(D + o_cost), st.single_queue ? 1 : 0, d_seqbufs, d_ctabs, detect BAMD_PROF_ARG(prof))
-    if (zstd && zsearch) { if (zhuf) BAMD_ENC_LAUNCH(ENC_ZSTD_HCH); else BAMD_ENC_LAUNCH(ENC_ZSTD_HC); }
-    else if (zstd && ztab) { if (zhuf) BAMD_ENC_LAUNCH(ENC_ZSTD_TH); else BAMD_ENC_LAUNCH(ENC_ZSTD_T); }
-    else if (zstd) BAMD_ENC_LAUNCH(ENC_ZSTD);
-    else if (zlibc && zdyn) { if (zsearch) BAMD_ENC_LAUNCH(ENC_ZLIB_DYN_HC); else BAMD_ENC_LAUNCH(ENC_ZLIB_DYN); }
-    else if (zlibc && zsearch) BAMD_ENC_LAUNCH(ENC_ZLIB_HC);
-    else if (zlibc) BAMD_ENC_LAUNCH(ENC_ZLIB);
-    else if (hc) BAMD_ENC_LAUNCH(ENC_HC);
-    else BAMD_ENC_LAUNCH(ENC_LZ);
+#define BAMD_ENC_LAUNCH(MODE) case MODE: hipLaunchKernelGGL(k_encode_streams_t<MODE>, grid, block, 0, stream, d_streams, d_ticket, d_qlist, d_qoff, d_shoff, d_chunks, d_blocks, d_ready, d_cost, st.single_queue ? 1 : 0, d_seqbufs, d_ctabs, detect BAMD_PROF_ARG(prof)); break
+    switch (g.mode) {
+      BAMD_ENC_LAUNCH(ENC_ZSTD_HCH); BAMD_ENC_LAUNCH(ENC_ZSTD_HC); BAMD_ENC_LAUNCH(ENC_ZSTD_TH); BAMD_ENC_LAUNCH(ENC_ZSTD_T); BAMD_ENC_LAUNCH(ENC_ZSTD);
+      BAMD_ENC_LAUNCH(ENC_ZLIB_DYN_HC); BAMD_ENC_LAUNCH(ENC_ZLIB_DYN); BAMD_ENC_LAUNCH(ENC_ZLIB_HC); BAMD_ENC_LAUNCH(ENC_ZLIB);
+      BAMD_ENC_LAUNCH(ENC_HC); BAMD_ENC_LAUNCH(ENC_LZ);
+    }
 #undef BAMD_ENC_LAUNCH
   }
   if (!packed) {
@@ -744,17 +808,18 @@ int engine_compress_batch(const CompressParams& p, int n, const Job* jobs, int* 
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(P + p_results, d_results, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(P + p_cost, D + o_cost, sizeof(uint32_t) * kCostWords, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(P + p_cost, D + o_cost, sizeof(uint32_t) * kCostWords * ngrp, hipMemcpyDeviceToHost, stream));
   if (packed) HIP_TRY(hipMemcpyAsync(P + p_offsets, D + o_offsets, sizeof(uint64_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, stream));
   ht.mark(3);     // kernel launches
   // ---- collect ----
   HIP_TRY(hipStreamSynchronize(stream));
   ht.mark(4);     // waiting for the device
   prof_collect(st);
-  if (nstr && check_done((const uint32_t*)(P + p_cost), (size_t)tc.ntasks, 0, "compress")) return -1;
+  for (size_t k = 0; nstr && k < tc.groups.size(); k++)      // every group's launch took what was queued for it
+    if (check_done((const uint32_t*)(P + p_cost) + kCostWords * k, (size_t)tc.groups[k].ntasks, 0, "compress")) return -1;
   if (packed) for (int i = 0; i <= n; i++) packed->offsets[i] = (size_t)((const uint64_t*)(P + p_offsets))[i];
   tc.commit(B.key);
-  if (nstr >= 4096) { memcpy(st.enc_cost, P + p_cost, sizeof st.enc_cost); st.enc_cost_valid = true; }   // small calls say little
+  if (feedback && nstr >= 4096) { memcpy(st.enc_cost, P + p_cost, sizeof st.enc_cost); st.enc_cost_valid = true; }   // small calls say little
   const int32_t* r = (const int32_t*)(P + p_results);
   for (int i = 0; i < n; i++) if (B.live[(size_t)i]) results[i] = r[i];
   return io.collect(n, jobs, chunks, B.live, results, stream);

@@ -21,6 +21,9 @@ namespace bamd {
 // a counter of their own, by the waves that draw a negative entry and by waves that would otherwise wait for a block that is not
 // ready (k_encode.hip): when the streams are cheap (incompressible data) the transposes then run on every waiting wave instead of
 // on the few that drew the negative entries.  *sh_at = index of shoff[0] in `out`.
+// chunk_group != nullptr (a batch whose chunks go to more than one variant of the encode kernel, engine.hip): only the blocks of the
+// chunks c with chunk_group[c] == group are queued - streams, shuffle tasks and shuffle list alike, so a launch that is given these
+// queues never sees a task of another group's chunk.  A block keeps its queue g % nq whatever the group: the table is one for the batch.
 constexpr size_t kEncLookaheadDefault = 32;
 inline size_t enc_lookahead() { return kEncLookaheadDefault; }     // (swept 1 ... 64 in round 4: 8.4 ... 8.0 ms, profiles/r04/r04q_enc_lookahead_sweep.txt - the distance hardly matters)
 // BLOSC_AMD_SCHED=0: plain block order (no cost feedback)
@@ -52,12 +55,16 @@ inline void plane_order(const uint32_t* cost, bool valid, int T, std::vector<int
 // cheap streams instead of 3 ms ones.  (One pass in the decode queues' manner - expensive planes of block i + lead with the cheap
 // planes of block i, lead 16 / 64 / 256 - is 4 ... 7 % slower: profiles/r04/r04zg_enc_ab_one_pass_lead_order_rejected.txt.)
 inline void build_encode_queues(const std::vector<BlockDesc>& blocks, const std::vector<ChunkDesc>& chunks,
-                                const uint32_t* cost, bool cost_valid, std::vector<int32_t>& out, int nq = 8, size_t* sh_at = nullptr) {
+                                const uint32_t* cost, bool cost_valid, std::vector<int32_t>& out, int nq = 8, size_t* sh_at = nullptr,
+                                const uint8_t* chunk_group = nullptr, int group = 0) {
   std::vector<int32_t> q[8], sh[8];
   std::vector<uint32_t> mine[8];
   for (int x = 0; x < nq; x++) mine[x].reserve(blocks.size() / (size_t)nq + 1);
   size_t nstr_all = 0;
-  for (size_t g = 0; g < blocks.size(); g++) if (blocks[g].nstreams > 0) { mine[g % (size_t)nq].push_back((uint32_t)g); nstr_all += (size_t)blocks[g].nstreams; }
+  for (size_t g = 0; g < blocks.size(); g++) {
+    if (blocks[g].nstreams <= 0 || (chunk_group && chunk_group[(size_t)blocks[g].chunk] != group)) continue;
+    mine[g % (size_t)nq].push_back((uint32_t)g); nstr_all += (size_t)blocks[g].nstreams;
+  }
   std::vector<int> order; int nheavy = 0, lastT = -1;
   for (int x = 0; x < 8; x++) {
     const std::vector<uint32_t>& B = mine[x];

@@ -1,0 +1,87 @@
+"""tensors.py — a list of device tensors of mixed dtypes in ONE packed container, written by ONE call (include/blosc_gpu_params.h).
+
+A state dict, a table's columns, a cache line of activations: float32, bfloat16, int8 and int64 side by side.  Every tensor becomes one
+c-blosc chunk whose typesize is the tensor's element size, with the codec, filter and clevel of the call or of its own; the chunks lie
+back to back in one device buffer with an offset table (include/blosc_gpu_packed.h), in the caller's order.  `unpack_tensors` is the
+reverse through blosc_gpu_decompress_packed, which reads chunks of any format, typesize and filter in one call anyway.
+
+Like blpk.py's device functions this module only drives the library: `lib` is the ctypes handle (load() of the package), memory comes
+from a `mem` with blpk.TorchMem's alloc().  There is no CPU implementation: without the library and a GPU the calls fail.
+"""
+import ctypes as C
+import importlib.util
+import os
+import sys
+
+MAX_CHUNK = 2 ** 31 - 1 - 16      # BLOSC_MAX_BUFFERSIZE: one tensor is one chunk
+
+
+def _sibling(name, file):
+    """the package's loader / blpk.py, whether this file was imported as part of the package or loaded by its path"""
+    if __package__:
+        return importlib.import_module("." + name if name else __package__, __package__) if name else sys.modules[__package__]
+    key = "_c_blosc_amd_" + (name or "pkg")
+    if key not in sys.modules:
+        spec = importlib.util.spec_from_file_location(key, os.path.join(os.path.dirname(os.path.abspath(__file__)), file))
+        mod = importlib.util.module_from_spec(spec)
+        sys.modules[key] = mod
+        spec.loader.exec_module(mod)
+    return sys.modules[key]
+
+
+def pack_tensors(lib, tensors, cname=b"lz4", clevel=5, shuffle=1, align=256, overrides=None, mem=None, stream=None):
+    """Compress the device tensors `tensors` into one container with one call of blosc_gpu_compress_packed_params.
+    Tensor i is chunk i: typesize = its element_size(); codec, clevel and filter are the call's unless overrides[i] (overrides: a dict
+    index -> dict with any of cname / clevel / shuffle / blocksize / splitmode) says otherwise.
+    Returns (container, offsets, meta): a uint8 device tensor of offsets[-1] bytes, the offset table [n + 1] (multiples of `align`), and
+    [(dtype, shape)] for unpack_tensors."""
+    pkg = _sibling("", "__init__.py")
+    mem = mem if mem is not None else _sibling("blpk", "blpk.py").TorchMem()
+    pkg.declare_packed(lib)
+    pkg.declare_params(lib)
+    n = len(tensors)
+    if n == 0:
+        return mem.alloc(0)[1][:0], [0], []
+    flat = [t.contiguous() for t in tensors]      # (kept alive until the call has returned)
+    sizes = [t.numel() * t.element_size() for t in flat]
+    if max(sizes) > MAX_CHUNK:
+        raise ValueError("a tensor above 2 GiB - 17 bytes does not fit one chunk: split it")
+    rows = []
+    for k, t in enumerate(flat):
+        kw = dict(cname=cname, clevel=clevel, shuffle=shuffle)
+        kw.update((overrides or {}).get(k, {}))
+        rows.append(pkg.cparams(t.element_size(), **kw))
+    b = pkg.PackedBatch(n, lib=lib)
+    cap = b.bound(sizes, align)
+    if cap == 0 and any(sizes):
+        raise ValueError("align must be a power of two up to 4096")
+    dest, keep = mem.alloc(cap)
+    if b.compress_params([t.data_ptr() if s else 0 for t, s in zip(flat, sizes)], sizes, rows, dest, cap, align, stream) != 0:
+        raise RuntimeError("blosc_gpu_compress_packed_params failed")
+    bad = [(k, r) for k, r in enumerate(b.results()) if r <= 0]
+    if bad:
+        raise RuntimeError(f"tensors that did not compress (index, code): {bad}")
+    off = b.offsets()
+    return keep[:off[-1]], off, [(t.dtype, tuple(t.shape)) for t in tensors]
+
+
+def unpack_tensors(lib, container, offsets, meta, mem=None, stream=None):
+    """The tensors of a container of pack_tensors, bit for bit, through one blosc_gpu_decompress_packed."""
+    import torch
+    pkg = _sibling("", "__init__.py")
+    mem = mem if mem is not None else _sibling("blpk", "blpk.py").TorchMem()
+    pkg.declare_packed(lib)
+    n = len(meta)
+    if n == 0:
+        return []
+    want = [int(torch.empty(0, dtype=dt).element_size()) * int(torch.Size(shape).numel()) for dt, shape in meta]
+    total = sum(want)
+    dest, keep = mem.alloc(total)
+    b = pkg.PackedBatch(n, lib=lib)
+    if b.decompress(container.data_ptr(), int(container.numel()), list(offsets), dest, total, stream) != 0:
+        raise RuntimeError("blosc_gpu_decompress_packed failed")
+    if b.results() != want:
+        raise RuntimeError(f"the container does not hold these tensors: decoded sizes {b.results()}, expected {want}")
+    at = b.offsets()
+    # a slice of the byte buffer begins wherever the tensors in front of it end: each tensor gets storage of its own, aligned for its dtype
+    return [keep[at[k]:at[k + 1]].clone().view(dt).reshape(shape) for k, (dt, shape) in enumerate(meta)]

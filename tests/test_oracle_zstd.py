@@ -31,6 +31,19 @@ def test_committed_reference_chunks(oracle):
         assert r == n and np.array_equal(out, DATASETS[dname](n)), meta[k]
 
 
+def test_reference_written_feature_frames(oracle):
+    """tests/golden/ref_zstd_features.npz: frames the reference's encoder wrote through its advanced API, every optional feature of the
+    format in several of them (window descriptor, no content size, raw / RLE blocks, RLE / single-stream / treeless literals, repeat
+    tables, 3-byte sequence counts: tests/test_zstd_features_cpu.py has the census) - what ZSTD_compress() at blosc's settings never writes"""
+    import ctypes as C
+    from zstd_feature_checks import fixture
+    oracle.orc_zstd_decompress.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    for e in fixture():
+        out = np.full(e.n + 64, 0xA5, np.uint8)
+        assert oracle.orc_zstd_decompress(ptr(e.frame), e.frame.size, ptr(out), e.n) == e.n, (e, sorted(e.classes))
+        assert np.array_equal(out[:e.n], e.plain) and np.all(out[e.n:] == 0xA5), e
+
+
 def test_truncated_and_corrupt_frames_fail_cleanly(oracle):
     z = golden_npz("ref_zstd_chunks.npz")
     chunk = z["c0"]; n = int(z["meta"][0].split(",")[1])

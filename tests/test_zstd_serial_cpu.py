@@ -58,6 +58,17 @@ def test_serial_primitives_decode_every_frame(zs, oracle):
     assert n >= 60
 
 
+def test_serial_primitives_decode_the_feature_frames(zs):
+    """tests/golden/ref_zstd_features.npz (every optional feature of the format in several reference-written frames) against the recorded
+    plain bytes, exact-size buffers on both sides"""
+    from zstd_feature_checks import fixture
+    for e in fixture():
+        src = np.empty(e.frame.size, np.uint8); src[:] = e.frame
+        out = np.zeros(e.n, np.uint8)
+        assert zs.zs_decompress(ptr(src), src.size, ptr(out), e.n) == e.n, (e, sorted(e.classes))
+        assert np.array_equal(out, e.plain), e
+
+
 def test_serial_primitives_survive_corruption(zs, oracle):
     """bit flips and truncations: same verdict as the oracle whenever the oracle accepts, never a crash"""
     oracle.orc_zstd_decompress.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]

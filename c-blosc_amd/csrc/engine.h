@@ -51,6 +51,8 @@ int engine_decompress_batch(int n, const Job* jobs, int* results, bool device_pt
 // the parsed 16-byte headers of n device-resident chunks (one gather kernel, one synchronisation)
 struct Header;
 int engine_chunk_headers(int n, const void* const* src, Header* out, hipStream_t stream);
+// blosc_getitem: engine_getitem_batch's pipeline for one range of one chunk, either pointer host or device memory (a host source is staged,
+// a host dest is written only when the result is positive), with the reference's messages on stderr for a range out of bounds
 int engine_getitem(const void* src, int start, int nitems, void* dest, bool src_on_device, bool dst_on_device,
                    hipStream_t stream);
 // Many item ranges of many device-resident chunks in one call (include/blosc_gpu_getitem.h).  chunks[i]: src and srcsize (0 = trust the

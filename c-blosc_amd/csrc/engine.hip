@@ -864,19 +864,22 @@ static int fetch_headers(EngineState& st, int n, const Job* jobs, bool device_pt
     for (int i = 0; i < n; i++) hdrs[(size_t)i] = parse_header((const uint8_t*)jobs[i].src);
     return 0;
   }
+  // device room: the first 16 bytes of the arena alone (carved first: a fixed offset), zeroed for the entries below.  The pointer table and the
+  // headers live in the pinned arena only
+  if (st.dev.ensure(16)) return -1;
   Carver cv;
   const size_t o_ptrs = cv.take(sizeof(void*) * (size_t)n);
   const size_t o_hdr = cv.take(16 * (size_t)n);
-  if (st.dev.ensure(cv.off)) return -1;
   if (st.pin.ensure(cv.off)) return -1;
   const void** pp = (const void**)(st.pin.base + o_ptrs);
-  // an entry whose caller-stated size cannot hold a header is never dereferenced: it reads the (zeroed) slot 0 of
-  // the header area instead and is rejected by classify_for_decompress (cbytes 0 > ... version 0)
+  // an entry whose caller-stated size cannot hold a header is never dereferenced: it reads those 16 zeroed bytes
+  // instead and is rejected by classify_for_decompress (cbytes 0 > ... version 0)
   bool any_short = false;
-  for (int i = 0; i < n; i++) { const bool sh = jobs[i].srcsize && jobs[i].srcsize < (size_t)kMaxOverhead; any_short |= sh; pp[i] = sh ? (const void*)(st.dev.base + o_hdr) : jobs[i].src; }
-  if (any_short) HIP_TRY(hipMemsetAsync(st.dev.base + o_hdr, 0, 16, stream));
-  // the kernel reads the pointer table from, and writes the headers to, the pinned (device-mapped) table memory itself: one device operation in
-  // front of the synchronisation instead of three (late in round 6; the call's host side is time the device stands idle)
+  for (int i = 0; i < n; i++) { const bool sh = jobs[i].srcsize && jobs[i].srcsize < (size_t)kMaxOverhead; any_short |= sh; pp[i] = sh ? (const void*)st.dev.base : jobs[i].src; }
+  if (any_short) HIP_TRY(hipMemsetAsync(st.dev.base, 0, 16, stream));
+  // the kernel reads the pointer table from, and writes the headers to, the pinned arena directly, through its host address: one device operation
+  // in front of the synchronisation instead of three (late in round 6; the call's host side is time the device stands idle).  This relies on
+  // hipHostMalloc memory being mapped on every device, at the address the host uses
   hipLaunchKernelGGL(k_gather_headers, grid1((size_t)n * 16, 256), dim3(256), 0, stream,
                      (const uint8_t* const*)(st.pin.base + o_ptrs), st.pin.base + o_hdr, n);
   HIP_TRY(hipGetLastError());
@@ -917,7 +920,7 @@ static void add_decode_chunk(const Header& h, int fmt, int chunk_index, int32_t 
 }
 
 // Everything launch_decode hands to the kernels.  The device pointers into the call's workspace are set by decode_workspace(); the block
-// table and the queues (d_blocks, d_q*, d_zq*: the table cache's, or getitem's own) and the any_* / tiles_* of filter_tiles() by the caller.
+// table and the queues (d_blocks, d_q*, d_zq*: the table cache's, or getitem's in its table area) and the any_* / tiles_* of filter_tiles() by the caller.
 struct DecodeLaunch {
   ChunkDesc* d_chunks; BlockDesc* d_blocks; StreamDesc* d_streams; int32_t* d_status; uint32_t* d_ticket; uint32_t* d_blkdone;
   size_t clear_bytes;                            // d_status .. the end of d_cost: cleared by clear_decode_counters() before every launch
@@ -935,17 +938,16 @@ struct DecodeLaunch {
   size_t nstr_queued;                              // streams left to k_decode_streams
 };
 
-// The decode workspace in st.dev, for the batched call and for getitem.
+// The decode workspace in st.dev, for decompress and for getitem.
 struct DecodeShape {
   int nchunks; size_t nblk, nstr;
   size_t filt_bytes;        // filter scratch of the shuffled / bitshuffled chunks
   size_t zlit_bytes;        // literal scratch of the Zstd chunks (and as much again for the sequence triples of the two-phase path)
   bool any_zstd, two_phase; // two_phase:           // Zstd frames may go through k_zstd_entropy / k_zstd_exec (zstd2_mode()); false: all of them through k_zstd_streams
-  size_t out_bytes;         // getitem only: the decoded blocks land in the workspace,
-  bool own_tables;          //               and so do its block table and queues (it bypasses the table cache)
-  size_t extra_bytes = 0;   // getitem batch only: one more area, for all of its tables (it uploads them as one piece)
+  size_t out_bytes = 0;     // getitem only: the decoded blocks land in the workspace,
+  size_t extra_bytes = 0;   //               and so do all of its tables, in one more area (it uploads them as one piece, past the table cache)
 };
-struct DecodeAreas { uint8_t *filt, *zlit, *out, *blocks, *queues, *extra; };
+struct DecodeAreas { uint8_t *filt, *zlit, *out, *extra; };
 static int decode_workspace(EngineState& st, const DecodeShape& s, DecodeLaunch& L, DecodeAreas& A) {
   const size_t n = (size_t)s.nchunks, nblk1 = s.nblk ? s.nblk : 1, nstr1 = s.nstr ? s.nstr : 1;
   const int zstd2 = (s.any_zstd && s.two_phase) ? zstd2_mode() : 0;
@@ -968,12 +970,10 @@ static int decode_workspace(EngineState& st, const DecodeShape& s, DecodeLaunch&
   const size_t o_zgscr = cv.take(zstd2 == 2 ? sizeof(ZgLds) * nstr1 : 64);
   const size_t o_zctab = cv.take(use_zctab ? sizeof(ZcTab) * nstr1 : 64);
   const size_t o_out = cv.take(s.out_bytes ? s.out_bytes + 256 : 0);
-  const size_t o_blocks = cv.take(s.own_tables ? sizeof(BlockDesc) * nblk1 : 0);
-  const size_t o_queues = cv.take(s.own_tables ? sizeof(int32_t) * (9 + nstr1) : 0);
   const size_t o_extra = cv.take(s.extra_bytes);
   if (st.dev.ensure(cv.off)) return -1;
   uint8_t* D = st.dev.base;
-  A = DecodeAreas{D + o_filt, D + o_zlit, D + o_out, D + o_blocks, D + o_queues, D + o_extra};
+  A = DecodeAreas{D + o_filt, D + o_zlit, D + o_out, D + o_extra};
   L.d_chunks = (ChunkDesc*)(D + o_chunks); L.d_streams = (StreamDesc*)(D + o_streams);
   L.d_status = (int32_t*)(D + o_status);
   L.d_ticket = (uint32_t*)(D + o_status + ticket_offset(n));
@@ -990,6 +990,20 @@ static int decode_workspace(EngineState& st, const DecodeShape& s, DecodeLaunch&
 static int clear_decode_counters(const DecodeLaunch& L, hipStream_t stream) {
   HIP_TRY(hipMemsetAsync(L.d_status, 0, L.clear_bytes, stream));
   if (L.any_zstd || L.any_zlib) HIP_TRY(hipMemsetAsync(L.d_zticket, 0, 64, stream));
+  return 0;
+}
+
+// The other end of a launch: the chunks' status words and the feedback words into pinned memory (read_back_decode, behind launch_decode) and,
+// once the stream has been synchronised, decode_feedback: every queued task was taken, and a launch of 4096 streams or more - fewer say
+// little - leaves its plane costs for the queue order of the calls that follow.
+static int read_back_decode(const DecodeLaunch& L, void* status, void* cost, hipStream_t stream) {
+  HIP_TRY(hipMemcpyAsync(status, L.d_status, sizeof(int32_t) * (size_t)L.nchunks, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(cost, L.d_cost, sizeof(uint32_t) * kCostWords, hipMemcpyDeviceToHost, stream));
+  return 0;
+}
+static int decode_feedback(EngineState& st, const DecodeLaunch& L, const void* cost, const char* what) {
+  if (check_done((const uint32_t*)cost, L.nstr_queued, L.any_zstd ? L.nstr : 0, what, L.nstr_zlib)) return -1;
+  if (L.nstr >= 4096) { memcpy(st.dec_cost, cost, sizeof st.dec_cost); st.dec_cost_valid = true; }
   return 0;
 }
 
@@ -1157,7 +1171,7 @@ int engine_decompress_batch(int n, const Job* jobs, int* results, bool device_pt
   const size_t nblk = blocks.size();
   // ---- workspace ----
   DecodeAreas A;
-  if (decode_workspace(st, DecodeShape{n, nblk, nstr, filt_bytes, zlit_bytes, L.any_zstd, /*two_phase*/ true, /*out_bytes*/ 0, /*own_tables*/ false}, L, A)) return -1;
+  if (decode_workspace(st, DecodeShape{n, nblk, nstr, filt_bytes, zlit_bytes, L.any_zstd, /*two_phase*/ true}, L, A)) return -1;
   // ---- stage the inputs of a host-pointer call, point every chunk at its scratch ----
   if (io.reserve(st.io)) return -1;
   {
@@ -1194,17 +1208,14 @@ int engine_decompress_batch(int n, const Job* jobs, int* results, bool device_pt
   L.nstr_queued = nstr - nstr_z;
   ht.mark(2);     // tables, queues, uploads
   // ---- launch ----
-  if (launch_decode(st, L, stream)) return -1;
-  HIP_TRY(hipMemcpyAsync(P + p_status, L.d_status, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(P + p_cost, L.d_cost, sizeof(uint32_t) * kCostWords, hipMemcpyDeviceToHost, stream));
+  if (launch_decode(st, L, stream) || read_back_decode(L, P + p_status, P + p_cost, stream)) return -1;
   ht.mark(3);     // kernel launches
   // ---- collect ----
   HIP_TRY(hipStreamSynchronize(stream));
   ht.mark(4);     // waiting for the device
   prof_collect(st);
-  if (nblk && check_done((const uint32_t*)(P + p_cost), nstr - nstr_z, L.any_zstd ? nstr : 0, "decompress", nstr_zlib)) return -1;
+  if (nblk && decode_feedback(st, L, P + p_cost, "decompress")) return -1;
   tc.commit(key);
-  if (nstr >= 4096) { memcpy(st.dec_cost, P + p_cost, sizeof st.dec_cost); st.dec_cost_valid = true; }
   if (debug_cost_enabled()) {
     fprintf(stderr, "[blosc_amd] decode plane costs:");
     for (int k = 0; k < 16; k++) fprintf(stderr, " %u", st.dec_cost[k]);
@@ -1236,100 +1247,16 @@ static int classify_for_getitem(const Header& h, int* res, int* fmt) {
   return 1;
 }
 
-int engine_getitem(const void* src, int start, int nitems, void* dest, bool src_dev, bool dst_dev, hipStream_t stream) {
-  CtxGuard ctx;
-  EngineState& st = *ctx.st;
-  if (ensure_device(st) || call_stream(st, !src_dev && !dst_dev, &stream)) return -1;
-  Job job{src, nullptr, 0, 0};
-  std::vector<Header> hdrs;
-  if (fetch_headers(st, 1, &job, src_dev, stream, hdrs)) return -1;
-  const Header h = hdrs[0];
-  const int stop = start + nitems;
-  int fmt = 0, bad = -1;
-  if (!classify_for_getitem(h, &bad, &fmt)) return bad;
-  const int32_t T = h.typesize, bs = h.blocksize;
-  if (start < 0 || (int64_t)start * T > h.nbytes) { fprintf(stderr, "`start` out of bounds"); return -1; }
-  if (stop < 0 || (int64_t)stop * T > h.nbytes) { fprintf(stderr, "`start`+`nitems` out of bounds"); return -1; }
-  const int64_t lo = (int64_t)start * T, hi = (int64_t)stop * T;
-  if (hi <= lo) return 0;
-  const size_t want = (size_t)(hi - lo);
-  const hipMemcpyKind out_kind = dst_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-
-  const uint8_t* dsrc = (const uint8_t*)src;
-  if (!src_dev) {   // bring the chunk to the device
-    if (h.cbytes < kMaxOverhead) return -1;
-    if (st.io.ensure((size_t)h.cbytes + 256)) return -1;
-    HIP_TRY(hipMemcpyAsync(st.io.base, src, (size_t)h.cbytes, hipMemcpyHostToDevice, stream));
-    dsrc = st.io.base;
-  }
-  if (h.flags & kFlagMemcpyed) {
-    HIP_TRY(hipMemcpyAsync(dest, dsrc + kMaxOverhead + lo, want, out_kind, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return (int)want;
-  }
-  // ---- lay out blocks [j0, j1) ----
-  const int32_t j0 = (int32_t)(lo / bs), j1 = (int32_t)((hi + bs - 1) / bs);
-  ChunkDesc c;
-  std::vector<BlockDesc> blocks;
-  size_t nstr = 0;
-  add_decode_chunk(h, fmt, 0, j0, j1, c, blocks, nstr);
-  const size_t nblk = blocks.size();
-  const size_t span = (size_t)(j1 - j0) * (size_t)bs;
-  DecodeLaunch L{};
-  L.any_zstd = fmt == FMT_ZSTD; L.any_zlib = fmt == FMT_ZLIB;
-  filter_tiles(c, L, !st.single_queue);   // may set CH_FUSED_UNSHUF: before the upload
-  // ---- workspace (filter scratch: room for the padded plane layout of a fused chunk) ----
-  DecodeAreas A;
-  if (decode_workspace(st, DecodeShape{1, nblk, nstr, span, L.any_zstd ? span : 0, L.any_zstd, /*two_phase*/ false, /*out_bytes*/ span, /*own_tables*/ true}, L, A)) return -1;
-  c.src = dsrc;
-  // kernels address block j at base + j*blocksize: bias the bases so that block j0 lands at offset 0
-  c.dst = A.out - (size_t)j0 * bs;
-  c.stage = L.any_zstd ? A.zlit - (size_t)j0 * bs : nullptr;
-  c.filt = (c.mode & (CH_SHUFFLE | CH_BITSHUFFLE)) ? A.filt - (size_t)j0 * filt_block_stride(c) : nullptr;   // (the block stride depends on the mode filter_tiles chose)
-  // ---- tables: its own, next to the workspace - a handful of blocks is not worth a place in the table cache ----
-  std::vector<int32_t> queues;     // (one chunk, one format: the zlib kernel's queues when it is a zlib chunk, k_decode_streams' otherwise)
-  build_xcd_queues(blocks, nstr, st.dec_cost, st.dec_cost_valid, queues, st.single_queue ? 1 : 8, L.any_zlib ? (uint32_t)BLK_ZLIB : 0u);
-  Carver pc;
-  const size_t p_chunks = pc.take(sizeof(ChunkDesc));
-  const size_t p_blocks = pc.take(sizeof(BlockDesc) * nblk);
-  const size_t p_status = pc.take(sizeof(int32_t));
-  const size_t p_cost = pc.take(sizeof(uint32_t) * kCostWords);
-  const size_t p_queues = pc.take(sizeof(int32_t) * queues.size());
-  if (st.pin.ensure(pc.off)) return -1;
-  uint8_t* P = st.pin.base;
-  memcpy(P + p_queues, queues.data(), sizeof(int32_t) * queues.size()); memcpy(P + p_chunks, &c, sizeof c); memcpy(P + p_blocks, blocks.data(), sizeof(BlockDesc) * nblk);
-  HIP_TRY(hipMemcpyAsync(L.d_chunks, P + p_chunks, sizeof c, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(A.blocks, P + p_blocks, sizeof(BlockDesc) * nblk, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(A.queues, P + p_queues, sizeof(int32_t) * queues.size(), hipMemcpyHostToDevice, stream));
-  if (clear_decode_counters(L, stream)) return -1;      // (a handful of blocks: the plane costs are not fed back, only the task count is checked)
-  L.d_blocks = (BlockDesc*)A.blocks;
-  L.d_qoff = (const int32_t*)A.queues; L.d_qlist = L.d_qoff + 9;
-  L.d_zqoff = L.d_qoff; L.d_zqlist = L.d_qlist; L.nstr_zlib = L.any_zlib ? nstr : 0;
-  L.nstr_queued = (L.any_zstd || L.any_zlib) ? 0 : nstr;    // Zstd / zlib: their own kernels
-  // ---- launch, collect ----
-  if (launch_decode(st, L, stream)) return -1;
-  HIP_TRY(hipMemcpyAsync(P + p_status, L.d_status, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(P + p_cost, L.d_cost, sizeof(uint32_t) * kCostWords, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  prof_collect(st);
-  if (check_done((const uint32_t*)(P + p_cost), L.nstr_queued, L.any_zstd ? nstr : 0, "getitem", L.any_zlib ? nstr : 0)) return -1;
-  const int32_t stt = *(const int32_t*)(P + p_status);
-  if (stt < 0) return stt;                                                        // blosc.c:1689-1692: blosc_d's code is returned as is
-  HIP_TRY(hipMemcpyAsync(dest, A.out + (size_t)(lo - (int64_t)j0 * bs), want, out_kind, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  return (int)want;
-}
-
-// ---------------------------------------------------------------------------------------------
-// getitem, batched (include/blosc_gpu_getitem.h): many item ranges of many device-resident chunks in one call
-// ---------------------------------------------------------------------------------------------
-// engine_getitem costs a header fetch, a decode pipeline for a handful of blocks, two synchronisations and a copy PER RANGE.  Here:
-//   1. one header fetch for the distinct chunks the ranges name, then every range is validated on the host (engine_getitem's checks);
+// One pipeline serves every entry point: many item ranges of many device-resident chunks (include/blosc_gpu_getitem.h: getitem_ranges below),
+// and blosc_getitem / blosc_gpu_getitem as one range of one chunk (engine_getitem at the end).
+//   1. one header fetch for the distinct chunks the ranges name, then every range is validated on the host (blosc.c:1645-1653);
 //   2. per chunk the union of the blocks its valid ranges touch, cut into maximal runs of consecutive blocks.  A run decodes into one
-//      slot of the workspace (bases biased like engine_getitem's, so a range that crosses blocks reads one contiguous piece), and a
-//      block is decoded once however many ranges touch it.  Ranges of MEMCPYED chunks are served straight from src + 16;
+//      slot of the workspace (the kernels address block j at base + j * blocksize, so the bases are biased to put the run's first block at
+//      its slot: a range that crosses blocks reads one contiguous piece), and a block is decoded once however many ranges touch it.
+//      Ranges of MEMCPYED chunks are served straight from src + 16;
 //   3. one table upload and one launch_decode for all runs, formats mixed as in engine_decompress_batch;
-//   4. k_getitem_gather (k_decode.hip) writes every slice, after reading the verdict of the blocks the slice depends on;
+//   4. k_getitem_gather (k_decode.hip) writes every slice, after reading the verdict of the blocks the slice depends on: a range that fails
+//      writes nothing;
 //   5. status and cost words come back, one synchronisation.
 // Verdicts.  The decode kernels keep one status word per ChunkDesc, and blosc_getitem answers the code of the FIRST block (in block order) that
 // does not decode, whatever happens to blocks the range does not touch.  So every block of a run enters the tables as a ChunkDesc of its own
@@ -1407,7 +1334,7 @@ static int getitem_pass(EngineState& st, int pass, std::vector<RangeChunk>& uc, 
   }
   const uint32_t ntiles = tile_first[(size_t)nranges];
   if (!nblk && !ntiles) return 0;
-  // ---- queues, as engine_decompress_batch builds them (a few blocks each time: not worth a place in the table cache) ----
+  // ---- queues, as engine_decompress_batch builds them (a few blocks each time: the table cache stays the decompress path's alone) ----
   const int nq = st.single_queue ? 1 : 8;
   std::vector<int32_t> queues, zqueues;
   build_xcd_queues(blocks, nstr, st.dec_cost, st.dec_cost_valid, queues, nq);
@@ -1424,8 +1351,7 @@ static int getitem_pass(EngineState& st, int pass, std::vector<RangeChunk>& uc, 
   const size_t p_status = tv.take(sizeof(int32_t) * (n ? n : 1));      // (pinned only: what comes back)
   const size_t p_cost = tv.take(sizeof(uint32_t) * kCostWords);
   DecodeAreas A;
-  if (decode_workspace(st, DecodeShape{(int)n, nblk, nstr, any_filt ? span : 0, L.any_zstd ? span : 0, L.any_zstd, /*two_phase*/ false, /*out_bytes*/ span, /*own_tables*/ false,
-                                       table_bytes}, L, A)) return -1;
+  if (decode_workspace(st, DecodeShape{(int)n, nblk, nstr, any_filt ? span : 0, L.any_zstd ? span : 0, L.any_zstd, /*two_phase*/ false, /*out_bytes*/ span, table_bytes}, L, A)) return -1;
   if (st.pin.ensure(tv.off)) return -1;
   uint8_t* P = st.pin.base;
   // kernels address block j at base + j * blocksize: bias the bases so that block r.j0 lands at the run's slot
@@ -1466,9 +1392,7 @@ static int getitem_pass(EngineState& st, int pass, std::vector<RangeChunk>& uc, 
   L.nstr_queued = nstr - nstr_z;
   // ---- launch, collect ----
   if (nblk) {
-    if (clear_decode_counters(L, stream) || launch_decode(st, L, stream)) return -1;
-    HIP_TRY(hipMemcpyAsync(P + p_status, L.d_status, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(P + p_cost, L.d_cost, sizeof(uint32_t) * kCostWords, hipMemcpyDeviceToHost, stream));
+    if (clear_decode_counters(L, stream) || launch_decode(st, L, stream) || read_back_decode(L, P + p_status, P + p_cost, stream)) return -1;
   }
   if (ntiles) {
     ProfScope ps(st, stream, "k_getitem_gather");
@@ -1479,8 +1403,7 @@ static int getitem_pass(EngineState& st, int pass, std::vector<RangeChunk>& uc, 
   HIP_TRY(hipStreamSynchronize(stream));
   prof_collect(st);
   if (!nblk) return 0;
-  if (check_done((const uint32_t*)(P + p_cost), nstr - nstr_z, L.any_zstd ? nstr : 0, "getitem batch", nstr_zlib)) return -1;
-  if (nstr >= 4096) { memcpy(st.dec_cost, P + p_cost, sizeof st.dec_cost); st.dec_cost_valid = true; }      // (partial decodes of a few blocks say little)
+  if (decode_feedback(st, L, P + p_cost, "getitem")) return -1;
   const int32_t* stt = (const int32_t*)(P + p_status);
   for (int r = 0; r < nranges; r++) {
     const GatherRange& g = gr[(size_t)r];
@@ -1490,23 +1413,23 @@ static int getitem_pass(EngineState& st, int pass, std::vector<RangeChunk>& uc, 
   return 0;
 }
 
-int engine_getitem_batch(int nchunks, const Job* chunks, int nranges, const ItemRange* ranges, int* results, hipStream_t stream,
-                         const PackedBuffer* packed) {
-  if (packed) packed->offsets[0] = 0;
-  if (nranges <= 0) return 0;
-  CtxGuard ctx; EngineState& st = *ctx.st;
-  if (ensure_device(st)) return -1;
+// The call, in a context its caller holds.  chunks[].src is device memory; `given`: the headers of chunks[] where the caller has fetched them
+// (nchunks entries), nullptr: fetched here.  `say`: the reference's two messages on stderr for ranges out of bounds (blosc_getitem's; the batched
+// calls are silent).  results[r] is written for every range; -1: the call itself failed.
+static int getitem_ranges(EngineState& st, int nchunks, const Job* chunks, const Header* given, int nranges, const ItemRange* ranges, int* results,
+                          hipStream_t stream, const PackedBuffer* packed, bool say) {
   // ---- the headers of the distinct chunks the ranges name: one fetch ----
   std::vector<int> slot_of((size_t)(nchunks > 0 ? nchunks : 0), -1);
   std::vector<Job> jobs;
+  std::vector<Header> hdrs;
   for (int r = 0; r < nranges; r++) {
     const int ci = ranges[r].chunk;
     if (ci < 0 || ci >= nchunks || slot_of[(size_t)ci] >= 0) continue;
     slot_of[(size_t)ci] = (int)jobs.size();
     jobs.push_back(chunks[ci]);
+    if (given) hdrs.push_back(given[ci]);
   }
-  std::vector<Header> hdrs;
-  if (!jobs.empty() && fetch_headers(st, (int)jobs.size(), jobs.data(), true, stream, hdrs)) return -1;
+  if (!given && !jobs.empty() && fetch_headers(st, (int)jobs.size(), jobs.data(), true, stream, hdrs)) return -1;
   std::vector<RangeChunk> uc(jobs.size());
   for (size_t k = 0; k < uc.size(); k++) {
     RangeChunk& u = uc[k];
@@ -1517,7 +1440,7 @@ int engine_getitem_batch(int nchunks, const Job* chunks, int nranges, const Item
     else if (srcsize && (h.cbytes < 0 || (size_t)h.cbytes > srcsize)) u.verdict = -1;
     else { u.usable = true; u.memcpyed = (h.flags & kFlagMemcpyed) != 0; }
   }
-  // ---- the ranges: engine_getitem's checks; packed: the slices back to back ----
+  // ---- the ranges: blosc_getitem's checks; packed: the slices back to back ----
   std::vector<PlacedRange> pr((size_t)nranges);
   size_t off = 0;
   for (int r = 0; r < nranges; r++) {
@@ -1531,7 +1454,8 @@ int engine_getitem_batch(int nchunks, const Job* chunks, int nranges, const Item
     const Header& h = hdrs[(size_t)slot];
     const int32_t T = h.typesize, bs = h.blocksize;
     const int start = ranges[r].start, stop = (int)((unsigned)start + (unsigned)ranges[r].nitems);
-    if (start < 0 || (int64_t)start * T > h.nbytes || stop < 0 || (int64_t)stop * T > h.nbytes) continue;      // blosc.c:1645-1653
+    if (start < 0 || (int64_t)start * T > h.nbytes) { if (say) fprintf(stderr, "`start` out of bounds"); continue; }      // blosc.c:1645-1653
+    if (stop < 0 || (int64_t)stop * T > h.nbytes) { if (say) fprintf(stderr, "`start`+`nitems` out of bounds"); continue; }
     const int64_t lo = (int64_t)start * T, hi = (int64_t)stop * T;
     if (hi <= lo) { results[r] = 0; continue; }
     PlacedRange& p = pr[(size_t)r];
@@ -1558,6 +1482,43 @@ int engine_getitem_batch(int nchunks, const Job* chunks, int nranges, const Item
   for (int p = 0; p <= pass; p++)
     if (getitem_pass(st, p, uc, hdrs, jobs, nranges, pr, results, stream)) return -1;
   return 0;
+}
+
+int engine_getitem_batch(int nchunks, const Job* chunks, int nranges, const ItemRange* ranges, int* results, hipStream_t stream,
+                         const PackedBuffer* packed) {
+  if (packed) packed->offsets[0] = 0;
+  if (nranges <= 0) return 0;
+  CtxGuard ctx; EngineState& st = *ctx.st;
+  if (ensure_device(st)) return -1;
+  return getitem_ranges(st, nchunks, chunks, nullptr, nranges, ranges, results, stream, packed, /*say*/ false);
+}
+
+// blosc_getitem / blosc_gpu_getitem: one chunk, one range, one result, each pointer host or device memory.  What only this call has: a stream
+// of the context's own for host buffers; a host source staged into st.io, its header parsed where it lies and its cbytes trusted as
+// blosc_getitem trusts it; a host destination served from a slot behind the source and copied out once the result is known to be
+// positive - a call that fails writes nothing to dest.
+int engine_getitem(const void* src, int start, int nitems, void* dest, bool src_dev, bool dst_dev, hipStream_t stream) {
+  CtxGuard ctx; EngineState& st = *ctx.st;
+  if (ensure_device(st) || call_stream(st, !src_dev && !dst_dev, &stream)) return -1;
+  Job chunk{src, nullptr, 0, 0};
+  ItemRange range{0, start, nitems, dest};
+  std::vector<Header> hdrs;
+  if (fetch_headers(st, 1, &chunk, src_dev, stream, hdrs)) return -1;
+  const Header& h = hdrs[0];
+  const bool host = !src_dev || !dst_dev;
+  int verdict = -1, fmt = 0;
+  if (host && nitems > 0 && classify_for_getitem(h, &verdict, &fmt)) {      // (any other call decodes nothing and touches neither pointer)
+    const size_t in = src_dev ? 0 : align_up((size_t)h.cbytes, 256);
+    const size_t out = dst_dev ? 0 : (size_t)std::min<int64_t>((int64_t)nitems * h.typesize, h.nbytes);
+    if (st.io.ensure(in + out + 256)) return -1;
+    if (!src_dev) { HIP_TRY(hipMemcpyAsync(st.io.base, src, (size_t)h.cbytes, hipMemcpyHostToDevice, stream)); chunk.src = st.io.base; }
+    if (!dst_dev) range.dst = st.io.base + in;
+  }
+  int result = -1;
+  if (getitem_ranges(st, 1, &chunk, &h, 1, &range, &result, stream, nullptr, /*say*/ true)) return -1;
+  if (!dst_dev && result > 0) HIP_TRY(hipMemcpyAsync(dest, range.dst, (size_t)result, hipMemcpyDeviceToHost, stream));
+  if (host) HIP_TRY(hipStreamSynchronize(stream));      // the staged source has been read, dest is written
+  return result;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1,10 +1,10 @@
 """What tests/test_gpu_getitem_ranges.py (device) and tests/test_emu_getitem_ranges.py (wavefront emulator) both assert about the calls of
-include/blosc_gpu_getitem.h.  Expected results and bytes come from the oracle's orc_getitem on the same chunk, range by range, never from
+include/blosc_gpu_getitem.h (check_batch) and about the single calls blosc_getitem / blosc_gpu_getitem that the same pipeline serves (check_single).  Expected results and bytes come from the oracle's orc_getitem on the same chunk, range by range, never from
 the library under test.  `mem` is how a test reaches "device" memory: mem.put(array) -> (keep-alive handle, address), mem.get(handle) ->
 host array, mem.filled(n, value) -> (handle, address)."""
 import numpy as np
 
-from helpers import header, ptr
+from helpers import header, orc_compress, ptr, ref_compress
 
 SENTINEL = 0xA5
 SMALL = 40 * 1024 + 24          # with blocksize 8192: five blocks and a leftover where the block is not split (typesize 17) - a split block
@@ -125,6 +125,79 @@ def check_batch(pkgmod, lib, mem, oracle, chunks, ranges, what=""):
         k = max(j for j, a in enumerate(at) if a <= bad) if bad >= at[0] else -1
         raise AssertionError((what, "byte", bad, "range", k, ranges[k] if k >= 0 else None, "slot at", at[k] if k >= 0 else None, int((buf != exp).sum())))
     return got
+
+
+def expected_single(oracle, ref, chunk, start, nitems):
+    """(result, bytes) of one blosc_getitem: the reference's where it is built, the oracle's otherwise.  The chunk lies in front of 256 zero
+    bytes: a damaged bstarts entry sends the reader behind the chunk"""
+    T = max(header(chunk)["typesize"], 1)
+    padded = np.concatenate([np.asarray(chunk, np.uint8), np.zeros(256, np.uint8)])
+    buf = np.full(max(nitems, 0) * T + 16, SENTINEL, np.uint8)
+    fn = ref.blosc_getitem if ref is not None else oracle.orc_getitem
+    r = fn(ptr(padded), start, nitems, ptr(buf))
+    assert r < 0 or np.all(buf[r:] == SENTINEL), "the checker wrote more than it returned"
+    return r, buf[:max(r, 0)].copy()
+
+
+def check_single(call, src_mem, dst_mem, oracle, ref, chunk, ranges, what=""):
+    """One `call(src address, start, nitems, dest address)` - blosc_getitem or blosc_gpu_getitem - per (start, nitems) of `ranges` on one
+    chunk held in src_mem: every result and every byte those of expected_single.  Every destination sits at offset 1 of a buffer of sentinels
+    in dst_mem, and every byte outside [1, 1 + max(result, 0)) is still the sentinel afterwards: a call that fails writes nothing."""
+    T = max(header(chunk)["typesize"], 1)
+    keep, src = src_mem.put(chunk)
+    got = []
+    for s, k in ranges:
+        r, data = expected_single(oracle, ref, chunk, s, k)
+        total = 1 + max(k, 0) * T + 33
+        out, base = dst_mem.filled(total, SENTINEL)
+        res = call(src, s, k, base + 1)
+        buf = dst_mem.get(out)[:total]
+        print(what, (s, k), "->", res, "want", r)
+        assert res == r, (what, (s, k), res, r)
+        exp = np.full(total, SENTINEL, np.uint8)
+        exp[1:1 + max(r, 0)] = data
+        assert np.array_equal(buf, exp), (what, (s, k), "byte", int(np.flatnonzero(buf != exp)[0]), int((buf != exp).sum()))
+        got.append(res)
+    del keep
+    return got
+
+
+def single_grid_chunks(oracle, ref, lib_compress):
+    """the chunks of the single-call grid as (name, chunk): Zstd and zlib written by the reference where it is built and by the library under
+    test (lib_compress(data, typesize, shuffle, cname, blocksize)) otherwise, LZ4 and BloscLZ by the oracle; the three specials"""
+    small = plain(SMALL)
+    out = []
+    for T, shuffle, cname in ((17, 1, "lz4"), (17, 2, "blosclz"), (4, 2, "zstd"), (8, 1, "zlib"), (17, 0, "zstd")):
+        if cname in ("lz4", "blosclz"): c = orc_compress(oracle, small, T, 5, shuffle, cname, blocksize=BLOCKSIZE)[1]
+        elif ref is not None: c = ref_compress(ref, small, T, 5, shuffle, cname.encode(), blocksize=BLOCKSIZE)[1]
+        else: c = lib_compress(small, T, shuffle, cname, BLOCKSIZE)
+        out.append((f"{cname} T{T} shuffle {shuffle}", c))
+    out.append(("memcpyed", orc_compress(oracle, np.random.default_rng(3).integers(0, 256, 9000, dtype=np.uint8), 4, 5, 1, "lz4")[1]))
+    out.append(("100 bytes", orc_compress(oracle, plain(100), 4, 5, 1, "lz4")[1]))
+    out.append(("empty", orc_compress(oracle, plain(0), 4, 5, 1, "lz4")[1]))
+    assert header(out[-3][1])["flags"] & 2 and header(out[-1][1])["nbytes"] == 0
+    assert all(-(-header(c)["nbytes"] // header(c)["blocksize"]) >= 5 for _, c in out[:5] if header(c)["typesize"] == 17)
+    return out
+
+
+def damaged_single_chunks(oracle, ref, lib_compress):
+    """(name, damaged chunk, its three ranges) for pick_damage on a SMALL typesize-17 shuffle-1 chunk of each of the four codecs"""
+    out = []
+    for cname in ("lz4", "blosclz", "zstd", "zlib"):
+        if cname in ("lz4", "blosclz"): c = orc_compress(oracle, plain(SMALL), 17, 5, 1, cname, blocksize=BLOCKSIZE)[1]
+        elif ref is not None: c = ref_compress(ref, plain(SMALL), 17, 5, 1, cname.encode(), blocksize=BLOCKSIZE)[1]
+        else: c = lib_compress(plain(SMALL), 17, 1, cname, BLOCKSIZE)
+        found, rngs = pick_damage(oracle, c)
+        out += [(f"{cname}, {kind}", bad, rngs) for kind, bad in found]
+    return out
+
+
+def check_damage(call, src_mem, dst_mem, oracle, ref, damaged, what=""):
+    """the range inside the damaged block and the one crossing into it answer the checker's negative code and write nothing, the range in the
+    block before it answers its bytes"""
+    for name, bad, rngs in damaged:
+        got = check_single(call, src_mem, dst_mem, oracle, ref, bad, rngs, (what, name))
+        assert got[0] < 0 and got[1] == 7 * 17 and got[2] < 0, (what, name, got)
 
 
 def pick_damage(oracle, chunk):

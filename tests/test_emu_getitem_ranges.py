@@ -1,13 +1,15 @@
-"""CPU: blosc_gpu_getitem_batch / blosc_gpu_getitem_packed (include/blosc_gpu_getitem.h) on the emulated library - the host engine's
-range validation, runs, tables and passes, the decode kernels' per-block status words and k_getitem_gather.  The checks are those of
+"""CPU: blosc_gpu_getitem_batch / blosc_gpu_getitem_packed (include/blosc_gpu_getitem.h) and the single calls blosc_getitem / blosc_gpu_getitem
+on the emulated library - the host engine's range validation, runs, tables and passes, the decode kernels' per-block status words and k_getitem_gather.  The checks are those of
 tests/test_gpu_getitem_ranges.py (tests/getitem_ranges_checks.py), the chunk grid thinned to what the emulator decodes in seconds."""
+import ctypes as C
 import importlib.util
 import os
 
 import numpy as np
 import pytest
 
-from getitem_ranges_checks import (BIG, BLOCKSIZE, SENTINEL, SMALL, NumpyMem, check_batch, chunk_ranges, expected, pick_damage, plain, prefix)
+from getitem_ranges_checks import (BIG, BLOCKSIZE, SENTINEL, SMALL, NumpyMem, check_batch, check_damage, check_single, chunk_ranges, damaged_single_chunks,
+                                   expected, pick_damage, plain, prefix, single_grid_chunks)
 from helpers import header, orc_compress, ptr, ref_compress
 from test_emu_library import emulib  # noqa: F401  (the fixture)
 
@@ -27,6 +29,7 @@ def elib(emulib, pkgmod):
     assert hasattr(emulib, "blosc_gpu_getitem_batch"), "the library has no batched getitem"
     pkgmod.declare_getitem(emulib)
     pkgmod.declare_packed(emulib)
+    emulib.blosc_gpu_getitem.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     return emulib
 
 
@@ -141,3 +144,40 @@ def test_packed(elib, pkgmod, oracle):
     # tables that are unusable as a whole
     assert b.packed(cont.ctypes.data, cont.size - 1, offs, None, 0) < 0
     assert b.packed(cont.ctypes.data, cont.size, [0, 5, 4, offs[-1]], None, 0) < 0
+
+
+# ---- the single calls: one range of one chunk through the same pipeline (the emulator's "device" memory is the host's, so each entry point runs as it is) ----
+def single_calls(elib):
+    return [("blosc_getitem", elib.blosc_getitem), ("blosc_gpu_getitem", lambda src, s, k, dst: elib.blosc_gpu_getitem(src, s, k, dst, None))]
+
+
+@pytest.fixture(scope="module")
+def single_chunks(elib, oracle, ref):
+    return single_grid_chunks(oracle, ref, lambda d, T, shuffle, cname, bs: lib_compress(elib, d, T, shuffle, cname.encode(), bs))
+
+
+@pytest.mark.parametrize("entry", [0, 1], ids=["blosc_getitem", "blosc_gpu_getitem"])
+def test_single_call_grid(elib, oracle, ref, single_chunks, entry):
+    name, call = single_calls(elib)[entry]
+    for cname, chunk in single_chunks:
+        got = check_single(call, NumpyMem(), NumpyMem(), oracle, ref, chunk, chunk_ranges(chunk), (name, cname))
+        assert got[-2] == -1                                       # start = -1
+
+
+@pytest.mark.parametrize("entry", [0, 1], ids=["blosc_getitem", "blosc_gpu_getitem"])
+def test_single_call_in_passes(elib, oracle, ref, single_chunks, entry):
+    """a pass bound of 16 KiB: a single chunk beyond the bound still decodes, as a pass of its own"""
+    name, call = single_calls(elib)[entry]
+    elib.blosc_amd_getitem_pass_bytes(16 << 10)
+    try:
+        for cname, chunk in single_chunks:
+            check_single(call, NumpyMem(), NumpyMem(), oracle, ref, chunk, chunk_ranges(chunk), (name, cname, "16 KiB passes"))
+    finally:
+        elib.blosc_amd_getitem_pass_bytes(0)
+
+
+def test_single_call_on_damaged_blocks(elib, oracle, ref):
+    damaged = damaged_single_chunks(oracle, ref, lambda d, T, shuffle, cname, bs: lib_compress(elib, d, T, shuffle, cname.encode(), bs))
+    assert len({n.split(",")[0] for n, _, _ in damaged}) == 4
+    for name, call in single_calls(elib):
+        check_damage(call, NumpyMem(), NumpyMem(), oracle, ref, damaged, name)

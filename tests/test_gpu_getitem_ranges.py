@@ -1,10 +1,10 @@
 """blosc_gpu_getitem_batch / blosc_gpu_getitem_packed on the device (include/blosc_gpu_getitem.h): many item ranges of many chunks in one
-call.  Expected results and bytes come from the oracle's orc_getitem on the same chunk, range by range (tests/getitem_ranges_checks.py)."""
+call; blosc_getitem / blosc_gpu_getitem, one range of one chunk through the same pipeline, with host and device memory on either side.  Expected results and bytes come from the oracle's orc_getitem on the same chunk, range by range (tests/getitem_ranges_checks.py)."""
 import numpy as np
 import pytest
 
-from getitem_ranges_checks import (BIG, BLOCKSIZE, SENTINEL, SHUFFLES, SMALL, TYPESIZES, TorchMem, check_batch, chunk_ranges, expected, pick_damage,
-                                   plain, prefix)
+from getitem_ranges_checks import (BIG, BLOCKSIZE, SENTINEL, SHUFFLES, SMALL, TYPESIZES, NumpyMem, TorchMem, check_batch, check_damage, check_single,
+                                   chunk_ranges, damaged_single_chunks, expected, pick_damage, plain, prefix, single_grid_chunks)
 from helpers import header, orc_compress, ref_compress
 
 pytestmark = pytest.mark.gpu
@@ -159,3 +159,54 @@ def test_one_pipeline_per_call(pkg, lib, mem, oracle):
         assert pkg.profile_get("k_decode_streams")[1] == 1 and pkg.profile_get("k_getitem_gather")[1] == 1
     finally:
         lib.blosc_gpu_profile(0)
+
+
+# ---- the single calls: one range of one chunk through the same pipeline ----
+# blosc_getitem finds out by itself where each pointer lies: all four combinations of host and device memory; blosc_gpu_getitem: device memory
+SINGLE = [("blosc_getitem", "host", "host"), ("blosc_getitem", "host", "device"), ("blosc_getitem", "device", "host"),
+          ("blosc_getitem", "device", "device"), ("blosc_gpu_getitem", "device", "device")]
+SINGLE_IDS = [f"{e}-{a}-to-{b}" for e, a, b in SINGLE]
+
+
+def single_call(lib, mem, case):
+    entry, src, dst = case
+    call = lib.blosc_getitem if entry == "blosc_getitem" else (lambda p, s, k, d: lib.blosc_gpu_getitem(p, s, k, d, None))
+    return call, (mem if src == "device" else NumpyMem()), (mem if dst == "device" else NumpyMem())
+
+
+@pytest.fixture(scope="module")
+def single_chunks(pkg, mem, oracle, ref):
+    return single_grid_chunks(oracle, ref, lambda d, T, shuffle, cname, bs: lib_chunks(pkg, mem, [d], T, shuffle, cname, bs)[0])
+
+
+@pytest.fixture(scope="module")
+def damaged(pkg, mem, oracle, ref):
+    out = damaged_single_chunks(oracle, ref, lambda d, T, shuffle, cname, bs: lib_chunks(pkg, mem, [d], T, shuffle, cname, bs)[0])
+    assert len({n.split(",")[0] for n, _, _ in out}) == 4
+    return out
+
+
+@pytest.mark.parametrize("case", SINGLE, ids=SINGLE_IDS)
+def test_single_call_grid(lib, mem, oracle, ref, single_chunks, case):
+    call, src_mem, dst_mem = single_call(lib, mem, case)
+    for cname, chunk in single_chunks:
+        got = check_single(call, src_mem, dst_mem, oracle, ref, chunk, chunk_ranges(chunk), (case, cname))
+        assert got[-2] == -1                                       # start = -1
+
+
+@pytest.mark.parametrize("case", SINGLE, ids=SINGLE_IDS)
+def test_single_call_in_passes(lib, mem, oracle, ref, single_chunks, case):
+    """a pass bound of 16 KiB: a single chunk beyond the bound still decodes, as a pass of its own"""
+    call, src_mem, dst_mem = single_call(lib, mem, case)
+    lib.blosc_amd_getitem_pass_bytes(16 << 10)
+    try:
+        for cname, chunk in single_chunks:
+            check_single(call, src_mem, dst_mem, oracle, ref, chunk, chunk_ranges(chunk), (case, cname, "16 KiB passes"))
+    finally:
+        lib.blosc_amd_getitem_pass_bytes(0)
+
+
+@pytest.mark.parametrize("case", SINGLE, ids=SINGLE_IDS)
+def test_single_call_on_damaged_blocks(lib, mem, oracle, ref, damaged, case):
+    call, src_mem, dst_mem = single_call(lib, mem, case)
+    check_damage(call, src_mem, dst_mem, oracle, ref, damaged, case)

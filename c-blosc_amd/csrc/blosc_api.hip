@@ -561,6 +561,13 @@ int blosc_gpu_checksum_packed(int kind, int nruns, const void* container, size_t
   return checksum_runs(kind, nruns, jobs, digest_out, stream);
 }
 
+// test hooks of the persistent grids (engine.h)
+__attribute__((visibility("default"))) int blosc_internal_persistent_grids(int cap, const char** names, int* launched, int* occupancy) {
+  return bamd::engine_persistent_grids(cap, names, launched, occupancy);
+}
+__attribute__((visibility("default"))) int blosc_internal_enc_lz_occupancy(int dynamic_lds) { return bamd::engine_enc_lz_occupancy(dynamic_lds); }
+__attribute__((visibility("default"))) void blosc_internal_last_compress_tasks(unsigned out[3]) { bamd::engine_last_compress_tasks(out); }
+
 // Filters as stand-alone calls on HOST buffers, same names and signatures as the symbols the
 // reference exports for its own shuffle tests (blosc/shuffle.h:34-61 under BLOSC_TESTING).  The
 // shuffle variants of the byte filter with a bitshuffle-only case (bsize < typesize: not applied,

@@ -30,10 +30,21 @@ constexpr int ENC_TAB_BYTES = BAMD_ENC_SPLIT_TAB ? ENC_TAB * 3 : ENC_TAB * 4;
                                  // filled the registers were two dozen loop-invariant values derived from the lane number that the compiler hoists out of the step and the chain
                                  // loop; with the lane number made opaque at the top of both (enc_lz4p.h) the step fits 80 registers without a spill: 24 waves, 7.6 ms (r06w)
 #endif
-constexpr int ENC_LDS_WAVES = (160 * 1024) / ENC_TAB_BYTES;
+// A CU's 160 KiB of LDS are handed out in granules of 1280 bytes (320 dwords): a workgroup that declares 6656 bytes occupies 7680.  Source:
+// profiles/r07b_lds_granule.txt - the runtime's occupancy figure for the LZ4 kernel against its LDS size.  The compiler's own occupancy remark
+// (-Rpass-analysis=kernel-resource-usage) counts with 128-byte granules and is no guide here.
+constexpr int LDS_BYTES_PER_CU = 160 * 1024;
+constexpr int LDS_GRANULE_BYTES = 1280;
+constexpr int lds_occupied(int bytes) { return (bytes + LDS_GRANULE_BYTES - 1) / LDS_GRANULE_BYTES * LDS_GRANULE_BYTES; }
+constexpr int lds_workgroups_per_cu(int bytes) { return bytes > 0 ? LDS_BYTES_PER_CU / lds_occupied(bytes) : 32; }      // (32: the CU's wave slots)
+// Upper bounds of the persistent grids per CU - what the LDS and the register allocator's plan leave room for.  The grid itself is sized by the
+// runtime's occupancy figure for the kernel, asked once per device (engine.hip: query_persistent_grids), and never above these.
+constexpr int ENC_LDS_WAVES = lds_workgroups_per_cu(ENC_TAB_BYTES);
 constexpr int ENC_WAVES_PER_CU = ENC_LDS_WAVES < 4 * BAMD_ENC_MINWAVES ? ENC_LDS_WAVES : 4 * BAMD_ENC_MINWAVES;   // persistent grid size per CU
-constexpr int ENC_LZ_LDS_WAVES = (160 * 1024) / (ENC_TAB_BYTES + 512);                                             // (+ the parallel emitter's 128 scratch dwords, enc_lz4p.h)
+constexpr int ENC_LZ_SCR_BYTES = 256;                                                                              // the parallel emitter's 64 scratch dwords, enc_lz4p.h
+constexpr int ENC_LZ_LDS_WAVES = lds_workgroups_per_cu(ENC_TAB_BYTES + ENC_LZ_SCR_BYTES);
 constexpr int ENC_LZ_WAVES_PER_CU = ENC_LZ_LDS_WAVES < 4 * BAMD_ENC_LZ_MINWAVES ? ENC_LZ_LDS_WAVES : 4 * BAMD_ENC_LZ_MINWAVES;   // ... of the LZ4 / BloscLZ kernel
+static_assert(lds_occupied(ENC_TAB_BYTES + ENC_LZ_SCR_BYTES) * ENC_LZ_WAVES_PER_CU <= LDS_BYTES_PER_CU, "the LZ4 kernel's workgroups of one CU fit its LDS");
 
 // the table of one wave (LDS)
 struct EncTable {

@@ -26,8 +26,13 @@
 #ifndef BAMD_ENC_PAR
 #define BAMD_ENC_PAR 1
 #endif
-constexpr int ENC_SCR_BYTES = 512;     // 128 dwords behind the hash table: sequence info on its way from rank lanes to byte lanes (one word per position of a step)
-static_assert(ENC_LZ_LDS_WAVES == (160 * 1024) / (ENC_TAB_BYTES + ENC_SCR_BYTES), "enc_lz.h sizes the persistent grid with this scratch in mind");
+// 64 dwords behind the hash table: sequence info on its way from rank lanes to byte lanes, one word per LANE - per position of a 64-position step, per
+// pair of positions of a 128-position one.  Two sequences never start inside one pair: a sequence holds a match of four bytes at least, so the starts of a
+// chain lie four positions apart or more; bit 28 of the word says which position of the pair it is.  (Until round 7 one word per position, 512 bytes: with
+// the 6 KiB table that was 6656 bytes, which the LDS granule rounds to 7680 - 21 workgroups per CU where enc_lz.h counted 24.)
+constexpr int ENC_SCR_BYTES = 256;
+static_assert(ENC_SCR_BYTES == ENC_LZ_SCR_BYTES, "enc_lz.h sizes the persistent grid with this scratch in mind");
+static_assert((ENC_TAB_BYTES + ENC_SCR_BYTES) % LDS_GRANULE_BYTES == 0 || !BAMD_ENC_SPLIT_TAB, "table + scratch fill whole LDS granules");
 #ifndef BAMD_ENC_BACK2
 #define BAMD_ENC_BACK2 1     // sequences whose four bytes in front all match look at eight more (one more memory round trip for the steps that hold such a sequence)
 #endif
@@ -350,13 +355,14 @@ __device__ uint32_t lz4_encode_wave_par(const gu8* __restrict__ src, uint32_t n,
         PROF_ADD(3, 1);
       }
       // sequence info from rank lanes to byte lanes: the word lands on the sequence's first position (the search start cq)
+      // (SS = 1: the word of the pair cq >> 1 = the lane that owns both positions, bit 28 = the odd one; see ENC_SCR_BYTES)
       scr[lane] = 0u;
-      if (SS) scr[lane + 64] = 0u;
       BAMD_LDS_SYNC();
-      if (valid) scr[cq] = 0x80000000u | (excl + hdr) | (inl << 10) | (w << 17) | (L << 23);
+      if (valid) scr[cq >> SS] = 0x80000000u | (excl + hdr) | (inl << 10) | (w << 17) | (L << 23) | (SS ? (cq & 1u) << 28 : 0u);
       BAMD_LDS_SYNC();
-      const uint32_t myw = scr[lq];
-      const uint32_t myw1 = SS ? scr[lq + 1u] : 0u;
+      const uint32_t pw = scr[lane];
+      const uint32_t myw = (SS && (pw & (1u << 28))) ? 0u : pw;
+      const uint32_t myw1 = (SS && (pw & (1u << 28))) ? pw : 0u;
       const uint64_t fm = __ballot((myw >> 31) != 0u);
       uint32_t s;                                                                   // the last sequence start at or before this lane's first position
       bool has;                                                                     // (positions below lane_lo belong to sequences emitted earlier)
@@ -371,7 +377,7 @@ __device__ uint32_t lz4_encode_wave_par(const gu8* __restrict__ src, uint32_t n,
         s = 63u - (uint32_t)__builtin_clzll(below | 1ull);
         has = below != 0ull;
       }
-      const uint32_t inf = scr[s];
+      const uint32_t inf = scr[s >> SS];
       BAMD_LDS_SYNC();
       // ---- all stores of the step: tokens, length bytes, offsets (rank lanes), then literals (byte lanes; SS = 1: one position after the other, so that
       //      the fields of the first are dead before those of the second are made) ----

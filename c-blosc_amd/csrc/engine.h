@@ -72,6 +72,13 @@ void engine_checksum_tile_bytes(size_t bytes);  // test hook: bytes per tile (a 
 // one block through one filter kernel, host buffers (test hook; kind 0..3 = shuffle, unshuffle, bitshuffle, bitunshuffle)
 int engine_filter(int kind, size_t typesize, size_t blocksize, const void* src, void* dst);
 
+// test hooks of the persistent grids (engine.hip: query_persistent_grids; none of them launches a kernel): per persistent kernel its name, the workgroups per
+// CU its launches ask for and the runtime's occupancy figure - returns how many kernels there are, fills the first `cap`; the occupancy of the LZ4 encode
+// kernel with dynamic LDS on top; tasks taken / streams / shuffle tasks of the last compress call that ran streams
+int engine_persistent_grids(int cap, const char** names, int* launched, int* occupancy);
+int engine_enc_lz_occupancy(int dynamic_lds);
+void engine_last_compress_tasks(uint32_t out[3]);
+
 int engine_set_device(int dev);      // selects the HIP device for this process (default: current)
 int engine_thread_device(int dev);   // >= 0: the calling THREAD's calls run on this device (multi-GPU entry points); -1: back to the process-wide one
 int engine_device_count();

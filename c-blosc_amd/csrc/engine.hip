@@ -138,6 +138,44 @@ static int check_done(const uint32_t* fb, size_t expect, size_t expect_zstd, con
   return -1;
 }
 
+// The persistent kernels: one-wave workgroups that draw tasks from queues, launched as many as stay resident - a workgroup beyond that starts when
+// the first ones leave, finds the queues empty and goes, and a grid below it leaves wave slots empty for the whole launch.  How many stay resident is
+// the runtime's to say (registers the compiler really used, LDS in the device's granules): hipOccupancyMaxActiveBlocksPerMultiprocessor, asked once per
+// kernel when a context meets its device; the constexpr bound next to each kernel caps it.  Entries 0 .. kEncModes - 1 are k_encode_streams_t's modes.
+// (k_getitem_gather's grid is a choice, not a residency: 16 waves per CU saturate the copy it is)
+enum { GRID_DECODE = 11, GRID_ZSTD_EXEC, GRID_ZSTD_STREAMS, GRID_ZLIB_STREAMS, kGridKernels };
+struct GridKernel { const char* name; const void* fn; int threads; int bound; };
+static const GridKernel* grid_kernels() {
+#define BAMD_ENC_GRID(MODE) {"k_encode_streams_t<" #MODE ">", (const void*)k_encode_streams_t<MODE>, 64 * ENC_WAVES, enc_grid_bound(MODE)}
+  static const GridKernel k[kGridKernels] = {
+    BAMD_ENC_GRID(ENC_LZ), BAMD_ENC_GRID(ENC_ZSTD), BAMD_ENC_GRID(ENC_ZLIB), BAMD_ENC_GRID(ENC_HC), BAMD_ENC_GRID(ENC_ZSTD_T), BAMD_ENC_GRID(ENC_ZSTD_HC),
+    BAMD_ENC_GRID(ENC_ZLIB_HC), BAMD_ENC_GRID(ENC_ZSTD_TH), BAMD_ENC_GRID(ENC_ZSTD_HCH), BAMD_ENC_GRID(ENC_ZLIB_DYN), BAMD_ENC_GRID(ENC_ZLIB_DYN_HC),
+    {"k_decode_streams", (const void*)k_decode_streams, 64 * DEC_WAVES, DEC_WAVES_PER_CU},
+    {"k_zstd_exec", (const void*)k_zstd_exec, 64, ZEXEC_WAVES_PER_CU},
+    {"k_zstd_streams", (const void*)k_zstd_streams, 64, ZSTD_WAVES_PER_CU},
+    {"k_zlib_streams", (const void*)k_zlib_streams, 64, ZLIB_WAVES_PER_CU}};
+#undef BAMD_ENC_GRID
+  return k;
+}
+static_assert(ENC_LZ == 0 && ENC_ZLIB_DYN_HC == 10, "the encoder's modes index the table above");
+// (k_encode_streams_t states the same for each of its modes)
+static_assert(lds_occupied(DEC_WAVES * (int)DR_LDS_BYTES) * DEC_WAVES_PER_CU <= LDS_BYTES_PER_CU, "k_decode_streams: the workgroups of one CU fit its LDS, granule by granule");
+static_assert(lds_occupied((int)sizeof(uint32_t) * (int)ZXB_WORDS) * ZEXEC_WAVES_PER_CU <= LDS_BYTES_PER_CU, "k_zstd_exec: the workgroups of one CU fit its LDS, granule by granule");
+static_assert(lds_occupied((int)sizeof(ZstdLds)) * ZSTD_WAVES_PER_CU <= LDS_BYTES_PER_CU, "k_zstd_streams: the workgroups of one CU fit its LDS, granule by granule");
+static_assert(lds_occupied((int)sizeof(zi::Tabs)) * ZLIB_WAVES_PER_CU <= LDS_BYTES_PER_CU, "k_zlib_streams: the workgroups of one CU fit its LDS, granule by granule");
+// launches nothing; occupancy[i] = 0 where the runtime gave no answer (the bound alone sizes that grid)
+static void query_persistent_grids(int* wpc, int* occupancy) {
+  const GridKernel* k = grid_kernels();
+  for (int i = 0; i < kGridKernels; i++) {
+    int occ = 0;
+#ifndef BAMD_WAVE_EMU      // (the emulator runs a grid's workgroups one after the other: any size is a right one)
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k[i].fn, k[i].threads, 0) != hipSuccess || occ < 0) { (void)hipGetLastError(); occ = 0; }
+#endif
+    occupancy[i] = occ;
+    wpc[i] = (occ > 0 && occ < k[i].bound) ? occ : k[i].bound;
+  }
+}
+
 struct EngineState {
   std::mutex mu;
   bool device_ok = false;
@@ -161,6 +199,8 @@ struct EngineState {
   // or BLOSC_AMD_SINGLE_QUEUE=1) - one queue, shuffle / unshuffle in kernels of their own.
   bool single_queue = false;
   int cus = 0;          // compute units of the selected device (persistent grids)
+  // workgroups per CU of every persistent kernel on this device: the runtime's occupancy figure, never above the kernel's own bound (query_persistent_grids above)
+  int grid_wpc[kGridKernels] = {0}, grid_occupancy[kGridKernels] = {0};
   // Tables that are a function of a batch's GEOMETRY alone - the block table and the task queues (0.5 MB for 128 chunks of 64 MiB) - stay on the
   // device from one call to the next (round 6).  A call that finds its own block table, fusion flags and SET of expensive planes (order_signature) equal to the ones the tables
   // were made from neither builds the queues nor uploads anything but its chunk descriptors: callers send equal-shaped chunks call after call
@@ -371,6 +411,7 @@ static int ensure_device(EngineState& st) {
     st.single_queue = true;
     if (debug_enabled()) fprintf(stderr, "blosc_amd: %s is not on the allow-list of the relaxed in-kernel hand-off; using one task queue and unfused filters\n", have_props ? pr.gcnArchName : "(unknown device)");
   }
+  query_persistent_grids(st.grid_wpc, st.grid_occupancy);
   st.enc_cost_valid = st.dec_cost_valid = false;
   st.device_ok = true;
   st.device_hint.store(st.device, std::memory_order_relaxed);
@@ -512,33 +553,37 @@ struct HostStaging {
 // it waits for the kernel, writes the file and frees them.  BAMD_PROF_ARG is that last argument.  The product build has neither.
 #ifdef BAMD_PROFILE_DECODE
 struct StreamProfile {
-  uint32_t* d = nullptr; const char* path; size_t bytes; hipStream_t stream;
-  StreamProfile(const char* switch_name, size_t nstr, hipStream_t s) : path(getenv(switch_name)), bytes(nstr * 64), stream(s) {
-    if (path && hipMalloc((void**)&d, bytes) == hipSuccess) (void)hipMemsetAsync(d, 0, bytes, stream);
+  uint32_t* d = nullptr; std::string path; size_t bytes; hipStream_t stream;
+  // suffix: a second file next to the one the switch names (the encode kernel's per-wave records: <file>.waves, one record per workgroup of the grid)
+  StreamProfile(const char* switch_name, size_t nrec, hipStream_t s, const char* suffix = "") : path(getenv(switch_name) ? getenv(switch_name) : ""), bytes(nrec * 64), stream(s) {
+    if (!path.empty()) path += suffix;
+    if (!path.empty() && bytes && hipMalloc((void**)&d, bytes) == hipSuccess) (void)hipMemsetAsync(d, 0, bytes, stream);
   }
   ~StreamProfile() {
     if (!d) return;
     std::vector<uint32_t> h(bytes / 4);
     (void)hipStreamSynchronize(stream); (void)hipMemcpy(h.data(), d, bytes, hipMemcpyDeviceToHost); (void)hipFree(d);
-    FILE* f = fopen(path, "wb");
+    FILE* f = fopen(path.c_str(), "wb");
     if (f) { fwrite(h.data(), 4, h.size(), f); fclose(f); }
   }
 };
 #define BAMD_STREAM_PROFILE(var, switch_name, nstr) StreamProfile var(switch_name, nstr, stream)
+#define BAMD_WAVE_PROFILE(var, switch_name, nwaves) StreamProfile var(switch_name, nwaves, stream, ".waves")
 #define BAMD_PROF_ARG(var) , var.d
 #else
 #define BAMD_STREAM_PROFILE(var, switch_name, nstr)
+#define BAMD_WAVE_PROFILE(var, switch_name, nwaves)
 #define BAMD_PROF_ARG(var)
 #endif
 
 // The variant of k_encode_streams_t that serves a (codec, clevel), and what its launch needs.  The switches are read per call, as ever.
 struct EncVariant {
   int mode = ENC_LZ; const char* name = "k_encode_streams";
-  int waves_per_cu = 0;            // what fits into a CU's LDS
+  int waves_per_cu = 0;            // what stays resident on a CU (EngineState::grid_wpc)
   bool zstd = false, zdyn = false; // Zstd: predefined FSE tables + one sequence scratch per persistent wave; zlib with dynamic codes: the token scratch
   int detect = 0;                  // the periodic-plane shortcut of the shuffle tasks
 };
-static EncVariant encoder_variant(int codec, int clevel) {
+static EncVariant encoder_variant(const EngineState& st, int codec, int clevel) {
   EncVariant v;
   // "lz4hc": the LZ4HC-grade search of k_encode.hip (lz4hc_encode_wave), or the plain LZ4 match finder at its highest effort
   const bool zstd = codec == kZstd, zlibc = codec == kZlib;
@@ -552,8 +597,6 @@ static EncVariant encoder_variant(int codec, int clevel) {
   // ratio: search + dynamic codes give 73.4 (reference 47.4, fixed codes without search 40.5) at 57 ms per 8 GiB, still 150 GB/s.
   const bool zsearch = (zstd && zstd_search_enabled(clevel)) || (zlibc && zlib_search_enabled());
   const bool zhuf = zstd && (ztab || zsearch) && zstd_huffman_enabled();      // Huffman-coded literals: on top of either switch
-  const int enc_wpc_lz = (zstd || zlibc) ? ENC_WAVES_PER_CU : ENC_LZ_WAVES_PER_CU;
-  v.waves_per_cu = zsearch ? (160 * 1024) / (HC_TAB_BYTES + ZS_LDS_BYTES) : (hc ? HC_WAVES_PER_CU : enc_wpc_lz);
   v.zstd = zstd;
   v.zdyn = zlibc && zlib_dynamic_enabled();      // zlib with dynamic Huffman codes: two passes, the tokens in the sequence scratch
   v.detect = (!zstd && !zlibc && periodic_enabled()) ? 1 : 0;
@@ -566,6 +609,7 @@ static EncVariant encoder_variant(int codec, int clevel) {
   else if (zlibc) v.mode = ENC_ZLIB;
   else if (hc) v.mode = ENC_HC;
   else v.mode = ENC_LZ;
+  v.waves_per_cu = st.grid_wpc[v.mode];
   return v;
 }
 constexpr int kEncModes = 11;      // ENC_LZ ... ENC_ZLIB_DYN_HC
@@ -638,6 +682,37 @@ static bool add_encode_chunk(const CompressParams& p, const Job& job, int i, int
   return true;
 }
 
+// test hooks (tests/test_gpu_persistent_grid.py).  Neither launches a kernel: a context that has met its device answers from what it asked then,
+// otherwise the runtime is asked now, for the device the calling thread would use.
+int engine_persistent_grids(int cap, const char** names, int* launched, int* occupancy) {
+  CtxGuard ctx; EngineState& st = *ctx.st;
+  int wpc[kGridKernels], occ[kGridKernels];
+  if (st.device_ok && wanted_device() == st.device) { memcpy(wpc, st.grid_wpc, sizeof wpc); memcpy(occ, st.grid_occupancy, sizeof occ); }
+  else {
+    const int dev = wanted_device();
+    if (dev < 0 || hipSetDevice(dev) != hipSuccess) return -1;
+    query_persistent_grids(wpc, occ);
+  }
+  for (int i = 0; i < kGridKernels && i < cap; i++) { names[i] = grid_kernels()[i].name; launched[i] = wpc[i]; occupancy[i] = occ[i]; }
+  return kGridKernels;
+}
+// resident workgroups per CU of the LZ4 / BloscLZ encode kernel with `dynamic_lds` bytes on top of its own LDS (scripts/lds_granule.py: where the
+// figure steps says how the device hands out LDS); < 0: no answer
+int engine_enc_lz_occupancy(int dynamic_lds) {
+#ifdef BAMD_WAVE_EMU
+  return -1;
+#else
+  const int dev = wanted_device();
+  int occ = -1;
+  if (dev < 0 || hipSetDevice(dev) != hipSuccess) return -1;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)k_encode_streams_t<ENC_LZ>, 64 * ENC_WAVES, (size_t)dynamic_lds) != hipSuccess) { (void)hipGetLastError(); return -1; }
+  return occ;
+#endif
+}
+// the last compress call of this process that ran streams: tasks its kernels took (the sum of every launch's plane_cost[256]), streams and shuffle tasks it queued
+static std::atomic<uint32_t> g_last_enc_tasks[3];
+void engine_last_compress_tasks(uint32_t out[3]) { for (int i = 0; i < 3; i++) out[i] = g_last_enc_tasks[i].load(); }
+
 int engine_compress_batch(const CompressParams* params, bool per_chunk, int n, const Job* jobs, int* results, bool device_ptrs,
                           hipStream_t stream, const PackedBuffer* packed) {
   if (n <= 0) return 0;
@@ -659,7 +734,7 @@ int engine_compress_batch(const CompressParams* params, bool per_chunk, int n, c
     io.add((size_t)chunks[(size_t)i].nbytes, (size_t)chunks[(size_t)i].cbytes);
     if (chunks[(size_t)i].mode & CH_MEMCPYED) continue;
     int8_t& m = variant_of[p.codec][p.clevel];      // (both in range: the chunk passed add_encode_chunk's checks)
-    if (m < 0) { const EncVariant v = encoder_variant(p.codec, p.clevel); m = (int8_t)v.mode; B.variants[v.mode] = v; }
+    if (m < 0) { const EncVariant v = encoder_variant(st, p.codec, p.clevel); m = (int8_t)v.mode; B.variants[v.mode] = v; }
     B.variant[(size_t)i] = (uint8_t)m;
     if (!B.present[m]) { B.present[m] = true; B.ngroups++; }
   }
@@ -778,7 +853,8 @@ int engine_compress_batch(const CompressParams* params, bool per_chunk, int n, c
     const int detect = v.detect;
     const dim3 grid(persistent_grid(st, (size_t)g.ntasks, v.waves_per_cu)), block(64 * ENC_WAVES);
     BAMD_STREAM_PROFILE(prof, "BLOSC_AMD_ENC_PROFILE", nstr);
-#define BAMD_ENC_LAUNCH(MODE) case MODE: hipLaunchKernelGGL(k_encode_streams_t<MODE>, grid, block, 0, stream, d_streams, d_ticket, d_qlist, d_qoff, d_shoff, d_chunks, d_blocks, d_ready, d_cost, st.single_queue ? 1 : 0, d_seqbufs, d_ctabs, detect BAMD_PROF_ARG(prof)); break
+    BAMD_WAVE_PROFILE(wprof, "BLOSC_AMD_ENC_PROFILE", grid.x);
+#define BAMD_ENC_LAUNCH(MODE) case MODE: hipLaunchKernelGGL(k_encode_streams_t<MODE>, grid, block, 0, stream, d_streams, d_ticket, d_qlist, d_qoff, d_shoff, d_chunks, d_blocks, d_ready, d_cost, st.single_queue ? 1 : 0, d_seqbufs, d_ctabs, detect BAMD_PROF_ARG(prof) BAMD_PROF_ARG(wprof)); break
     switch (g.mode) {
       BAMD_ENC_LAUNCH(ENC_ZSTD_HCH); BAMD_ENC_LAUNCH(ENC_ZSTD_HC); BAMD_ENC_LAUNCH(ENC_ZSTD_TH); BAMD_ENC_LAUNCH(ENC_ZSTD_T); BAMD_ENC_LAUNCH(ENC_ZSTD);
       BAMD_ENC_LAUNCH(ENC_ZLIB_DYN_HC); BAMD_ENC_LAUNCH(ENC_ZLIB_DYN); BAMD_ENC_LAUNCH(ENC_ZLIB_HC); BAMD_ENC_LAUNCH(ENC_ZLIB);
@@ -818,6 +894,14 @@ int engine_compress_batch(const CompressParams* params, bool per_chunk, int n, c
   for (size_t k = 0; nstr && k < tc.groups.size(); k++)      // every group's launch took what was queued for it
     if (check_done((const uint32_t*)(P + p_cost) + kCostWords * k, (size_t)tc.groups[k].ntasks, 0, "compress")) return -1;
   if (packed) for (int i = 0; i <= n; i++) packed->offsets[i] = (size_t)((const uint64_t*)(P + p_offsets))[i];
+  if (nstr) {
+    uint32_t taken = 0, nshuf = 0;
+    for (size_t k = 0; k < tc.groups.size(); k++) {
+      taken += ((const uint32_t*)(P + p_cost) + kCostWords * k)[256];
+      nshuf += (uint32_t)tc.queues[tc.groups[k].sh_at + 8];      // shoff[8]: the entries of the group's eight shuffle lists
+    }
+    g_last_enc_tasks[0] = taken; g_last_enc_tasks[1] = (uint32_t)nstr; g_last_enc_tasks[2] = nshuf;
+  }
   tc.commit(B.key);
   if (feedback && nstr >= 4096) { memcpy(st.enc_cost, P + p_cost, sizeof st.enc_cost); st.enc_cost_valid = true; }   // small calls say little
   const int32_t* r = (const int32_t*)(P + p_results);
@@ -1015,7 +1099,7 @@ static int launch_decode(EngineState& st, const DecodeLaunch& L, hipStream_t str
     }
     if (L.nstr_queued) {
       ProfScope ps(st, stream, "k_decode_streams");
-      const dim3 dgrid(persistent_grid(st, L.nstr_queued ? L.nstr_queued : 1, DEC_WAVES_PER_CU));
+      const dim3 dgrid(persistent_grid(st, L.nstr_queued ? L.nstr_queued : 1, st.grid_wpc[GRID_DECODE]));
       BAMD_STREAM_PROFILE(prof, "BLOSC_AMD_DEC_PROFILE", L.nstr);
       hipLaunchKernelGGL(k_decode_streams, dgrid, dim3(64 * DEC_WAVES), 0, stream, L.d_streams, L.d_status, L.d_ticket, L.d_qlist, L.d_qoff, L.d_chunks, L.d_blocks, L.d_blkdone, L.d_spans, L.d_pat, L.d_cost, st.single_queue ? 1 : 0 BAMD_PROF_ARG(prof));
     }
@@ -1039,7 +1123,7 @@ static int launch_decode(EngineState& st, const DecodeLaunch& L, hipStream_t str
       }
       {
         ProfScope ps(st, stream, "k_zstd_exec");
-        hipLaunchKernelGGL(k_zstd_exec, dim3(persistent_grid(st, L.nstr, ZEXEC_WAVES_PER_CU)), dim3(64), 0, stream, L.d_streams, (int)L.nstr, L.d_status, L.d_zticket + 1,
+        hipLaunchKernelGGL(k_zstd_exec, dim3(persistent_grid(st, L.nstr, st.grid_wpc[GRID_ZSTD_EXEC])), dim3(64), 0, stream, L.d_streams, (int)L.nstr, L.d_status, L.d_zticket + 1,
                            L.d_chunks, L.d_blocks, L.d_zmeta, L.zseq_delta);
       }
       d_taken = (const uint32_t*)L.d_zmeta;
@@ -1047,12 +1131,12 @@ static int launch_decode(EngineState& st, const DecodeLaunch& L, hipStream_t str
     if (L.any_zstd) {
       ProfScope ps(st, stream, "k_zstd_streams");
       BAMD_STREAM_PROFILE(zprof, "BLOSC_AMD_ZSTD_PROFILE", L.nstr);
-      hipLaunchKernelGGL(k_zstd_streams, dim3(persistent_grid(st, L.nstr, ZSTD_WAVES_PER_CU)), dim3(64), 0, stream, L.d_streams, (int)L.nstr, L.d_status,
+      hipLaunchKernelGGL(k_zstd_streams, dim3(persistent_grid(st, L.nstr, st.grid_wpc[GRID_ZSTD_STREAMS])), dim3(64), 0, stream, L.d_streams, (int)L.nstr, L.d_status,
                          L.d_zticket, L.d_chunks, L.d_blocks, L.d_cost + 257, d_taken BAMD_PROF_ARG(zprof));
     }
     if (L.any_zlib) {
       ProfScope ps(st, stream, "k_zlib_streams");
-      hipLaunchKernelGGL(k_zlib_streams, dim3(persistent_grid(st, L.nstr_zlib ? L.nstr_zlib : 1, ZLIB_WAVES_PER_CU)), dim3(64), 0, stream, L.d_streams, L.d_status,
+      hipLaunchKernelGGL(k_zlib_streams, dim3(persistent_grid(st, L.nstr_zlib ? L.nstr_zlib : 1, st.grid_wpc[GRID_ZLIB_STREAMS])), dim3(64), 0, stream, L.d_streams, L.d_status,
                          L.d_zticket + 8, L.d_zqlist, L.d_zqoff, L.d_cost + 259, L.d_chunks, L.d_blocks, L.d_blkdone, st.single_queue ? 1 : 0);
     }
     if (L.any_shuf) {

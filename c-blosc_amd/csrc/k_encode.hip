@@ -37,7 +37,13 @@ namespace bamd {
 //        5 backward extensions tried, 7 of those > 0 bytes, 4 of those > 4 bytes
 //        (Zstd: 4 cycles tail literals + offset values, 5 cycles sequences section)
 //        13 cycles: waiting for the block's shuffle task
-//        8 cycles: window+probe, 9 candidates+select, 10 extension, 11 emit, 12 tail
+//        8 cycles: window+probe, 9 candidates+select, 10 extension, 11 emit, 12 tail; 15: the device's real-time clock (100 MHz, one for all CUs) at the stream's end
+// and per persistent wave (the kernel's last parameter, scripts/enc_wave_time.py), 16 words: 0-1 real-time clock at entry, 2-3 at exit (s_memtime, the
+// shader clock the cycle counts are in, starts differently on every shader engine: it orders nothing between two waves), 4 cycles inside
+// encode_one_stream (slot 13 of its streams - the second wait for the block's shuffle - included), 5 inside shuffle_block_task, 6 in the queue loop's
+// wait for a block that is not shuffled yet (without the shuffle tasks taken meanwhile), 7 tasks taken, 8 of them streams, 9 shuffle tasks run
+// (queue entries and help), 10 XCC id, 12 cycles from entry to exit, 13 the part of 6 in front of the wave's first stream (the launch's ramp).
+// What is left of exit - entry is tickets, descriptors and the calls.
 #ifdef BAMD_PROFILE_DECODE
 #define EPROF_ARG , DecProf& prof_
 #define EPROF_PASS , prof_
@@ -123,7 +129,7 @@ __device__ __attribute__((noinline)) void encode_one_stream(StreamDesc* sd_, enc
     atomicAdd(plane_cost + (j & 255u), (uint32_t)((__builtin_amdgcn_s_memtime() - cost_t0) >> 10));
   }
 #ifdef BAMD_PROFILE_DECODE
-  prof_.c[15] = (uint32_t)(prof_.t0 >> 6);
+  prof_.c[15] = (uint32_t)__builtin_amdgcn_s_memrealtime();
   if (lane == 0 && profslot) for (int i_ = 0; i_ < 16; i_++) profslot[i_] = prof_.c[i_];
 #endif
 }
@@ -133,21 +139,45 @@ __device__ __attribute__((noinline)) void encode_one_stream(StreamDesc* sd_, enc
 // host puts every block's shuffle task a few dozen entries ahead of its streams (queue_order.h:
 // build_encode_queues), so the bandwidth-bound transposes run underneath the latency/issue-bound match
 // finding of other waves instead of in a kernel of their own.
+// LDS of one workgroup: the match finder's table, the writers' LDS behind it (ENC_LZ: the 64 scratch dwords of the parallel LZ4 emitter, enc_lz4p.h)
+constexpr int enc_lds_bytes(int mode) {
+  return (enc_mode_hc(mode) ? HC_TAB_BYTES : ENC_TAB_BYTES) +
+         (enc_mode_zstd(mode) ? ZS_LDS_BYTES : (enc_mode_zlib(mode) ? DFL_LDS_BYTES : (mode == ENC_LZ ? ENC_SCR_BYTES : 0)));
+}
+// waves per SIMD the register allocator plans for: the 24 KiB table of the HC modes leaves room for 1.5, the Zstd modes' LDS for 5
+constexpr int enc_min_waves(int mode) {
+  return enc_mode_hc(mode) ? 2 : ((mode == ENC_ZSTD_T || mode == ENC_ZSTD_TH) ? 5 : (mode == ENC_LZ ? BAMD_ENC_LZ_MINWAVES : BAMD_ENC_MINWAVES));
+}
+// upper bound of the persistent grid per CU: whole LDS granules (enc_lz.h), and no more waves than the CU has slots for.  The launch takes the
+// runtime's occupancy figure (engine.hip: query_persistent_grids), which also knows the registers the compiler really used.
+constexpr int enc_grid_bound(int mode) { return lds_workgroups_per_cu(enc_lds_bytes(mode)) < 32 ? lds_workgroups_per_cu(enc_lds_bytes(mode)) : 32; }
 template <int MODE>
-// (waves per SIMD the register allocator plans for: the 24 KiB table of the HC modes leaves room for 1.5, the Zstd modes' LDS for 5)
-__global__ __launch_bounds__(64 * ENC_WAVES, enc_mode_hc(MODE) ? 2 : ((MODE == ENC_ZSTD_T || MODE == ENC_ZSTD_TH) ? 5 : (MODE == ENC_LZ ? BAMD_ENC_LZ_MINWAVES : BAMD_ENC_MINWAVES))) void k_encode_streams_t(
+__global__ __launch_bounds__(64 * ENC_WAVES, enc_min_waves(MODE)) void k_encode_streams_t(
     StreamDesc* __restrict__ streams, uint32_t* __restrict__ tickets /*[8]*/, const int32_t* __restrict__ qlist,
     const int32_t* __restrict__ qoff /*[9]*/, const int32_t* __restrict__ shoff /*[9] | shuffle list*/, const ChunkDesc* __restrict__ chunks, const BlockDesc* __restrict__ blocks,
     uint32_t* __restrict__ blk_ready, uint32_t* __restrict__ plane_cost, int single_queue,
     uint64_t* __restrict__ seqbufs, const zenc::CTabs* __restrict__ ctabs, int detect_periodic
 #ifdef BAMD_PROFILE_DECODE
-    , uint32_t* __restrict__ profbuf
+    , uint32_t* __restrict__ profbuf, uint32_t* __restrict__ profwave
 #endif
     ) {
+#ifdef BAMD_PROFILE_DECODE
+  const uint64_t wt_entry = __builtin_amdgcn_s_memtime(), wr_entry = __builtin_amdgcn_s_memrealtime();
+  uint64_t wt_stream = 0, wt_shuffle = 0, wt_wait = 0, wt_wait_first = 0;
+  uint32_t wn_stream = 0, wn_shuffle = 0;
+#define WPROF_BEGIN(t) const uint64_t t = __builtin_amdgcn_s_memtime()
+#define WPROF_END(acc, t) acc += __builtin_amdgcn_s_memtime() - t
+#else
+#define WPROF_BEGIN(t)
+#define WPROF_END(acc, t)
+#endif
   constexpr bool ZSTD = enc_mode_zstd(MODE);
   constexpr int TABBYTES = enc_mode_hc(MODE) ? HC_TAB_BYTES : ENC_TAB_BYTES;      // the match finder's table; the writers' LDS sits behind it
-  __shared__ __attribute__((aligned(16))) enc_entry_t tabs[ENC_WAVES][(TABBYTES + (ZSTD ? ZS_LDS_BYTES : (enc_mode_zlib(MODE) ? DFL_LDS_BYTES : (MODE == ENC_LZ ? ENC_SCR_BYTES : 0)))) / 4];      // ENC_LZ: the 64 scratch dwords of the parallel LZ4 emitter behind the table (enc_lz4p.h)
+  // declared in whole granules, which is what the workgroup occupies anyway: the runtime's occupancy figure divides the CU's LDS by the declared size
+  // (profiles/r07b_lds_granule.txt) and is the resident count only then
+  __shared__ __attribute__((aligned(16))) enc_entry_t tabs[ENC_WAVES][lds_occupied(enc_lds_bytes(MODE)) / 4];
   static_assert(ENC_WAVES == 1, "one stream per wave, one wave per workgroup");
+  static_assert(lds_occupied(enc_lds_bytes(MODE)) * enc_grid_bound(MODE) <= LDS_BYTES_PER_CU, "the workgroups of one CU fit its LDS, granule by granule");
   const int lane = threadIdx.x & 63;
   uint64_t* seqbuf = nullptr;
   if (ZSTD) {       // the predefined FSE tables of the sequence coder, once per persistent wave
@@ -168,7 +198,12 @@ __global__ __launch_bounds__(64 * ENC_WAVES, enc_mode_hc(MODE) ? 2 : ((MODE == E
   auto shuffle_one = [&]() -> bool {
     const uint32_t s = take_ticket(tickets + 8 + xcc, lane);
     if (s >= shlen) return false;
+    WPROF_BEGIN(ts_);
     shuffle_block_task(chunks, blocks, uni((uint32_t)shlist[shbase + s]), blk_ready, streams, detect_periodic, lane, (volatile uint32_t*)tabs[0]);
+    WPROF_END(wt_shuffle, ts_);
+#ifdef BAMD_PROFILE_DECODE
+    wn_shuffle++;
+#endif
     return true;
   };
   uint32_t t = take_ticket(tickets + xcc, lane);
@@ -187,15 +222,24 @@ __global__ __launch_bounds__(64 * ENC_WAVES, enc_mode_hc(MODE) ? 2 : ((MODE == E
         // (profiles/r04/r04z2_enc_ab_help_bound_variants.txt).
         const ChunkDesc* cd = chunks + uni((uint32_t)sd->chunk);
         bool more = !(uni(cd->mode) & CH_BITSHUFFLE) && shuffle_generic_T(uni((uint32_t)cd->typesize));
+#ifdef BAMD_PROFILE_DECODE
+        const uint64_t tw_ = __builtin_amdgcn_s_memtime(), sh0_ = wt_shuffle;
+#endif
         while (__hip_atomic_load(&blk_ready[gb], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
           // ... but not further ahead of its own block than BAMD_ENC_HELP blocks of the list: planes shuffled much earlier than they are
           // encoded have left the L2 / MALL by then (unbounded: config 2 + 7 %, profiles/r04/r04z_enc_ab_help_unbounded_vs_off.txt)
           if (BAMD_ENC_HELP && more && __hip_atomic_load(tickets + 8 + xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (single_queue ? gb : gb / 8u) + (uint32_t)BAMD_ENC_HELP) more = shuffle_one();
           else __builtin_amdgcn_s_sleep(16);
         }
+#ifdef BAMD_PROFILE_DECODE
+        wt_wait += (__builtin_amdgcn_s_memtime() - tw_) - (wt_shuffle - sh0_);
+        if (wn_stream == 0) wt_wait_first = wt_wait;
+#endif
       }
 #ifdef BAMD_PROFILE_DECODE
+      const uint64_t te_ = __builtin_amdgcn_s_memtime();
       encode_one_stream<MODE>(streams + task, tabs[0], chunks, blk_ready, lane, blocks, (uint32_t)task, plane_cost, seqbuf, profbuf ? profbuf + (size_t)task * 16 : nullptr);
+      wt_stream += __builtin_amdgcn_s_memtime() - te_; wn_stream++;
 #else
       encode_one_stream<MODE>(streams + task, tabs[0], chunks, blk_ready, lane, blocks, (uint32_t)task, plane_cost, seqbuf);
 #endif
@@ -204,6 +248,18 @@ __global__ __launch_bounds__(64 * ENC_WAVES, enc_mode_hc(MODE) ? 2 : ((MODE == E
     t = take_ticket(tickets + xcc, lane);
   }
   if (lane == 0 && ndone) atomicAdd(plane_cost + 256, ndone);
+#ifdef BAMD_PROFILE_DECODE
+  if (lane == 0 && profwave) {
+    uint32_t* w = profwave + (size_t)blockIdx.x * 16;
+    const uint64_t wt_exit = __builtin_amdgcn_s_memtime(), wr_exit = __builtin_amdgcn_s_memrealtime();
+    w[0] = (uint32_t)wr_entry; w[1] = (uint32_t)(wr_entry >> 32); w[2] = (uint32_t)wr_exit; w[3] = (uint32_t)(wr_exit >> 32);
+    w[4] = (uint32_t)wt_stream; w[5] = (uint32_t)wt_shuffle; w[6] = (uint32_t)wt_wait; w[7] = ndone; w[8] = wn_stream; w[9] = wn_shuffle; w[10] = xcc;
+    w[11] = 1u;      // the record is written
+    w[12] = (uint32_t)(wt_exit - wt_entry); w[13] = (uint32_t)wt_wait_first;
+  }
+#endif
+#undef WPROF_BEGIN
+#undef WPROF_END
 }
 
 // The stream table of a compress call, one thread per block: stream s of block j reads the block's split s out of the filtered image

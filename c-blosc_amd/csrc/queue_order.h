@@ -24,8 +24,17 @@ namespace bamd {
 // chunk_group != nullptr (a batch whose chunks go to more than one variant of the encode kernel, engine.hip): only the blocks of the
 // chunks c with chunk_group[c] == group are queued - streams, shuffle tasks and shuffle list alike, so a launch that is given these
 // queues never sees a task of another group's chunk.  A block keeps its queue g % nq whatever the group: the table is one for the batch.
-constexpr size_t kEncLookaheadDefault = 32;
-inline size_t enc_lookahead() { return kEncLookaheadDefault; }     // (swept 1 ... 64 in round 4: 8.4 ... 8.0 ms, profiles/r04/r04q_enc_lookahead_sweep.txt - the distance hardly matters)
+// The distance in blocks.  A shuffle task of one wave takes about 1.1 M clocks of the 2.4 GHz shader clock on a 1 MiB block (profiles/r07a_*), and with 768
+// waves of an XCD drawing from a first pass of three entries per block (the shuffle task, two expensive planes) a ticket is drawn every 3.7 k clocks: at 32
+// blocks = 96 tickets the streams of a block were drawn 0.36 M clocks behind its shuffle task and slept through the rest of it - half of the 11 % of resident
+// wave time the kernel spent waiting (the other half is the launch's ramp).  96 blocks cover the task.  Round 7, config 2, same session: 32 / 64 / 96 / 160
+// blocks: 7.24 / 7.08 / 7.00 - 7.05 / 7.01 ms (profiles/r07c_bench_parent_vs_branch.txt).  (Round 4's sweep, 1 ... 64: 8.4 ... 8.0 ms, "hardly matters" -
+// with 20 waves per CU and streams twice as long.)
+#ifndef BAMD_ENC_LOOKAHEAD
+#define BAMD_ENC_LOOKAHEAD 96
+#endif
+constexpr size_t kEncLookaheadDefault = BAMD_ENC_LOOKAHEAD;
+inline size_t enc_lookahead() { return kEncLookaheadDefault; }
 // BLOSC_AMD_SCHED=0: plain block order (no cost feedback)
 // (read once: getenv is not safe against a setenv from another host thread.  blosc_gpu_profile(2) switches the feedback off for the calls
 //  that follow - bench.py's `sched_cold` leg: one step in the order a first call on new data gets)

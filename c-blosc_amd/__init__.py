@@ -80,104 +80,92 @@ def load():
         raise RuntimeError(
             f"{LIB_PATH} not found: build it with `make -C {_HERE}` (hipcc, gfx950). "
             "There is no fallback implementation.")
-    L = C.CDLL(LIB_PATH)
-    vp, sz, i = C.c_void_p, C.c_size_t, C.c_int
-    L.blosc_compress.argtypes = [i, i, sz, sz, vp, vp, sz]
-    L.blosc_compress_ctx.argtypes = [i, i, sz, sz, vp, vp, sz, C.c_char_p, sz, i]
-    L.blosc_decompress.argtypes = [vp, vp, sz]
-    L.blosc_decompress_ctx.argtypes = [vp, vp, sz, i]
-    L.blosc_getitem.argtypes = [vp, i, i, vp]
-    L.blosc_set_compressor.argtypes = [C.c_char_p]
-    L.blosc_get_compressor.restype = C.c_char_p
-    L.blosc_list_compressors.restype = C.c_char_p
-    L.blosc_get_version_string.restype = C.c_char_p
-    L.blosc_cbuffer_complib.restype = C.c_char_p
-    L.blosc_cbuffer_complib.argtypes = [vp]
-    L.blosc_compname_to_compcode.argtypes = [C.c_char_p]
-    L.blosc_compcode_to_compname.argtypes = [i, C.POINTER(C.c_char_p)]
-    L.blosc_get_complib_info.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]
-    L.blosc_cbuffer_sizes.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
-    L.blosc_cbuffer_sizes.restype = None
-    L.blosc_cbuffer_validate.argtypes = [vp, sz, C.POINTER(sz)]
-    L.blosc_cbuffer_metainfo.argtypes = [vp, C.POINTER(sz), C.POINTER(i)]
-    L.blosc_cbuffer_metainfo.restype = None
-    L.blosc_cbuffer_versions.argtypes = [vp, C.POINTER(i), C.POINTER(i)]
-    L.blosc_cbuffer_versions.restype = None
-    L.blosc_set_blocksize.argtypes = [sz]
-    L.blosc_set_blocksize.restype = None
-    L.blosc_set_splitmode.argtypes = [i]
-    L.blosc_set_splitmode.restype = None
-    L.blosc_gpu_compress_batch.argtypes = [i, i, sz, C.c_char_p, sz, i, C.POINTER(vp), C.POINTER(sz),
-                                           C.POINTER(vp), C.POINTER(sz), C.POINTER(i), vp]
-    L.blosc_gpu_decompress_batch.argtypes = [i, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz),
-                                             C.POINTER(i), vp]
-    L.blosc_gpu_compress_batch_host.argtypes = [i, i, sz, C.c_char_p, sz, i, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(i)]
-    L.blosc_gpu_decompress_batch_host.argtypes = [i, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(i)]
-    if hasattr(L, "blosc_gpu_partition"):        # (A/B scripts also load builds of earlier rounds through this loader)
-        L.blosc_gpu_partition.argtypes = [sz, i, i, C.POINTER(sz), C.POINTER(sz)]
-        L.blosc_gpu_compress_batch_multi.argtypes = [i, C.POINTER(i), i, i, sz, C.c_char_p, sz, i, C.POINTER(vp), C.POINTER(sz),
-                                                     C.POINTER(vp), C.POINTER(sz), C.POINTER(i)]
-        L.blosc_gpu_decompress_batch_multi.argtypes = [i, C.POINTER(i), i, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(i)]
-    if hasattr(L, "blosc_gpu_compress_packed"):
-        declare_packed(L)
-    if hasattr(L, "blosc_gpu_compress_batch_params"):
-        declare_params(L)
-    if hasattr(L, "blosc_gpu_getitem_batch"):
-        declare_getitem(L)
-    if hasattr(L, "blosc_gpu_checksum_batch"):
-        declare_checksum(L)
-    L.blosc_gpu_getitem.argtypes = [vp, i, i, vp, vp]
-    L.blosc_gpu_profile.argtypes = [i]
-    L.blosc_gpu_profile.restype = None
-    L.blosc_gpu_profile_reset.restype = None
-    L.blosc_gpu_profile_get.argtypes = [C.c_char_p, C.POINTER(C.c_double), C.POINTER(i)]
-    for name in ("blosc_internal_shuffle", "blosc_internal_unshuffle"):
-        getattr(L, name).argtypes = [sz, sz, vp, vp]
-        getattr(L, name).restype = None
-    for name in ("blosc_internal_bitshuffle", "blosc_internal_bitunshuffle"):
-        getattr(L, name).argtypes = [sz, sz, vp, vp, vp]
-    if hasattr(L, "blosc_amd_policy_blocksize"):
-        L.blosc_amd_policy_blocksize.argtypes = [i, i, i, i, i, i]
-        L.blosc_amd_policy_split.argtypes = [i, i, i, i]
-    _lib = L
+    _lib = declare(C.CDLL(LIB_PATH))
+    return _lib
+
+
+def _signatures():
+    """name -> (argtypes, restype) of every exported function whose ctypes defaults (no argument check, an int back) do not fit."""
+    vp, sz, i, s = C.c_void_p, C.c_size_t, C.c_int, C.c_char_p
+    P = C.POINTER
+    ip, zp, pp = P(i), P(sz), P(vp)
+    batch = [pp, zp, pp, zp, ip]                        # src, their sizes, dest, their sizes, the results
+    one = [i, i, sz, s, sz]                             # clevel, doshuffle, typesize, compressor, blocksize
+    return {
+        # include/blosc.h
+        "blosc_compress": ([i, i, sz, sz, vp, vp, sz], i),
+        "blosc_compress_ctx": ([i, i, sz, sz, vp, vp, sz, s, sz, i], i),
+        "blosc_decompress": ([vp, vp, sz], i),
+        "blosc_decompress_ctx": ([vp, vp, sz, i], i),
+        "blosc_getitem": ([vp, i, i, vp], i),
+        "blosc_set_compressor": ([s], i),
+        "blosc_get_compressor": (None, s),
+        "blosc_list_compressors": (None, s),
+        "blosc_get_version_string": (None, s),
+        "blosc_cbuffer_complib": ([vp], s),
+        "blosc_compname_to_compcode": ([s], i),
+        "blosc_compcode_to_compname": ([i, P(s)], i),
+        "blosc_get_complib_info": ([s, P(s), P(s)], i),
+        "blosc_cbuffer_sizes": ([vp, zp, zp, zp], None),
+        "blosc_cbuffer_validate": ([vp, sz, zp], i),
+        "blosc_cbuffer_metainfo": ([vp, zp, ip], None),
+        "blosc_cbuffer_versions": ([vp, ip, ip], None),
+        "blosc_set_blocksize": ([sz], None),
+        "blosc_set_splitmode": ([i], None),
+        # include/blosc_gpu.h
+        "blosc_gpu_compress_batch": (one + [i] + batch + [vp], i),
+        "blosc_gpu_decompress_batch": ([i] + batch + [vp], i),
+        "blosc_gpu_compress_batch_host": (one + [i] + batch, i),
+        "blosc_gpu_decompress_batch_host": ([i] + batch, i),
+        "blosc_gpu_partition": ([sz, i, i, zp, zp], i),
+        "blosc_gpu_compress_batch_multi": ([i, ip] + one + [i] + batch, i),
+        "blosc_gpu_decompress_batch_multi": ([i, ip, i] + batch, i),
+        "blosc_gpu_getitem": ([vp, i, i, vp, vp], i),
+        "blosc_gpu_profile": ([i], None),
+        "blosc_gpu_profile_reset": (None, None),
+        "blosc_gpu_profile_get": ([s, P(C.c_double), ip], i),
+        # include/blosc_gpu_packed.h
+        "blosc_gpu_packed_bound": ([i, zp, sz], sz),
+        "blosc_gpu_compress_packed": (one + [i, pp, zp, vp, sz, sz, zp, ip, vp], i),
+        "blosc_gpu_decompress_packed": ([i, vp, sz, zp, vp, sz, zp, ip, vp], i),
+        "blosc_gpu_cbuffer_sizes_batch": ([i, pp, zp, zp, zp, vp], i),
+        # include/blosc_gpu_params.h
+        "blosc_gpu_compress_batch_params": ([i, P(CParams)] + batch + [vp], i),
+        "blosc_gpu_compress_packed_params": ([i, P(CParams), pp, zp, vp, sz, sz, zp, ip, vp], i),
+        # include/blosc_gpu_getitem.h
+        "blosc_gpu_getitem_batch": ([i, pp, i, ip, ip, ip, pp, ip, vp], i),
+        "blosc_gpu_getitem_packed": ([i, vp, sz, zp, i, ip, ip, ip, vp, sz, zp, ip, vp], i),
+        # include/blosc_gpu_checksum.h
+        "blosc_gpu_checksum_batch": ([i, i, pp, zp, P(C.c_uint), vp], i),
+        "blosc_gpu_checksum_packed": ([i, i, vp, sz, zp, zp, P(C.c_uint), vp], i),
+        # test hooks
+        "blosc_internal_shuffle": ([sz, sz, vp, vp], None),
+        "blosc_internal_unshuffle": ([sz, sz, vp, vp], None),
+        "blosc_internal_bitshuffle": ([sz, sz, vp, vp, vp], i),
+        "blosc_internal_bitunshuffle": ([sz, sz, vp, vp, vp], i),
+        "blosc_amd_policy_blocksize": ([i, i, i, i, i, i], i),
+        "blosc_amd_policy_split": ([i, i, i, i], i),
+        "blosc_amd_getitem_pass_bytes": ([sz], None),
+        "blosc_amd_checksum_tile_bytes": ([sz], None),
+    }
+
+
+SIGNATURES = _signatures()
+
+
+def declare(L):
+    """SIGNATURES on a library handle, for every symbol the handle has: the product in load(), the emulator build of the CPU tests, and
+    the builds of earlier rounds that A/B scripts load through this module, which lack the newer calls.  Returns the handle."""
+    for name, (argtypes, restype) in SIGNATURES.items():
+        if hasattr(L, name):
+            f = getattr(L, name)
+            if argtypes is not None:
+                f.argtypes = argtypes
+            f.restype = restype
     return L
 
 
-def declare_packed(L):
-    """argtypes of include/blosc_gpu_packed.h on a library handle (load() calls it; the CPU tests call it on their emulator build)."""
-    vp, sz, i = C.c_void_p, C.c_size_t, C.c_int
-    L.blosc_gpu_packed_bound.argtypes = [i, C.POINTER(sz), sz]
-    L.blosc_gpu_packed_bound.restype = sz
-    L.blosc_gpu_compress_packed.argtypes = [i, i, sz, C.c_char_p, sz, i, C.POINTER(vp), C.POINTER(sz), vp, sz, sz,
-                                            C.POINTER(sz), C.POINTER(i), vp]
-    L.blosc_gpu_decompress_packed.argtypes = [i, vp, sz, C.POINTER(sz), vp, sz, C.POINTER(sz), C.POINTER(i), vp]
-    L.blosc_gpu_cbuffer_sizes_batch.argtypes = [i, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), vp]
-
-
-def declare_params(L):
-    """argtypes of include/blosc_gpu_params.h on a library handle (load() calls it; the CPU tests call it on their emulator build)."""
-    vp, sz, i = C.c_void_p, C.c_size_t, C.c_int
-    L.blosc_gpu_compress_batch_params.argtypes = [i, C.POINTER(CParams), C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(i), vp]
-    L.blosc_gpu_compress_packed_params.argtypes = [i, C.POINTER(CParams), C.POINTER(vp), C.POINTER(sz), vp, sz, sz, C.POINTER(sz), C.POINTER(i), vp]
-
-
-def declare_getitem(L):
-    """argtypes of include/blosc_gpu_getitem.h on a library handle (load() calls it; the CPU tests call it on their emulator build)."""
-    vp, sz, i = C.c_void_p, C.c_size_t, C.c_int
-    ip = C.POINTER(i)
-    L.blosc_gpu_getitem_batch.argtypes = [i, C.POINTER(vp), i, ip, ip, ip, C.POINTER(vp), ip, vp]
-    L.blosc_gpu_getitem_packed.argtypes = [i, vp, sz, C.POINTER(sz), i, ip, ip, ip, vp, sz, C.POINTER(sz), ip, vp]
-    L.blosc_amd_getitem_pass_bytes.argtypes = [sz]      # (test hook)
-    L.blosc_amd_getitem_pass_bytes.restype = None
-
-
-def declare_checksum(L):
-    """argtypes of include/blosc_gpu_checksum.h on a library handle (load() calls it; the CPU tests call it on their emulator build)."""
-    vp, sz, i = C.c_void_p, C.c_size_t, C.c_int
-    L.blosc_gpu_checksum_batch.argtypes = [i, i, C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_uint), vp]
-    L.blosc_gpu_checksum_packed.argtypes = [i, i, vp, sz, C.POINTER(sz), C.POINTER(sz), C.POINTER(C.c_uint), vp]
-    L.blosc_amd_checksum_tile_bytes.argtypes = [sz]     # (test hook)
-    L.blosc_amd_checksum_tile_bytes.restype = None
+declare_packed = declare_params = declare_getitem = declare_checksum = declare      # the names from when every header had a function of its own
 
 
 # ---- numpy conveniences (host buffers through the stock entry points) --------------------------

@@ -78,78 +78,111 @@ def _ptr_array(arrs):
     return (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
 
 
+def _failed(what, rc, res):
+    return BlpkError(f"{what} failed (rc {rc}, results {list(res)[:4]}...)")
+
+
+class _Writer:
+    """The file of `pack` and `pack_device`: the header and a placeholder offset table at once, then chunk() for every chunk in order
+    (its bytes, its digest - empty for checksum 0), then close(), which writes the table back and returns (nchunks, bytes written).
+    batches() cuts the `n` plain bytes into the calls' batches: (index of the first chunk, the plain sizes of its chunks)."""
+
+    def __init__(self, fh, n, chunk_size, typesize, checksum, batch_bytes):
+        if chunk_size <= 0 or chunk_size > (1 << 31) - 17:
+            raise BlpkError("chunk_size out of range")
+        self.fh, self.n, self.chunk_size = fh, n, chunk_size
+        self.nchunks = (n + chunk_size - 1) // chunk_size if n else 0
+        self.per_batch = max(1, batch_bytes // chunk_size)
+        header = pack_header(self.nchunks, chunk_size, n - (self.nchunks - 1) * chunk_size if self.nchunks else 0, typesize, checksum)
+        self.start = fh.tell()
+        fh.write(header)
+        self.offsets, self.written = np.full(self.nchunks, -1, "<i8"), 0
+        fh.write(self.offsets.tobytes())
+
+    def batches(self):
+        for b0 in range(0, self.nchunks, self.per_batch):
+            yield b0, [min(self.n, (k + 1) * self.chunk_size) - k * self.chunk_size for k in range(b0, min(self.nchunks, b0 + self.per_batch))]
+
+    def chunk(self, data, digest):
+        self.offsets[self.written] = self.fh.tell() - self.start
+        self.written += 1
+        self.fh.write(data); self.fh.write(digest)
+
+    def close(self):
+        end = self.fh.tell()
+        self.fh.seek(self.start + HEADER_LENGTH); self.fh.write(self.offsets.tobytes()); self.fh.seek(end)
+        return self.nchunks, end - self.start
+
+
+_META_DIGEST_LENGTH = {0: 0, 1: 4, 2: 4, 3: 16, 4: 20, 5: 28, 6: 32, 7: 48, 8: 64}      # metadata section: checksum kind -> bytes of its digest
+
+
+def _read_layout(raw):
+    """Where the chunks of the file image `raw` lie: (header dict, offsets, plain sizes, compressed sizes, bytes of a chunk's digest), one
+    list entry per chunk.  A metadata section is skipped; without an offset table the chunks are found one behind the other.  Every chunk's
+    16-byte header and, with its digest, its compressed bytes lie inside the image; nothing else is promised about the offsets."""
+    h = unpack_header(raw)
+    pos = HEADER_LENGTH
+    if h["metadata"]:                                  # skip: magic_format(8) options checksum codec level meta_size max_meta_size meta_comp_size user_codec(8)
+        if len(raw) < pos + METADATA_HEADER_LENGTH:
+            raise BlpkError("truncated metadata header")
+        max_meta = struct.unpack_from("<I", raw, pos + 16)[0]
+        dlen = _META_DIGEST_LENGTH.get(raw[pos + 9])
+        if dlen is None:
+            raise BlpkError("metadata checksum kind")
+        pos += METADATA_HEADER_LENGTH + max_meta + dlen
+    nch = h["nchunks"]
+    dlen = 4 if h["checksum"] else 0
+    table = None
+    if h["offsets"]:
+        tot = nch + h["max_app_chunks"]
+        if len(raw) < pos + 8 * tot:
+            raise BlpkError("truncated offset table")
+        table = np.frombuffer(raw, "<i8", tot, pos)[:nch]
+        pos += 8 * tot
+    offs, sizes, cbytes = [], [], []
+    for k in range(nch):
+        o = int(table[k]) if table is not None else pos
+        if o < 0 or o + 16 > len(raw):
+            raise BlpkError(f"chunk {k}: offset outside the file")
+        nb, _bs, cb = struct.unpack_from("<iii", raw, o + 4)
+        if cb < 16 or o + cb + dlen > len(raw) or nb < 0:
+            raise BlpkError(f"chunk {k}: header sizes outside the file")
+        offs.append(o); sizes.append(nb); cbytes.append(cb)
+        pos = o + cb + dlen
+    return h, offs, sizes, cbytes, dlen
+
+
 def pack(lib, data, fh, chunk_size=1 << 20, typesize=8, clevel=5, shuffle=1, cname=b"lz4", checksum=1, batch_bytes=1 << 30):
     """Compress `data` (numpy, any dtype) into the open binary file `fh`.  Chunks go to the GPU `batch_bytes` at a time
     through blosc_gpu_compress_batch_host.  Returns (nchunks, bytes written)."""
     a = np.ascontiguousarray(data).view(np.uint8).ravel()
-    n = a.size
-    if chunk_size <= 0 or chunk_size > (1 << 31) - 17:
-        raise BlpkError("chunk_size out of range")
-    nchunks = (n + chunk_size - 1) // chunk_size if n else 0
-    last = n - (nchunks - 1) * chunk_size if nchunks else 0
-    start = fh.tell()
-    fh.write(pack_header(nchunks, chunk_size, last, typesize, checksum))
-    off_pos = fh.tell()
-    offsets = np.full(nchunks, -1, "<i8")
-    fh.write(offsets.tobytes())
-    per_batch = max(1, batch_bytes // chunk_size)
-    for b0 in range(0, nchunks, per_batch):
-        b1 = min(nchunks, b0 + per_batch)
-        srcs = [a[k * chunk_size:min(n, (k + 1) * chunk_size)] for k in range(b0, b1)]
-        dsts = [np.empty(s.size + 16, np.uint8) for s in srcs]
-        m = b1 - b0
-        ssz = (C.c_size_t * m)(*[s.size for s in srcs]); dsz = (C.c_size_t * m)(*[d.size for d in dsts])
+    w = _Writer(fh, a.size, chunk_size, typesize, checksum, batch_bytes)
+    for b0, sizes in w.batches():
+        m = len(sizes)
+        srcs = [a[(b0 + k) * chunk_size:(b0 + k) * chunk_size + s] for k, s in enumerate(sizes)]
+        dsts = [np.empty(s + 16, np.uint8) for s in sizes]
         res = (C.c_int * m)()
-        rc = lib.blosc_gpu_compress_batch_host(clevel, shuffle, typesize, cname, 0, m, _ptr_array(srcs), ssz, _ptr_array(dsts), dsz, res)
+        rc = lib.blosc_gpu_compress_batch_host(clevel, shuffle, typesize, cname, 0, m, _ptr_array(srcs), (C.c_size_t * m)(*sizes), _ptr_array(dsts),
+                                               (C.c_size_t * m)(*[d.size for d in dsts]), res)
         if rc != 0 or any(r <= 0 for r in res):
-            raise BlpkError(f"compression failed (rc {rc}, results {list(res)[:4]}...)")
-        for k, (d, r) in enumerate(zip(dsts, res)):
-            offsets[b0 + k] = fh.tell() - start
+            raise _failed("compression", rc, res)
+        for d, r in zip(dsts, res):
             chunk = d[:r].tobytes()
-            fh.write(chunk); fh.write(_digest(checksum, chunk))
-    end = fh.tell()
-    fh.seek(off_pos); fh.write(offsets.tobytes()); fh.seek(end)
-    return nchunks, end - start
+            w.chunk(chunk, _digest(checksum, chunk))
+    return w.close()
 
 
 def unpack(lib, fh, batch_bytes=1 << 30, verify=True):
     """Read a bloscpack file from the open binary file `fh`; returns the plain bytes as a numpy uint8 array.  Chunks go to the
     GPU `batch_bytes` at a time through blosc_gpu_decompress_batch_host."""
     blob = fh.read()
-    h = unpack_header(blob)
-    pos = HEADER_LENGTH
-    if h["metadata"]:                                  # skip: magic_format(8) options checksum codec level meta_size max_meta_size meta_comp_size user_codec(8)
-        if len(blob) < pos + METADATA_HEADER_LENGTH:
-            raise BlpkError("truncated metadata header")
-        meta_checksum = blob[pos + 9]
-        max_meta = struct.unpack("<I", blob[pos + 16:pos + 20])[0]
-        dlen = {0: 0, 1: 4, 2: 4, 3: 16, 4: 20, 5: 28, 6: 32, 7: 48, 8: 64}.get(meta_checksum)
-        if dlen is None:
-            raise BlpkError("metadata checksum kind")
-        pos += METADATA_HEADER_LENGTH + max_meta + dlen
-    nch = h["nchunks"]
-    dlen = 4 if h["checksum"] else 0
-    if h["offsets"]:
-        tot = nch + h["max_app_chunks"]
-        if len(blob) < pos + 8 * tot:
-            raise BlpkError("truncated offset table")
-        offs = np.frombuffer(blob, "<i8", tot, pos)[:nch].astype(np.int64)
-        pos += 8 * tot
-    else:
-        offs = None
-    chunks = []; sizes = []
-    for k in range(nch):
-        o = int(offs[k]) if offs is not None else pos
-        if o < 0 or o + 16 > len(blob):
-            raise BlpkError(f"chunk {k}: offset outside the file")
-        nbytes, _bs, cbytes = struct.unpack("<iii", blob[o + 4:o + 16])
-        if cbytes < 16 or o + cbytes + dlen > len(blob) or nbytes < 0:
-            raise BlpkError(f"chunk {k}: header sizes outside the file")
-        c = np.frombuffer(blob, np.uint8, cbytes, o)
-        if verify and dlen and _digest(h["checksum"], c.tobytes()) != blob[o + cbytes:o + cbytes + dlen]:
+    h, offs, sizes, cbytes, dlen = _read_layout(blob)
+    nch = len(offs)
+    chunks = [np.frombuffer(blob, np.uint8, cb, o) for o, cb in zip(offs, cbytes)]
+    for k, (c, o) in enumerate(zip(chunks, offs)):
+        if verify and dlen and _digest(h["checksum"], c.tobytes()) != blob[o + c.size:o + c.size + dlen]:
             raise BlpkError(f"chunk {k}: checksum mismatch")
-        chunks.append(c); sizes.append(nbytes)
-        pos = o + cbytes + dlen
     total = int(sum(sizes))
     out = np.empty(total, np.uint8)
     starts = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
@@ -165,7 +198,7 @@ def unpack(lib, fh, batch_bytes=1 << 30, verify=True):
         res = (C.c_int * m)()
         rc = lib.blosc_gpu_decompress_batch_host(m, _ptr_array(srcs), ssz, _ptr_array(dsts), dsz, res)
         if rc != 0 or any(r != d.size for r, d in zip(res, dsts)):
-            raise BlpkError(f"decompression failed (rc {rc}, results {list(res)[:4]}...)")
+            raise _failed("decompression", rc, res)
         k0 = k1
     return out
 
@@ -210,35 +243,21 @@ def pack_device(lib, src_ptr, nbytes, fh, chunk_size=1 << 20, typesize=8, clevel
     bytes and settings.  Per `batch_bytes` of source: blosc_gpu_compress_packed (align 1) into one device container,
     blosc_gpu_checksum_packed over its chunks, ONE device-to-host copy of the used bytes, and the chunks and digests written from that
     buffer.  Returns (nchunks, bytes written)."""
-    if not 0 <= checksum < len(CHECKSUMS):
-        raise BlpkError("unknown checksum")
-    if chunk_size <= 0 or chunk_size > (1 << 31) - 17:
-        raise BlpkError("chunk_size out of range")
+    w = _Writer(fh, int(nbytes), chunk_size, typesize, checksum, batch_bytes)
     mem = mem if mem is not None else TorchMem()
-    n = int(nbytes)
-    nchunks = (n + chunk_size - 1) // chunk_size if n else 0
-    last = n - (nchunks - 1) * chunk_size if nchunks else 0
-    start = fh.tell()
-    fh.write(pack_header(nchunks, chunk_size, last, typesize, checksum))
-    off_pos = fh.tell()
-    offsets = np.full(nchunks, -1, "<i8")
-    fh.write(offsets.tobytes())
-    per_batch = max(1, batch_bytes // chunk_size)
     cont = keep = None; room = 0
-    for b0 in range(0, nchunks, per_batch):
-        b1 = min(nchunks, b0 + per_batch)
-        m = b1 - b0
-        sizes = [min(n, (k + 1) * chunk_size) - k * chunk_size for k in range(b0, b1)]
+    for b0, sizes in w.batches():
+        m = len(sizes)
         ssz = (C.c_size_t * m)(*sizes)
         bound = lib.blosc_gpu_packed_bound(m, ssz, 1)
         if cont is None or bound > room:
             keep = None                                  # (the first batch is the largest: this runs once)
             cont, keep = mem.alloc(bound); room = bound
         off = (C.c_size_t * (m + 1))(); res = (C.c_int * m)()
-        srcs = (C.c_void_p * m)(*[src_ptr + k * chunk_size for k in range(b0, b1)])
+        srcs = (C.c_void_p * m)(*[src_ptr + k * chunk_size for k in range(b0, b0 + m)])
         rc = lib.blosc_gpu_compress_packed(clevel, shuffle, typesize, cname, 0, m, srcs, ssz, cont, room, 1, off, res, None)
         if rc != 0 or any(r <= 0 for r in res):
-            raise BlpkError(f"compression failed (rc {rc}, results {list(res)[:4]}...)")
+            raise _failed("compression", rc, res)
         dig = (C.c_uint * m)()
         if checksum:
             rc = lib.blosc_gpu_checksum_packed(checksum, m, cont, room, off, (C.c_size_t * m)(*res), dig, None)
@@ -248,13 +267,8 @@ def pack_device(lib, src_ptr, nbytes, fh, chunk_size=1 << 20, typesize=8, clevel
         body = memoryview(np.ascontiguousarray(mem.to_host(cont, used)))
         digests = memoryview(np.asarray(dig, dtype="<u4").view(np.uint8))
         for k in range(m):
-            offsets[b0 + k] = fh.tell() - start
-            fh.write(body[off[k]:off[k] + res[k]])
-            if checksum:
-                fh.write(digests[4 * k:4 * k + 4])
-    end = fh.tell()
-    fh.seek(off_pos); fh.write(offsets.tobytes()); fh.seek(end)
-    return nchunks, end - start
+            w.chunk(body[off[k]:off[k] + res[k]], digests[4 * k:4 * k + 4] if checksum else b"")
+    return w.close()
 
 
 def unpack_device(lib, fh, dest_ptr=None, destsize=0, verify=True, mem=None):
@@ -264,36 +278,16 @@ def unpack_device(lib, fh, dest_ptr=None, destsize=0, verify=True, mem=None):
     image - a chunk's span to the next one is its bytes plus the digest, which that call takes as padding.  Header, table and chunk
     headers get `unpack`'s checks.  A file without an offset table, or whose table does not rise strictly, is `unpack`'s."""
     raw = fh.read()
-    h = unpack_header(raw)
-    pos = HEADER_LENGTH
-    if h["metadata"]:
-        if len(raw) < pos + METADATA_HEADER_LENGTH:
-            raise BlpkError("truncated metadata header")
-        max_meta = struct.unpack("<I", raw[pos + 16:pos + 20])[0]
-        dlen = {0: 0, 1: 4, 2: 4, 3: 16, 4: 20, 5: 28, 6: 32, 7: 48, 8: 64}.get(raw[pos + 9])
-        if dlen is None:
-            raise BlpkError("metadata checksum kind")
-        pos += METADATA_HEADER_LENGTH + max_meta + dlen
-    nch = h["nchunks"]
-    dlen = 4 if h["checksum"] else 0
+    h, offs, sizes, cbytes, dlen = _read_layout(raw)
+    nch = len(offs)
+    # what this path refuses on top: the image is decoded as ONE packed container, whose table rises and whose chunks do not overlap
     if not h["offsets"]:
         raise BlpkError("no offset table: not a file for unpack_device, use unpack")
-    tot = nch + h["max_app_chunks"]
-    if len(raw) < pos + 8 * tot:
-        raise BlpkError("truncated offset table")
-    offs = [int(o) for o in np.frombuffer(raw, "<i8", tot, pos)[:nch]]
-    sizes = []; cbytes = []
-    for k, o in enumerate(offs):
-        if o < 0 or o + 16 > len(raw):
-            raise BlpkError(f"chunk {k}: offset outside the file")
-        nb, _bs, cb = struct.unpack_from("<iii", raw, o + 4)
-        if cb < 16 or o + cb + dlen > len(raw) or nb < 0:
-            raise BlpkError(f"chunk {k}: header sizes outside the file")
-        if k and o <= offs[k - 1]:
+    for k in range(1, nch):
+        if offs[k] <= offs[k - 1]:
             raise BlpkError(f"chunk {k}: the offset table does not rise: not a file for unpack_device, use unpack")
-        if k and offs[k - 1] + cbytes[-1] + dlen > o:
+        if offs[k - 1] + cbytes[k - 1] + dlen > offs[k]:
             raise BlpkError(f"chunk {k - 1}: runs into chunk {k}")
-        sizes.append(nb); cbytes.append(cb)
     total = int(sum(sizes))
     if dest_ptr is None:
         return total
@@ -315,7 +309,7 @@ def unpack_device(lib, fh, dest_ptr=None, destsize=0, verify=True, mem=None):
     doff = (C.c_size_t * (nch + 1))(); res = (C.c_int * nch)()
     rc = lib.blosc_gpu_decompress_packed(nch, image, len(raw), table, dest_ptr, destsize, doff, res, None)
     if rc != 0 or any(r != s for r, s in zip(res, sizes)):
-        raise BlpkError(f"decompression failed (rc {rc}, results {list(res)[:4]}...)")
+        raise _failed("decompression", rc, res)
     del keep
     return total
 

@@ -1,4 +1,5 @@
-// blosc_api.hip — the exported C ABI (include/blosc.h, include/blosc_gpu.h, include/blosc_gpu_packed.h, include/blosc_gpu_params.h).
+// blosc_api.hip — the exported C ABI (include/blosc.h, include/blosc_gpu.h, include/blosc_gpu_packed.h, include/blosc_gpu_params.h,
+// include/blosc_gpu_getitem.h, include/blosc_gpu_checksum.h).
 //
 // Host-side mirror of the reference's public layer (blosc/blosc.c:1282-1703, :1951-2317):
 // process globals, the per-call environment overrides, name/code tables and cbuffer introspection
@@ -9,6 +10,9 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+
+#include <memory>
+#include <new>
 
 #include "../../include/blosc.h"
 #include "../../include/blosc_gpu.h"
@@ -32,6 +36,130 @@ static int g_splitmode = BLOSC_FORWARD_COMPAT_SPLIT;
 static const char* const kNames[6] = {BLOSC_BLOSCLZ_COMPNAME, BLOSC_LZ4_COMPNAME, BLOSC_LZ4HC_COMPNAME,
                                       BLOSC_SNAPPY_COMPNAME, BLOSC_ZLIB_COMPNAME, BLOSC_ZSTD_COMPNAME};
 static bool codec_built(int code) { return code == BLOSC_BLOSCLZ || code == BLOSC_LZ4 || code == BLOSC_LZ4HC || code == BLOSC_ZLIB || code == BLOSC_ZSTD; }
+
+// ---- marshalling of the batched extension: from the caller's arrays to the engine's tables --------------
+// Whole-call checks by family.  A call that fails one answers -1 and writes nothing; tests/test_abi_arguments.py pins every line.
+//   *_batch, *_batch_host, *_batch_multi   n <= 0 answers 0.  The arrays are the caller's word (include/blosc_gpu.h), only `srcsize` may be NULL.
+//   compress_batch_params                   n <= 0 answers 0, then every array must be there.
+//   the packed calls                        packed_opening(): n < 0 or no table to write is unusable, n == 0 writes an empty table and answers 0;
+//                                           then every array must be there.  `dest` may be NULL: the compress calls size (destsize must be 0
+//                                           then), the reading calls size whatever destsize says.
+//   getitem_batch                           a negative count is unusable, nranges == 0 answers 0, then every array (`src` when there are chunks).
+//   checksum_*                              checksum_opening(): `kind` first, then nruns <= 0 answers 0; then the arrays (`length` may be NULL,
+//                                           the container where every run is empty).
+//   cbuffer_sizes_batch                     n < 0 is unusable, n == 0 answers 0, then `src`; every output may be NULL.
+static const int kGo = 1;      // what a checks function answers for "go on"; anything else is the call's answer
+
+// a call's temporary table, freed on every path; null: the allocation failed, the call answers -1
+template <class T> using Table = std::unique_ptr<T[]>;
+template <class T> static Table<T> table(int n) { return Table<T>(new (std::nothrow) T[(size_t)(n > 0 ? n : 1)]); }
+
+// chunks given as parallel arrays; dest / insize / outsize NULL: no destination / 0
+static Table<Job> jobs_from_arrays(int n, const void* const* src, void* const* dest, const size_t* insize, const size_t* outsize) {
+  Table<Job> jobs = table<Job>(n);
+  for (int i = 0; jobs && i < n; i++) jobs[i] = Job{src[i], dest ? dest[i] : nullptr, insize ? insize[i] : 0, outsize ? outsize[i] : 0};
+  return jobs;
+}
+
+// Chunks (or runs) given as spans of one container: item i is what lies between offsets[i] and offsets[i + 1], all it may claim.  The table must
+// rise and end inside the container, else the whole call is unusable (null is returned, as for a failed allocation: both answer -1).
+//   length     (checksum) item i is the first length[i] bytes of its span; one that is longer than its span makes the call unusable.  NULL: the span
+//   min_span   (chunks: BLOSC_MIN_HEADER_LENGTH) the engine reads srcsize 0 as "trust the header", so a span that cannot hold a header (an empty one
+//              too) is passed as 1 byte, which it rejects without reading it.  0 (checksum): an empty run is a run
+static Table<Job> jobs_from_spans(int n, const void* container, size_t containersize, const size_t* offsets, const size_t* length, size_t min_span) {
+  for (int i = 0; i < n; i++)
+    if (offsets[i + 1] < offsets[i] || (length && length[i] > offsets[i + 1] - offsets[i])) return nullptr;
+  if (n > 0 && offsets[n] > containersize) return nullptr;
+  Table<Job> jobs = table<Job>(n);
+  for (int i = 0; jobs && i < n; i++) {
+    const size_t size = length ? length[i] : offsets[i + 1] - offsets[i];
+    jobs[i] = Job{(const void*)((uintptr_t)container + offsets[i]), nullptr, size < min_span ? 1 : size, 0};
+  }
+  return jobs;
+}
+
+// (clevel, doshuffle, typesize, compressor, blocksize) of a call with one parameter set, and the globals behind their defaults, as the engine's
+// parameter set; false: the codec is not built (a name nobody knows too).  chunk_params() is the per-chunk counterpart
+static bool call_params(int clevel, int doshuffle, size_t typesize, const char* compressor, size_t blocksize, CompressParams* p) {
+  const int code = compressor ? blosc_compname_to_compcode(compressor) : g_compressor;
+  if (code < 0 || !codec_built(code)) return false;
+  *p = CompressParams{clevel, doshuffle, typesize, code, (int32_t)(blocksize ? blocksize : (size_t)g_force_blocksize), g_splitmode};
+  return true;
+}
+// ... and what a call answers whose one parameter set names such a codec: every chunk -5, and none of them takes room
+static int answer_not_built(int n, int* results, size_t* offsets_out) {
+  for (int i = 0; i < n; i++) results[i] = -5;
+  for (int i = 0; offsets_out && i <= n; i++) offsets_out[i] = 0;
+  return 0;
+}
+// The engine checks every chunk's parameters by itself, in the reference's order (sizes, then parameters: -10, then the codec: -5), so an
+// unusable row of include/blosc_gpu_params.h is the outcome of its chunk alone.
+static Table<CompressParams> chunk_params(int nchunks, const blosc_gpu_cparams* params) {
+  Table<CompressParams> p = table<CompressParams>(nchunks);
+  for (int i = 0; p && i < nchunks; i++) {
+    const blosc_gpu_cparams& c = params[i];
+    p[i] = CompressParams{c.clevel, c.doshuffle, c.typesize, c.compcode == -1 ? g_compressor : c.compcode,
+                          (int32_t)(c.blocksize ? c.blocksize : (size_t)g_force_blocksize), c.splitmode ? c.splitmode : g_splitmode};
+    // a code outside 0 ... 5 is "not built" like Snappy (the engine's tables are indexed by the codes it knows)
+    if (p[i].codec < 0 || p[i].codec > 5) p[i].codec = BLOSC_SNAPPY;
+    // a split mode that does not exist is a parameter error of its chunk: handed on as a filter the engine's parameter check rejects
+    // (the global mode of the single-parameter calls is never checked - as in the reference - so the check cannot live there)
+    if (c.splitmode < 0 || c.splitmode > BLOSC_FORWARD_COMPAT_SPLIT) p[i].doshuffle = -1;
+  }
+  return p;
+}
+
+// The one road of the six compress entry points, of the four decompress and of the two getitem ones: a table that could not be made answers -1.
+// (The callers make their tables in the argument list: such a temporary lives until the call has returned.)
+// packed: every chunk's own limit is the size at which blosc_compress_ctx cannot answer 0; where it goes is the engine's layout step
+static int compress_call(const CompressParams* params, bool per_chunk, int n, const Table<Job>& jobs, int* results, bool device_ptrs, void* stream,
+                         const PackedBuffer* packed) {
+  if (!params || !jobs) return -1;
+  for (int i = 0; packed && i < n; i++) jobs[i].dstsize = jobs[i].srcsize + BLOSC_MAX_OVERHEAD;
+  return engine_compress_batch(params, per_chunk, n, jobs.get(), results, device_ptrs, (hipStream_t)stream, packed);
+}
+static int decompress_call(int n, const Table<Job>& jobs, int* results, bool device_ptrs, void* stream, const PackedBuffer* packed) {
+  return jobs ? engine_decompress_batch(n, jobs.get(), results, device_ptrs, (hipStream_t)stream, packed) : -1;
+}
+static int getitem_call(int nchunks, const Table<Job>& jobs, int nranges, const int* chunk, const int* start, const int* nitems, void* const* dest,
+                        int* results, void* stream, const PackedBuffer* packed) {
+  Table<ItemRange> ranges = table<ItemRange>(nranges);
+  if (!jobs || !ranges) return -1;
+  for (int i = 0; i < nranges; i++) ranges[i] = ItemRange{chunk[i], start[i], nitems[i], dest ? dest[i] : nullptr};
+  return engine_getitem_batch(nchunks, jobs.get(), nranges, ranges.get(), results, (hipStream_t)stream, packed);
+}
+
+// how every packed call opens
+static int packed_opening(int n, size_t* offsets_out) {
+  if (n < 0 || !offsets_out) return -1;
+  if (n == 0) { offsets_out[0] = 0; return 0; }
+  return kGo;
+}
+static bool packed_align(size_t* align) {      // 0 means 1; a power of two up to 4096
+  if (*align == 0) *align = 1;
+  return *align <= 4096 && (*align & (*align - 1)) == 0;
+}
+// ... and the rest of what the two packed compress calls check (the alignment before the count: an empty batch with a bad one is unusable)
+static int packed_compress_opening(int n, const void* const* src, const size_t* nbytes, void* dest, size_t destsize, size_t* align, size_t* offsets_out,
+                                   int* cbytes_out) {
+  if (!packed_align(align)) return -1;
+  const int c = packed_opening(n, offsets_out);
+  if (c != kGo) return c;
+  return (!src || !nbytes || !cbytes_out || (!dest && destsize)) ? -1 : kGo;
+}
+
+// how both checksum calls open (`kind` before the count), and how they end
+static int checksum_opening(int kind, int nruns) {
+  if (kind != BLOSC_GPU_CHECKSUM_ADLER32 && kind != BLOSC_GPU_CHECKSUM_CRC32) return -1;
+  return nruns <= 0 ? 0 : kGo;
+}
+static const size_t kChecksumMaxRun = (size_t)INT32_MAX + 16;      // beyond the largest chunk
+static int checksum_call(int kind, int nruns, const Table<Job>& jobs, unsigned int* digest_out, void* stream) {
+  if (!jobs) return -1;
+  for (int i = 0; i < nruns; i++)
+    if (jobs[i].srcsize > kChecksumMaxRun || (jobs[i].srcsize != 0 && !jobs[i].src)) return -1;
+  return engine_checksum_batch(kind, nruns, jobs.get(), digest_out, (hipStream_t)stream);
+}
 
 extern "C" {
 
@@ -256,15 +384,9 @@ static int compress_batch(int clevel, int doshuffle, size_t typesize, const char
                           int nchunks, const void* const* src, const size_t* nbytes, void* const* dest,
                           const size_t* destsize, int* cbytes_out, void* stream, bool device_ptrs) {
   if (nchunks <= 0) return 0;
-  const int code = compressor ? blosc_compname_to_compcode(compressor) : g_compressor;
-  if (code < 0 || !codec_built(code)) { for (int i = 0; i < nchunks; i++) cbytes_out[i] = -5; return 0; }
-  Job* jobs = (Job*)malloc(sizeof(Job) * (size_t)nchunks);
-  if (!jobs) return -1;
-  for (int i = 0; i < nchunks; i++) jobs[i] = Job{src[i], dest[i], nbytes[i], destsize[i]};
-  CompressParams p{clevel, doshuffle, typesize, code, (int32_t)(blocksize ? blocksize : (size_t)g_force_blocksize), g_splitmode};
-  int r = engine_compress_batch(&p, false, nchunks, jobs, cbytes_out, device_ptrs, (hipStream_t)stream);
-  free(jobs);
-  return r;
+  CompressParams p;
+  if (!call_params(clevel, doshuffle, typesize, compressor, blocksize, &p)) return answer_not_built(nchunks, cbytes_out, nullptr);
+  return compress_call(&p, false, nchunks, jobs_from_arrays(nchunks, src, dest, nbytes, destsize), cbytes_out, device_ptrs, stream, nullptr);
 }
 int blosc_gpu_compress_batch(int clevel, int doshuffle, size_t typesize, const char* compressor, size_t blocksize,
                              int nchunks, const void* const* src, const size_t* nbytes, void* const* dest,
@@ -281,12 +403,7 @@ int blosc_gpu_compress_batch_host(int clevel, int doshuffle, size_t typesize, co
 static int decompress_batch(int nchunks, const void* const* src, const size_t* srcsize, void* const* dest,
                             const size_t* destsize, int* nbytes_out, void* stream, bool device_ptrs) {
   if (nchunks <= 0) return 0;
-  Job* jobs = (Job*)malloc(sizeof(Job) * (size_t)nchunks);
-  if (!jobs) return -1;
-  for (int i = 0; i < nchunks; i++) jobs[i] = Job{src[i], dest[i], srcsize ? srcsize[i] : 0, destsize[i]};
-  int r = engine_decompress_batch(nchunks, jobs, nbytes_out, device_ptrs, (hipStream_t)stream);
-  free(jobs);
-  return r;
+  return decompress_call(nchunks, jobs_from_arrays(nchunks, src, dest, srcsize, destsize), nbytes_out, device_ptrs, stream, nullptr);
 }
 int blosc_gpu_decompress_batch(int nchunks, const void* const* src, const size_t* srcsize, void* const* dest,
                                const size_t* destsize, int* nbytes_out, void* stream) {
@@ -298,10 +415,6 @@ int blosc_gpu_decompress_batch_host(int nchunks, const void* const* src, const s
 }
 
 // ---- the batch in one device buffer (include/blosc_gpu_packed.h) ---------------------------------------
-static bool packed_align(size_t* align) {      // 0 means 1; a power of two up to 4096
-  if (*align == 0) *align = 1;
-  return *align <= 4096 && (*align & (*align - 1)) == 0;
-}
 size_t blosc_gpu_packed_bound(int nchunks, const size_t* nbytes, size_t align) {
   if (nchunks <= 0 || !nbytes || !packed_align(&align)) return 0;
   size_t total = 0;
@@ -312,108 +425,53 @@ size_t blosc_gpu_packed_bound(int nchunks, const size_t* nbytes, size_t align) {
 int blosc_gpu_compress_packed(int clevel, int doshuffle, size_t typesize, const char* compressor, size_t blocksize,
                               int nchunks, const void* const* src, const size_t* nbytes, void* dest, size_t destsize, size_t align,
                               size_t* offsets_out, int* cbytes_out, void* stream) {
-  if (nchunks < 0 || !offsets_out || !packed_align(&align)) return -1;
-  if (nchunks == 0) { offsets_out[0] = 0; return 0; }
-  if (!src || !nbytes || !cbytes_out || (!dest && destsize)) return -1;
-  const int code = compressor ? blosc_compname_to_compcode(compressor) : g_compressor;
-  if (code < 0 || !codec_built(code)) {      // as blosc_gpu_compress_batch answers: every chunk -5, and none of them takes room
-    for (int i = 0; i < nchunks; i++) { cbytes_out[i] = -5; offsets_out[i] = 0; }
-    offsets_out[nchunks] = 0;
-    return 0;
-  }
-  Job* jobs = (Job*)malloc(sizeof(Job) * (size_t)nchunks);
-  if (!jobs) return -1;
-  // every chunk's own limit is the size at which blosc_compress_ctx cannot answer 0; where it goes is the engine's layout step
-  for (int i = 0; i < nchunks; i++) jobs[i] = Job{src[i], nullptr, nbytes[i], nbytes[i] + BLOSC_MAX_OVERHEAD};
-  CompressParams p{clevel, doshuffle, typesize, code, (int32_t)(blocksize ? blocksize : (size_t)g_force_blocksize), g_splitmode};
+  const int c = packed_compress_opening(nchunks, src, nbytes, dest, destsize, &align, offsets_out, cbytes_out);
+  if (c != kGo) return c;
+  CompressParams p;
+  if (!call_params(clevel, doshuffle, typesize, compressor, blocksize, &p)) return answer_not_built(nchunks, cbytes_out, offsets_out);
   const PackedBuffer pk{dest, destsize, align, offsets_out};
-  int r = engine_compress_batch(&p, false, nchunks, jobs, cbytes_out, true, (hipStream_t)stream, &pk);
-  free(jobs);
-  return r;
+  return compress_call(&p, false, nchunks, jobs_from_arrays(nchunks, src, nullptr, nbytes, nullptr), cbytes_out, true, stream, &pk);
 }
 
-// ---- parameters per chunk (include/blosc_gpu_params.h) ---------------------------------------
-// The two calls above with a parameter set per chunk.  The engine checks every chunk's parameters by itself, in the reference's order
-// (sizes, then parameters: -10, then the codec: -5), so an unusable slot is the outcome of its chunk alone.
-static CompressParams* chunk_params(int nchunks, const blosc_gpu_cparams* params) {
-  CompressParams* p = (CompressParams*)malloc(sizeof(CompressParams) * (size_t)nchunks);
-  for (int i = 0; p && i < nchunks; i++) {
-    const blosc_gpu_cparams& c = params[i];
-    p[i] = CompressParams{c.clevel, c.doshuffle, c.typesize, c.compcode == -1 ? g_compressor : c.compcode,
-                          (int32_t)(c.blocksize ? c.blocksize : (size_t)g_force_blocksize), c.splitmode ? c.splitmode : g_splitmode};
-    // a code outside 0 ... 5 is "not built" like Snappy (the engine's tables are indexed by the codes it knows)
-    if (p[i].codec < 0 || p[i].codec > 5) p[i].codec = BLOSC_SNAPPY;
-    // a split mode that does not exist is a parameter error of its chunk: handed on as a filter the engine's parameter check rejects
-    // (the global mode of the single-parameter calls is never checked - as in the reference - so the check cannot live there)
-    if (c.splitmode < 0 || c.splitmode > BLOSC_FORWARD_COMPAT_SPLIT) p[i].doshuffle = -1;
-  }
-  return p;
-}
+// ---- parameters per chunk (include/blosc_gpu_params.h): the two calls above with chunk_params() ---------------------------------------
 int blosc_gpu_compress_batch_params(int nchunks, const blosc_gpu_cparams* params, const void* const* src, const size_t* nbytes,
                                     void* const* dest, const size_t* destsize, int* cbytes_out, void* stream) {
   if (nchunks <= 0) return 0;
   if (!params || !src || !nbytes || !dest || !destsize || !cbytes_out) return -1;
-  Job* jobs = (Job*)malloc(sizeof(Job) * (size_t)nchunks);
-  CompressParams* p = chunk_params(nchunks, params);
-  int r = -1;
-  if (jobs && p) {
-    for (int i = 0; i < nchunks; i++) jobs[i] = Job{src[i], dest[i], nbytes[i], destsize[i]};
-    r = engine_compress_batch(p, true, nchunks, jobs, cbytes_out, true, (hipStream_t)stream);
-  }
-  free(jobs); free(p);
-  return r;
+  return compress_call(chunk_params(nchunks, params).get(), true, nchunks, jobs_from_arrays(nchunks, src, dest, nbytes, destsize), cbytes_out, true, stream,
+                       nullptr);
 }
 int blosc_gpu_compress_packed_params(int nchunks, const blosc_gpu_cparams* params, const void* const* src, const size_t* nbytes,
                                      void* dest, size_t destsize, size_t align, size_t* offsets_out, int* cbytes_out, void* stream) {
-  if (nchunks < 0 || !offsets_out || !packed_align(&align)) return -1;
-  if (nchunks == 0) { offsets_out[0] = 0; return 0; }
-  if (!params || !src || !nbytes || !cbytes_out || (!dest && destsize)) return -1;
-  Job* jobs = (Job*)malloc(sizeof(Job) * (size_t)nchunks);
-  CompressParams* p = chunk_params(nchunks, params);
-  int r = -1;
-  if (jobs && p) {
-    for (int i = 0; i < nchunks; i++) jobs[i] = Job{src[i], nullptr, nbytes[i], nbytes[i] + BLOSC_MAX_OVERHEAD};      // (as blosc_gpu_compress_packed)
-    const PackedBuffer pk{dest, destsize, align, offsets_out};
-    r = engine_compress_batch(p, true, nchunks, jobs, cbytes_out, true, (hipStream_t)stream, &pk);
-  }
-  free(jobs); free(p);
-  return r;
+  const int c = packed_compress_opening(nchunks, src, nbytes, dest, destsize, &align, offsets_out, cbytes_out);
+  if (c != kGo) return c;
+  if (!params) return -1;
+  const PackedBuffer pk{dest, destsize, align, offsets_out};
+  return compress_call(chunk_params(nchunks, params).get(), true, nchunks, jobs_from_arrays(nchunks, src, nullptr, nbytes, nullptr), cbytes_out, true, stream,
+                       &pk);
 }
 
 int blosc_gpu_decompress_packed(int nchunks, const void* container, size_t containersize, const size_t* offsets,
                                 void* dest, size_t destsize, size_t* dest_offsets_out, int* nbytes_out, void* stream) {
-  if (nchunks < 0 || !dest_offsets_out) return -1;
-  if (nchunks == 0) { dest_offsets_out[0] = 0; return 0; }
+  const int c = packed_opening(nchunks, dest_offsets_out);
+  if (c != kGo) return c;
   if (!container || !offsets || !nbytes_out) return -1;
-  for (int i = 0; i < nchunks; i++) if (offsets[i + 1] < offsets[i]) return -1;
-  if (offsets[nchunks] > containersize) return -1;
-  Job* jobs = (Job*)malloc(sizeof(Job) * (size_t)nchunks);
-  if (!jobs) return -1;
-  for (int i = 0; i < nchunks; i++) {
-    // what lies between two offsets is all a chunk may claim.  The engine reads srcsize 0 as "trust the header": a slot that cannot hold a
-    // header (an empty one too) is passed as 1 byte, which it rejects without reading it
-    const size_t span = offsets[i + 1] - offsets[i];
-    jobs[i] = Job{(const uint8_t*)container + offsets[i], nullptr, span < (size_t)BLOSC_MIN_HEADER_LENGTH ? 1 : span, 0};
-  }
   const PackedBuffer pk{dest, dest ? destsize : 0, 0, dest_offsets_out};
-  int r = engine_decompress_batch(nchunks, jobs, nbytes_out, true, (hipStream_t)stream, &pk);
-  free(jobs);
-  return r;
+  return decompress_call(nchunks, jobs_from_spans(nchunks, container, containersize, offsets, nullptr, BLOSC_MIN_HEADER_LENGTH), nbytes_out, true, stream, &pk);
 }
 
 int blosc_gpu_cbuffer_sizes_batch(int nchunks, const void* const* src, size_t* nbytes, size_t* cbytes, size_t* blocksize, void* stream) {
   if (nchunks < 0 || (nchunks > 0 && !src)) return -1;
   if (nchunks == 0) return 0;
-  Header* h = (Header*)malloc(sizeof(Header) * (size_t)nchunks);
+  Table<Header> h = table<Header>(nchunks);
   if (!h) return -1;
-  const int r = engine_chunk_headers(nchunks, src, h, (hipStream_t)stream);
+  const int r = engine_chunk_headers(nchunks, src, h.get(), (hipStream_t)stream);
   for (int i = 0; r == 0 && i < nchunks; i++) {
     const bool known = h[i].version == BLOSC_VERSION_FORMAT;      // blosc_cbuffer_sizes: zeros for another format version (blosc.c:2117-2123)
     if (nbytes) nbytes[i] = known ? (size_t)h[i].nbytes : 0;
     if (cbytes) cbytes[i] = known ? (size_t)h[i].cbytes : 0;
     if (blocksize) blocksize[i] = known ? (size_t)h[i].blocksize : 0;
   }
-  free(h);
   return r;
 }
 
@@ -483,82 +541,39 @@ int blosc_gpu_getitem(const void* src, int start, int nitems, void* dest, void* 
 }
 
 // ---- many item ranges in one call (include/blosc_gpu_getitem.h) ---------------------------------------
-static ItemRange* item_ranges(int nranges, const int* chunk, const int* start, const int* nitems, void* const* dest) {
-  ItemRange* r = (ItemRange*)malloc(sizeof(ItemRange) * (size_t)(nranges > 0 ? nranges : 1));
-  for (int i = 0; r && i < nranges; i++) r[i] = ItemRange{chunk[i], start[i], nitems[i], dest ? dest[i] : nullptr};
-  return r;
-}
 int blosc_gpu_getitem_batch(int nchunks, const void* const* src, int nranges, const int* chunk, const int* start, const int* nitems,
                             void* const* dest, int* result_out, void* stream) {
   if (nchunks < 0 || nranges < 0) return -1;
   if (nranges == 0) return 0;
   if ((nchunks > 0 && !src) || !chunk || !start || !nitems || !dest || !result_out) return -1;
-  Job* jobs = (Job*)malloc(sizeof(Job) * (size_t)(nchunks > 0 ? nchunks : 1));
-  ItemRange* ranges = item_ranges(nranges, chunk, start, nitems, dest);
-  int r = -1;
-  if (jobs && ranges) {
-    for (int i = 0; i < nchunks; i++) jobs[i] = Job{src[i], nullptr, 0, 0};
-    r = engine_getitem_batch(nchunks, jobs, nranges, ranges, result_out, (hipStream_t)stream);
-  }
-  free(jobs); free(ranges);
-  return r;
+  return getitem_call(nchunks, jobs_from_arrays(nchunks, src, nullptr, nullptr, nullptr), nranges, chunk, start, nitems, dest, result_out, stream, nullptr);
 }
 int blosc_gpu_getitem_packed(int nchunks, const void* container, size_t containersize, const size_t* offsets,
                              int nranges, const int* chunk, const int* start, const int* nitems,
                              void* dest, size_t destsize, size_t* dest_offsets_out, int* result_out, void* stream) {
-  if (nchunks < 0 || nranges < 0 || !dest_offsets_out) return -1;
-  if (nranges == 0) { dest_offsets_out[0] = 0; return 0; }
+  if (nchunks < 0) return -1;
+  const int c = packed_opening(nranges, dest_offsets_out);
+  if (c != kGo) return c;
   if ((nchunks > 0 && (!container || !offsets)) || !chunk || !start || !nitems || !result_out) return -1;
-  for (int i = 0; i < nchunks; i++) if (offsets[i + 1] < offsets[i]) return -1;
-  if (nchunks > 0 && offsets[nchunks] > containersize) return -1;
-  Job* jobs = (Job*)malloc(sizeof(Job) * (size_t)(nchunks > 0 ? nchunks : 1));
-  ItemRange* ranges = item_ranges(nranges, chunk, start, nitems, nullptr);
-  int r = -1;
-  if (jobs && ranges) {
-    for (int i = 0; i < nchunks; i++) {
-      // as blosc_gpu_decompress_packed: the span between two offsets is all a chunk may claim; one that cannot hold a header is passed as 1 byte
-      const size_t span = offsets[i + 1] - offsets[i];
-      jobs[i] = Job{(const uint8_t*)container + offsets[i], nullptr, span < (size_t)BLOSC_MIN_HEADER_LENGTH ? 1 : span, 0};
-    }
-    const PackedBuffer pk{dest, dest ? destsize : 0, 0, dest_offsets_out};
-    r = engine_getitem_batch(nchunks, jobs, nranges, ranges, result_out, (hipStream_t)stream, &pk);
-  }
-  free(jobs); free(ranges);
-  return r;
+  const PackedBuffer pk{dest, dest ? destsize : 0, 0, dest_offsets_out};
+  return getitem_call(nchunks, jobs_from_spans(nchunks, container, containersize, offsets, nullptr, BLOSC_MIN_HEADER_LENGTH), nranges, chunk, start, nitems,
+                      nullptr, result_out, stream, &pk);
 }
 
 // ---- adler32 / crc32 of many runs (include/blosc_gpu_checksum.h) ---------------------------------------
-static const size_t kChecksumMaxRun = (size_t)INT32_MAX + 16;      // beyond the largest chunk
-static int checksum_runs(int kind, int nruns, Job* jobs, unsigned int* digest_out, void* stream) {
-  int r = -1;
-  if (jobs) {
-    bool ok = true;
-    for (int i = 0; i < nruns && ok; i++) ok = jobs[i].srcsize <= kChecksumMaxRun && (jobs[i].srcsize == 0 || jobs[i].src);
-    if (ok) r = engine_checksum_batch(kind, nruns, jobs, digest_out, (hipStream_t)stream);
-  }
-  free(jobs);
-  return r;
-}
 int blosc_gpu_checksum_batch(int kind, int nruns, const void* const* src, const size_t* nbytes, unsigned int* digest_out, void* stream) {
-  if (kind != BLOSC_GPU_CHECKSUM_ADLER32 && kind != BLOSC_GPU_CHECKSUM_CRC32) return -1;
-  if (nruns <= 0) return 0;
+  const int c = checksum_opening(kind, nruns);
+  if (c != kGo) return c;
   if (!src || !nbytes || !digest_out) return -1;
-  Job* jobs = (Job*)malloc(sizeof(Job) * (size_t)nruns);
-  for (int i = 0; jobs && i < nruns; i++) jobs[i] = Job{src[i], nullptr, nbytes[i], 0};
-  return checksum_runs(kind, nruns, jobs, digest_out, stream);
+  return checksum_call(kind, nruns, jobs_from_arrays(nruns, src, nullptr, nbytes, nullptr), digest_out, stream);
 }
 int blosc_gpu_checksum_packed(int kind, int nruns, const void* container, size_t containersize, const size_t* offsets,
                               const size_t* length, unsigned int* digest_out, void* stream) {
-  if (kind != BLOSC_GPU_CHECKSUM_ADLER32 && kind != BLOSC_GPU_CHECKSUM_CRC32) return -1;
-  if (nruns <= 0) return 0;
+  const int c = checksum_opening(kind, nruns);
+  if (c != kGo) return c;
   if (!offsets || !digest_out) return -1;
-  for (int i = 0; i < nruns; i++)
-    if (offsets[i + 1] < offsets[i] || (length && length[i] > offsets[i + 1] - offsets[i])) return -1;
-  if (offsets[nruns] > containersize || (offsets[nruns] > offsets[0] && !container)) return -1;
-  Job* jobs = (Job*)malloc(sizeof(Job) * (size_t)nruns);
-  for (int i = 0; jobs && i < nruns; i++)
-    jobs[i] = Job{(const uint8_t*)container + offsets[i], nullptr, length ? length[i] : offsets[i + 1] - offsets[i], 0};
-  return checksum_runs(kind, nruns, jobs, digest_out, stream);
+  if (!container && offsets[nruns] > offsets[0]) return -1;      // no container: only for a table of empty spans (jobs_from_spans() checks that it rises)
+  return checksum_call(kind, nruns, jobs_from_spans(nruns, container, containersize, offsets, length, 0), digest_out, stream);
 }
 
 // test hooks of the persistent grids (engine.h)

@@ -5,6 +5,7 @@ Chunk-level round trips through the stock C ABI for every codec and for every en
 the round's GPU time was spent get their host wiring (kernel selection, scratch allocation) exercised here before their first device
 run.  Yardsticks: the oracle and, where oracle/_ref ships, the reference itself."""
 import ctypes as C
+import importlib.util
 import os
 import subprocess
 import sys
@@ -36,12 +37,10 @@ def emulib():
     elif not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
         subprocess.check_call([CLANG, "-std=c++17", "-O1", "-shared", "-fPIC", "-w", "-I", os.path.join(tools, "wave_emu"), "-I", csrc,
                                "-I", os.path.join(ROOT, "include"), "-x", "c++", deps[0], "-o", so, "-lpthread"])
-    L = C.CDLL(so)
-    sz, i, vp = C.c_size_t, C.c_int, C.c_void_p
-    L.blosc_compress_ctx.argtypes = [i, i, sz, sz, vp, vp, sz, C.c_char_p, sz, i]
-    L.blosc_decompress_ctx.argtypes = [vp, vp, sz, i]
-    L.blosc_getitem.argtypes = [vp, i, i, vp]
-    return L
+    spec = importlib.util.spec_from_file_location("c_blosc_amd_for_emu", os.path.join(ROOT, "c-blosc_amd", "__init__.py"))
+    pkgmod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(pkgmod)
+    return pkgmod.declare(C.CDLL(so))
 
 
 def _compress(L, data, T, clevel, shuffle, cname, blocksize=0):

@@ -263,7 +263,12 @@ static void trampoline(unsigned lo, unsigned hi) {
   swapcontext(&w->ctx[l], &w->sched);
 }
 
-static thread_local char* g_stack_pool[MAXT];
+struct StackPool {      // a thread's fiber stacks, kept from launch to launch and freed when the thread ends (the multi-GPU calls run kernels on worker threads)
+  char* stack[MAXT] = {};
+  char*& operator[](int l) { return stack[l]; }
+  ~StackPool() { for (char* s : stack) free(s); }
+};
+static thread_local StackPool g_stack_pool;
 
 void run_group(int nthreads, void (*body)(int thread, void* arg), void* arg) {
   static bool handlers = false;

@@ -1,7 +1,7 @@
 """c-blosc_amd — Python-side loader for libblosc_amd.so (ctypes; test / bench plumbing only).
 
 The product is the C-ABI shared library built from ``csrc/`` (see ``include/blosc.h`` and
-``include/blosc_gpu.h``, ``include/blosc_gpu_packed.h``, ``include/blosc_gpu_params.h``, ``include/blosc_gpu_getitem.h``, ``include/blosc_gpu_checksum.h``).  This module only locates it, declares argument types and offers small
+``include/blosc_gpu.h``, ``include/blosc_gpu_packed.h``, ``include/blosc_gpu_params.h``, ``include/blosc_gpu_select.h``, ``include/blosc_gpu_getitem.h``, ``include/blosc_gpu_checksum.h``).  This module only locates it, declares argument types and offers small
 numpy conveniences that mirror how the reference is driven from Python through ctypes
 (SURVEY.md §A.8).  There is no CPU implementation here: if the library is missing, ``load()``
 raises; if there is no GPU, the library's calls return errors.
@@ -42,6 +42,9 @@ CHECKSUM_SYMBOLS = [    # include/blosc_gpu_checksum.h
 PARAMS_SYMBOLS = [      # include/blosc_gpu_params.h
     "blosc_gpu_compress_batch_params", "blosc_gpu_compress_packed_params",
 ]
+SELECT_SYMBOLS = [      # include/blosc_gpu_select.h
+    "blosc_gpu_compress_batch_select", "blosc_gpu_compress_packed_select",
+]
 CHECKSUM_ADLER32, CHECKSUM_CRC32 = 1, 2
 COMPCODES = {b"blosclz": 0, b"lz4": 1, b"lz4hc": 2, b"snappy": 3, b"zlib": 4, b"zstd": 5}      # include/blosc.h
 
@@ -67,6 +70,13 @@ def params_table(params):
     """The host array of blosc_gpu_cparams a call takes, from a list of CParams (or of argument tuples / dicts of cparams())"""
     rows = [p if isinstance(p, CParams) else (cparams(**p) if isinstance(p, dict) else cparams(*p)) for p in params]
     return (CParams * max(len(rows), 1))(*rows)
+
+
+def candidate_tables(cand_first, rows):
+    """(cand_first as a C int array, the rows' table) of a call of include/blosc_gpu_select.h.  cand_first: [n + 1], chunk i has the
+    candidates rows[cand_first[i]:cand_first[i + 1]]; rows: see params_table"""
+    assert cand_first[-1] == len(rows)
+    return (C.c_int * len(cand_first))(*cand_first), params_table(rows)
 
 _lib = None
 
@@ -132,6 +142,9 @@ def _signatures():
         # include/blosc_gpu_params.h
         "blosc_gpu_compress_batch_params": ([i, P(CParams)] + batch + [vp], i),
         "blosc_gpu_compress_packed_params": ([i, P(CParams), pp, zp, vp, sz, sz, zp, ip, vp], i),
+        # include/blosc_gpu_select.h
+        "blosc_gpu_compress_batch_select": ([i, ip, P(CParams)] + batch + [ip, ip, vp], i),
+        "blosc_gpu_compress_packed_select": ([i, ip, P(CParams), pp, zp, vp, sz, sz, zp, ip, ip, ip, vp], i),
         # include/blosc_gpu_getitem.h
         "blosc_gpu_getitem_batch": ([i, pp, i, ip, ip, ip, pp, ip, vp], i),
         "blosc_gpu_getitem_packed": ([i, vp, sz, zp, i, ip, ip, ip, vp, sz, zp, ip, vp], i),
@@ -165,7 +178,7 @@ def declare(L):
     return L
 
 
-declare_packed = declare_params = declare_getitem = declare_checksum = declare      # the names from when every header had a function of its own
+declare_packed = declare_params = declare_select = declare_getitem = declare_checksum = declare      # the names from when every header had a function of its own
 
 
 # ---- numpy conveniences (host buffers through the stock entry points) --------------------------
@@ -212,6 +225,23 @@ class DeviceBatch:
         return (lib if lib is not None else load()).blosc_gpu_compress_batch_params(self.n, params_table(params), self.src, self.ssz, self.dst, self.dsz,
                                                                                     self.res, stream)
 
+    def compress_select(self, cand_first, rows, stream=None, lib=None):
+        """chunk i with the best of rows[cand_first[i]:cand_first[i + 1]] (include/blosc_gpu_select.h), the whole batch in one call;
+        results() are the winners' sizes, choices() their indices inside their ranges, candidate_results() every candidate's size"""
+        assert len(cand_first) == self.n + 1
+        first, table = candidate_tables(cand_first, rows)
+        self.choice = (C.c_int * max(self.n, 1))()
+        self.cand = (C.c_int * max(len(rows), 1))()
+        self.ncand = len(rows)
+        return (lib if lib is not None else load()).blosc_gpu_compress_batch_select(self.n, first, table, self.src, self.ssz, self.dst, self.dsz, self.res,
+                                                                                    self.choice, self.cand, stream)
+
+    def choices(self):
+        return list(self.choice)[:self.n]
+
+    def candidate_results(self):
+        return list(self.cand)[:self.ncand]
+
     def decompress(self, stream=None, with_srcsize=True):
         return load().blosc_gpu_decompress_batch(self.n, self.src, self.ssz if with_srcsize else None, self.dst,
                                                  self.dsz, self.res, stream)
@@ -245,6 +275,23 @@ class PackedBatch:
         assert len(params) == self.n
         return self.lib.blosc_gpu_compress_packed_params(self.n, params_table(params), (C.c_void_p * self.n)(*src_ptrs),
                                                          (C.c_size_t * self.n)(*src_sizes), dest, destsize, align, self.off, self.res, stream)
+
+    def compress_select(self, src_ptrs, src_sizes, cand_first, rows, dest, destsize, align=1, stream=None):
+        """chunk i with the best of rows[cand_first[i]:cand_first[i + 1]] (include/blosc_gpu_select.h) into one container in the
+        caller's order; choices() are the winners' indices inside their ranges, candidate_results() every candidate's size"""
+        assert len(cand_first) == self.n + 1
+        first, table = candidate_tables(cand_first, rows)
+        self.choice = (C.c_int * max(self.n, 1))()
+        self.cand = (C.c_int * max(len(rows), 1))()
+        self.ncand = len(rows)
+        return self.lib.blosc_gpu_compress_packed_select(self.n, first, table, (C.c_void_p * self.n)(*src_ptrs), (C.c_size_t * self.n)(*src_sizes),
+                                                         dest, destsize, align, self.off, self.res, self.choice, self.cand, stream)
+
+    def choices(self):
+        return list(self.choice)[:self.n]
+
+    def candidate_results(self):
+        return list(self.cand)[:self.ncand]
 
     def decompress(self, container, containersize, offsets, dest, destsize, stream=None):
         return self.lib.blosc_gpu_decompress_packed(self.n, container, containersize, (C.c_size_t * (self.n + 1))(*offsets), dest, destsize,

@@ -18,6 +18,7 @@
 #include "../../include/blosc_gpu.h"
 #include "../../include/blosc_gpu_packed.h"
 #include "../../include/blosc_gpu_params.h"
+#include "../../include/blosc_gpu_select.h"
 #include "../../include/blosc_gpu_getitem.h"
 #include "../../include/blosc_gpu_checksum.h"
 #include "blosc_format.h"
@@ -41,6 +42,8 @@ static bool codec_built(int code) { return code == BLOSC_BLOSCLZ || code == BLOS
 // Whole-call checks by family.  A call that fails one answers -1 and writes nothing; tests/test_abi_arguments.py pins every line.
 //   *_batch, *_batch_host, *_batch_multi   n <= 0 answers 0.  The arrays are the caller's word (include/blosc_gpu.h), only `srcsize` may be NULL.
 //   compress_batch_params                   n <= 0 answers 0, then every array must be there.
+//   compress_batch_select, _packed_select   their _params form's checks, then select_tables(): the candidate tables must be there (only
+//                                           `cand_cbytes_out` may be NULL), cand_first must start at 0 and never decrease.
 //   the packed calls                        packed_opening(): n < 0 or no table to write is unusable, n == 0 writes an empty table and answers 0;
 //                                           then every array must be there.  `dest` may be NULL: the compress calls size (destsize must be 0
 //                                           then), the reading calls size whatever destsize says.
@@ -113,10 +116,10 @@ static Table<CompressParams> chunk_params(int nchunks, const blosc_gpu_cparams* 
 // (The callers make their tables in the argument list: such a temporary lives until the call has returned.)
 // packed: every chunk's own limit is the size at which blosc_compress_ctx cannot answer 0; where it goes is the engine's layout step
 static int compress_call(const CompressParams* params, bool per_chunk, int n, const Table<Job>& jobs, int* results, bool device_ptrs, void* stream,
-                         const PackedBuffer* packed) {
+                         const PackedBuffer* packed, const CandidateSelect* select = nullptr) {
   if (!params || !jobs) return -1;
   for (int i = 0; packed && i < n; i++) jobs[i].dstsize = jobs[i].srcsize + BLOSC_MAX_OVERHEAD;
-  return engine_compress_batch(params, per_chunk, n, jobs.get(), results, device_ptrs, (hipStream_t)stream, packed);
+  return engine_compress_batch(params, per_chunk, n, jobs.get(), results, device_ptrs, (hipStream_t)stream, packed, select);
 }
 static int decompress_call(int n, const Table<Job>& jobs, int* results, bool device_ptrs, void* stream, const PackedBuffer* packed) {
   return jobs ? engine_decompress_batch(n, jobs.get(), results, device_ptrs, (hipStream_t)stream, packed) : -1;
@@ -449,6 +452,32 @@ int blosc_gpu_compress_packed_params(int nchunks, const blosc_gpu_cparams* param
   const PackedBuffer pk{dest, destsize, align, offsets_out};
   return compress_call(chunk_params(nchunks, params).get(), true, nchunks, jobs_from_arrays(nchunks, src, nullptr, nbytes, nullptr), cbytes_out, true, stream,
                        &pk);
+}
+
+// ---- candidates per chunk (include/blosc_gpu_select.h): the two calls above with a range of rows per chunk ---------------------------------------
+static bool select_tables(int nchunks, const int* cand_first, const blosc_gpu_cparams* cands, const int* choice_out) {
+  if (!cand_first || !cands || !choice_out || cand_first[0] != 0) return false;
+  for (int i = 0; i < nchunks; i++) if (cand_first[i + 1] < cand_first[i]) return false;
+  return true;
+}
+int blosc_gpu_compress_batch_select(int nchunks, const int* cand_first, const blosc_gpu_cparams* cands, const void* const* src, const size_t* nbytes,
+                                    void* const* dest, const size_t* destsize, int* cbytes_out, int* choice_out, int* cand_cbytes_out, void* stream) {
+  if (nchunks <= 0) return 0;
+  if (!src || !nbytes || !dest || !destsize || !cbytes_out || !select_tables(nchunks, cand_first, cands, choice_out)) return -1;
+  const CandidateSelect sel{cand_first, choice_out, cand_cbytes_out};
+  return compress_call(chunk_params(cand_first[nchunks], cands).get(), true, nchunks, jobs_from_arrays(nchunks, src, dest, nbytes, destsize), cbytes_out, true,
+                       stream, nullptr, &sel);
+}
+int blosc_gpu_compress_packed_select(int nchunks, const int* cand_first, const blosc_gpu_cparams* cands, const void* const* src, const size_t* nbytes,
+                                     void* dest, size_t destsize, size_t align, size_t* offsets_out, int* cbytes_out, int* choice_out,
+                                     int* cand_cbytes_out, void* stream) {
+  const int c = packed_compress_opening(nchunks, src, nbytes, dest, destsize, &align, offsets_out, cbytes_out);
+  if (c != kGo) return c;
+  if (!select_tables(nchunks, cand_first, cands, choice_out)) return -1;
+  const PackedBuffer pk{dest, destsize, align, offsets_out};
+  const CandidateSelect sel{cand_first, choice_out, cand_cbytes_out};
+  return compress_call(chunk_params(cand_first[nchunks], cands).get(), true, nchunks, jobs_from_arrays(nchunks, src, nullptr, nbytes, nullptr), cbytes_out, true,
+                       stream, &pk, &sel);
 }
 
 int blosc_gpu_decompress_packed(int nchunks, const void* container, size_t containersize, const size_t* offsets,

@@ -44,8 +44,17 @@ struct PackedBuffer {
 // packed != nullptr (device pointers only): jobs[i].dst is ignored, jobs[i].dstsize is the chunk's own limit
 // compress: per_chunk - chunk i is compressed with params[i] (include/blosc_gpu_params.h); otherwise every chunk with params[0].  A
 // parameter error (-10) or a codec that is not built (-5) is the outcome of its chunk alone.
+// compress: select (include/blosc_gpu_select.h; device pointers only, per_chunk) - chunk i has the candidates params[cand_first[i] ..
+// cand_first[i + 1]).  Every candidate is encoded, the one with the smallest positive outcome (the lowest index on a tie) is the one
+// written, and results[i] is its outcome; where no candidate has one, results[i] is the first candidate's outcome (-10 without
+// candidates), nothing is written and the chunk takes 0 bytes of a packed buffer.
+struct CandidateSelect {
+  const int* cand_first;   // host [n + 1]: starts at 0 and never decreases (the caller has checked it)
+  int* choice;             // host [n], written: the winner's index relative to cand_first[i], or -1
+  int* cand_results;       // host [cand_first[n]], written, or nullptr: every candidate's outcome
+};
 int engine_compress_batch(const CompressParams* params, bool per_chunk, int n, const Job* jobs, int* results, bool device_ptrs,
-                          hipStream_t stream, const PackedBuffer* packed = nullptr);
+                          hipStream_t stream, const PackedBuffer* packed = nullptr, const CandidateSelect* select = nullptr);
 int engine_decompress_batch(int n, const Job* jobs, int* results, bool device_ptrs, hipStream_t stream,
                             const PackedBuffer* packed = nullptr);
 // the parsed 16-byte headers of n device-resident chunks (one gather kernel, one synchronisation)

@@ -713,10 +713,16 @@ int engine_enc_lz_occupancy(int dynamic_lds) {
 static std::atomic<uint32_t> g_last_enc_tasks[3];
 void engine_last_compress_tasks(uint32_t out[3]) { for (int i = 0; i < 3; i++) out[i] = g_last_enc_tasks[i].load(); }
 
-int engine_compress_batch(const CompressParams* params, bool per_chunk, int n, const Job* jobs, int* results, bool device_ptrs,
-                          hipStream_t stream, const PackedBuffer* packed) {
+// A call with candidates (engine.h: CandidateSelect) as compress_entries sees it: its n chunks are the ENTRIES, one per candidate, those of
+// one caller chunk adjacent - entries [first[i], first[i + 1]) are the candidates of caller chunk i of nchunks.  choice: [nchunks],
+// answers: [n], host arrays it writes.
+struct SelectRun { int nchunks; const int* first; int* choice; int* answers; };
+
+// The compress call over a table of n chunks.  sel == nullptr: engine_compress_batch as it is without candidates - not a launch, not a byte more.
+static int compress_entries(const CompressParams* params, bool per_chunk, int n, const Job* jobs, int* results, bool device_ptrs,
+                            hipStream_t stream, const PackedBuffer* packed, const SelectRun* sel) {
   if (n <= 0) return 0;
-  if (packed && !device_ptrs) return -1;
+  if ((packed || sel) && !device_ptrs) return -1;
   CtxGuard ctx; EngineState& st = *ctx.st;
   if (ensure_device(st) || call_stream(st, !device_ptrs, &stream)) return -1;
   HostPhases ht(0);
@@ -771,7 +777,10 @@ int engine_compress_batch(const CompressParams* params, bool per_chunk, int n, c
   const size_t o_blkoff = cv.take(sizeof(int32_t) * (nblk ? nblk : 1));
   // results + tickets | block-ready flags | cost words: taken back to back, ONE fill clears the three of them
   // (every group has ticket words and cost words of its own: group k's are the k-th set)
-  const size_t o_results = cv.take(ticket_offset((size_t)n) + sizeof(uint32_t) * kEncTicketWords * ngrp);
+  // (candidates: the choices and the candidate answers lie directly in front of the results - ONE download brings the three back)
+  const size_t sel_bytes = sel ? sizeof(int32_t) * ((size_t)sel->nchunks + (size_t)n) : 0;
+  const size_t o_sel = cv.take(sel_bytes + ticket_offset((size_t)n) + sizeof(uint32_t) * kEncTicketWords * ngrp);
+  const size_t o_results = o_sel + sel_bytes;
   const size_t o_ready = cv.take(sizeof(uint32_t) * (nblk ? nblk : 1));
   const size_t o_cost = cv.take(sizeof(uint32_t) * kCostWords * ngrp);
   const size_t clear_bytes = cv.off - o_results;
@@ -786,7 +795,8 @@ int engine_compress_batch(const CompressParams* params, bool per_chunk, int n, c
     if (v.zstd) { o_ctabs[g.mode] = cv.take(sizeof(zenc::CTabs) + 64); any_zstd = true; }
     if (zwaves) o_seqbufs[g.mode] = cv.take(zwaves * (v.zdyn ? (size_t)ZD_SCRATCH_U64 : (size_t)ZS_SEQCAP) * sizeof(uint64_t) + 64);
   }
-  const size_t o_offsets = packed ? cv.take(sizeof(uint64_t) * ((size_t)n + 1)) : 0;      // packed: the offset table k_packed_layout writes
+  const size_t o_offsets = (packed || sel) ? cv.take(sizeof(uint64_t) * ((size_t)n + 1)) : 0;      // packed: the offset table k_packed_layout writes
+  const size_t o_first = sel ? cv.take(sizeof(int32_t) * ((size_t)sel->nchunks + 1)) : 0;         // candidates: where every caller chunk's entries begin
   if (st.dev.ensure(cv.off)) return -1;
   uint8_t* D = st.dev.base;
   if (any_zstd) {
@@ -812,7 +822,8 @@ int engine_compress_batch(const CompressParams* params, bool per_chunk, int n, c
   ht.mark(1);     // queues, workspace, pointer patching
   // ---- upload the tables ----
   const size_t p_chunks = pc.take(sizeof(ChunkDesc) * (size_t)n);
-  const size_t p_results = pc.take(sizeof(int32_t) * (size_t)n);
+  const size_t p_results = pc.take(sel_bytes + sizeof(int32_t) * (size_t)n);
+  const size_t p_first = sel ? pc.take(sizeof(int32_t) * ((size_t)sel->nchunks + 1 + (size_t)n)) : 0;      // ... and the entries' outcomes so far
   const size_t p_cost = pc.take(sizeof(uint32_t) * kCostWords * ngrp);
   const size_t p_offsets = packed ? pc.take(sizeof(uint64_t) * ((size_t)n + 1)) : 0;
   if (st.pin.ensure(pc.off)) return -1;
@@ -821,6 +832,13 @@ int engine_compress_batch(const CompressParams* params, bool per_chunk, int n, c
   if (tc.upload(B.key, P, stream)) return -1;
   HIP_TRY(hipMemsetAsync(D + o_results, 0, clear_bytes, stream));
   HIP_TRY(hipMemcpyAsync(D + o_chunks, P + p_chunks, sizeof(ChunkDesc) * (size_t)n, hipMemcpyHostToDevice, stream));
+  if (sel) {      // the range table, and what the host has answered already (row errors: k_candidate_select hands them on with the sizes)
+    const size_t first_bytes = sizeof(int32_t) * ((size_t)sel->nchunks + 1);
+    memcpy(P + p_first, sel->first, first_bytes);
+    memcpy(P + p_first + first_bytes, results, sizeof(int32_t) * (size_t)n);
+    HIP_TRY(hipMemcpyAsync(D + o_first, P + p_first, first_bytes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(D + o_results, P + p_first + first_bytes, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, stream));
+  }
 
   ChunkDesc* d_chunks = (ChunkDesc*)(D + o_chunks); BlockDesc* d_blocks = tc.d_blocks(); StreamDesc* d_streams = (StreamDesc*)(D + o_streams);
   int32_t* d_blkoff = (int32_t*)(D + o_blkoff); int32_t* d_results = (int32_t*)(D + o_results);
@@ -862,7 +880,7 @@ int engine_compress_batch(const CompressParams* params, bool per_chunk, int n, c
     }
 #undef BAMD_ENC_LAUNCH
   }
-  if (!packed) {
+  if (!packed && !sel) {
     ProfScope ps(st, stream, "k_chunk_scan");
     hipLaunchKernelGGL(k_chunk_scan, dim3((unsigned)n), dim3(SCAN_THREADS), 0, stream, d_chunks, d_blocks, d_streams, d_blkoff, d_results);
   } else {
@@ -873,17 +891,31 @@ int engine_compress_batch(const CompressParams* params, bool per_chunk, int n, c
       ProfScope ps(st, stream, "k_chunk_scan");
       hipLaunchKernelGGL(k_chunk_scan_packed, dim3((unsigned)n), dim3(SCAN_THREADS), 0, stream, d_chunks, d_blocks, d_streams, d_blkoff, d_results);
     }
-    ProfScope ps(st, stream, "k_packed_layout");
-    hipLaunchKernelGGL(k_packed_layout, dim3(1), dim3(SCAN_THREADS), 0, stream, d_chunks, d_results, n, (uint8_t*)packed->base, (uint64_t)packed->size,
-                       (uint64_t)packed->align, d_offsets);
-    hipLaunchKernelGGL(k_packed_headers, dim3((unsigned)n), dim3(SCAN_THREADS), 0, stream, d_chunks, d_blkoff, d_results, d_offsets, (uint64_t)packed->size);
+    // candidates: the sizes are known and nothing is written yet - every entry but its chunk's winner leaves the call here (CH_SKIP, result 0:
+    // no room in the layout, no header, no compaction)
+    if (sel) {
+      ProfScope ps(st, stream, "k_candidate_select");
+      hipLaunchKernelGGL(k_candidate_select, dim3((unsigned)sel->nchunks), dim3(SELECT_THREADS), 0, stream, d_chunks, d_results, (const int32_t*)(D + o_first),
+                         (int32_t*)(D + o_sel) + sel->nchunks, (int32_t*)(D + o_sel));
+    }
+    if (packed) {
+      ProfScope ps(st, stream, "k_packed_layout");
+      hipLaunchKernelGGL(k_packed_layout, dim3(1), dim3(SCAN_THREADS), 0, stream, d_chunks, d_results, n, (uint8_t*)packed->base, (uint64_t)packed->size,
+                         (uint64_t)packed->align, d_offsets);
+      hipLaunchKernelGGL(k_packed_headers, dim3((unsigned)n), dim3(SCAN_THREADS), 0, stream, d_chunks, d_blkoff, d_results, d_offsets, (uint64_t)packed->size);
+    } else {
+      // candidates, a destination per chunk: c.dst is the caller's.  The winner's header and bstarts come from k_packed_headers over a table of
+      // zeros and a buffer of no bytes, so it pads nothing
+      HIP_TRY(hipMemsetAsync(d_offsets, 0, sizeof(uint64_t) * ((size_t)n + 1), stream));
+      hipLaunchKernelGGL(k_packed_headers, dim3((unsigned)n), dim3(SCAN_THREADS), 0, stream, d_chunks, d_blkoff, d_results, d_offsets, (uint64_t)0);
+    }
   }
   if (nblk) {
     ProfScope ps(st, stream, "k_chunk_compact");
     hipLaunchKernelGGL(k_chunk_compact, dim3((unsigned)nblk), dim3(COMPACT_THREADS), 0, stream, d_chunks, d_blocks, d_streams, d_blkoff);
   }
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(P + p_results, d_results, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(P + p_results, D + o_sel, sel_bytes + sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipMemcpyAsync(P + p_cost, D + o_cost, sizeof(uint32_t) * kCostWords * ngrp, hipMemcpyDeviceToHost, stream));
   if (packed) HIP_TRY(hipMemcpyAsync(P + p_offsets, D + o_offsets, sizeof(uint64_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, stream));
   ht.mark(3);     // kernel launches
@@ -904,9 +936,43 @@ int engine_compress_batch(const CompressParams* params, bool per_chunk, int n, c
   }
   tc.commit(B.key);
   if (feedback && nstr >= 4096) { memcpy(st.enc_cost, P + p_cost, sizeof st.enc_cost); st.enc_cost_valid = true; }   // small calls say little
-  const int32_t* r = (const int32_t*)(P + p_results);
+  const int32_t* r = (const int32_t*)(P + p_results + sel_bytes);
   for (int i = 0; i < n; i++) if (B.live[(size_t)i]) results[i] = r[i];
+  if (sel) {
+    memcpy(sel->choice, P + p_results, sizeof(int32_t) * (size_t)sel->nchunks);
+    memcpy(sel->answers, P + p_results + sizeof(int32_t) * (size_t)sel->nchunks, sizeof(int32_t) * (size_t)n);
+  }
   return io.collect(n, jobs, chunks, B.live, results, stream);
+}
+
+int engine_compress_batch(const CompressParams* params, bool per_chunk, int n, const Job* jobs, int* results, bool device_ptrs,
+                          hipStream_t stream, const PackedBuffer* packed, const CandidateSelect* select) {
+  if (!select) return compress_entries(params, per_chunk, n, jobs, results, device_ptrs, stream, packed, nullptr);
+  if (n <= 0) return 0;
+  if (!device_ptrs || !per_chunk) return -1;
+  // one entry per candidate: the candidates of a chunk share its source, its destination and its limit.  Everything the entries' call
+  // writes goes to tables of this function, so a call that fails leaves the caller's untouched
+  const int* first = select->cand_first;
+  const int E = first[n];
+  std::vector<Job> entries((size_t)E);
+  for (int i = 0; i < n; i++) for (int e = first[i]; e < first[i + 1]; e++) entries[(size_t)e] = jobs[i];
+  std::vector<int> sizes((size_t)E, 0), answers((size_t)E, 0), choice((size_t)n, -1);
+  std::vector<size_t> offsets((size_t)E + 1, 0);
+  PackedBuffer pk{};
+  if (packed) { pk = *packed; pk.offsets = offsets.data(); }
+  const SelectRun run{n, first, choice.data(), answers.data()};
+  if (compress_entries(params, true, E, entries.data(), sizes.data(), true, stream, packed ? &pk : nullptr, &run)) return -1;
+  // fold the entries' tables into the caller's: a chunk is its winner (in a packed buffer the losers took no room: the chunk begins
+  // where its first entry does)
+  for (int i = 0; i < n; i++) {
+    const int f = first[i], c = choice[(size_t)i];
+    results[i] = f == first[i + 1] ? -10 : (c >= 0 ? sizes[(size_t)(f + c)] : answers[(size_t)f]);
+    select->choice[i] = c;
+    if (packed) packed->offsets[i] = offsets[(size_t)f];
+  }
+  if (packed) packed->offsets[n] = offsets[(size_t)E];
+  if (select->cand_results && E > 0) memcpy(select->cand_results, answers.data(), sizeof(int) * (size_t)E);
+  return 0;
 }
 
 // ---------------------------------------------------------------------------------------------

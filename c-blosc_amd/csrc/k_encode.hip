@@ -393,6 +393,36 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_chunk_scan_packed(ChunkDesc* _
   chunk_scan<true>(chunks, blocks, streams, blk_off, results);
 }
 
+// k_candidate_select (include/blosc_gpu_select.h): ONE wave per chunk of the caller, behind k_chunk_scan_packed and in front of whatever writes
+// caller memory.  The entries [first[i], first[i + 1]) of the call's chunk table are the candidate encodings of chunk i, results[] their sizes
+// (or the row errors the host found, which it marked CH_SKIP: never winners).  The lanes stride over the range, each keeping the smallest
+// key (size, entry) of its entries - the smallest positive size wins, the lowest entry on a tie -, the wave takes the smallest of the 64.
+// answers[] gets every entry's result as found; then every entry but the winner becomes a chunk nothing behind this kernel touches:
+// CH_SKIP and result 0, as k_packed_layout leaves a chunk that has no place.  choice[i]: the winner relative to first[i], or -1.
+// A size never has all 32 bits set, so that is "no size" (INT32_MAX is the size of a MEMCPYED chunk of the largest buffer).
+constexpr int SELECT_THREADS = 64;
+__global__ __launch_bounds__(SELECT_THREADS) void k_candidate_select(ChunkDesc* __restrict__ chunks, int32_t* __restrict__ results,
+                                                                    const int32_t* __restrict__ first,   // [nchunks + 1]
+                                                                    int32_t* __restrict__ answers,       // [first[nchunks]] out
+                                                                    int32_t* __restrict__ choice) {      // [nchunks] out
+  const int i = blockIdx.x, lane = threadIdx.x;
+  const int32_t e0 = first[i], e1 = first[i + 1];
+  uint64_t best = ~0ull;
+  for (int32_t e = e0 + lane; e < e1; e += SELECT_THREADS) {
+    const int32_t r = results[e];
+    answers[e] = r;
+    if (r > 0 && !(chunks[e].mode & CH_SKIP)) {
+      const uint64_t key = ((uint64_t)(uint32_t)r << 32) | (uint32_t)e;
+      best = key < best ? key : best;
+    }
+  }
+  best = wave_min_u64(best);
+  const int32_t winner = (uint32_t)(best >> 32) != 0xffffffffu ? (int32_t)(uint32_t)best : -1;
+  for (int32_t e = e0 + lane; e < e1; e += SELECT_THREADS)
+    if (e != winner) { chunks[e].mode |= CH_SKIP; results[e] = 0; }
+  if (lane == 0) choice[i] = winner >= 0 ? winner - e0 : -1;
+}
+
 // k_packed_layout: ONE workgroup walks the batch in tiles of its width, the running offset carried from tile to tile in 64 bits (a container
 // passes 4 GiB long before a batch passes a few thousand chunks).  Chunk i of size r_i = max(results[i], 0) starts at
 //   off_0 = 0,  off_(i+1) = align_up(off_i + r_i, align)      (every off_i is a multiple of align: a prefix sum of align_up(r_i, align))

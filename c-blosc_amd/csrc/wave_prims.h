@@ -206,6 +206,15 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
   for (int m = 32; m >= 1; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m, 64);
   return v;
 }
+// the smallest of the lanes' 64-bit keys, in every lane (k_encode.hip: k_candidate_select)
+__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
+  for (int m = 32; m >= 1; m >>= 1) {
+    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m, 64);
+    const uint64_t o = ((uint64_t)hi << 32) | lo;
+    v = o < v ? o : v;
+  }
+  return v;
+}
 // Adler-32 of p[0..n): a = 1 + sum d_i, b = n + sum (n - i) d_i (mod 65521); every lane takes 16-byte pieces
 __device__ __forceinline__ uint32_t wave_adler32(const gu8* p, uint32_t n, int lane) {
   uint64_t s1 = 0, s2 = 0;

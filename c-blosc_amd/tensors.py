@@ -1,4 +1,5 @@
-"""tensors.py — a list of device tensors of mixed dtypes in ONE packed container, written by ONE call (include/blosc_gpu_params.h).
+"""tensors.py — a list of device tensors of mixed dtypes in ONE packed container, written by ONE call (include/blosc_gpu_params.h; with
+candidate settings to choose from: include/blosc_gpu_select.h).
 
 A state dict, a table's columns, a cache line of activations: float32, bfloat16, int8 and int64 side by side.  Every tensor becomes one
 c-blosc chunk whose typesize is the tensor's element size, with the codec, filter and clevel of the call or of its own; the chunks lie
@@ -29,12 +30,28 @@ def _sibling(name, file):
     return sys.modules[key]
 
 
-def pack_tensors(lib, tensors, cname=b"lz4", clevel=5, shuffle=1, align=256, overrides=None, mem=None, stream=None):
+def _distinct(settings, element_size):
+    """`settings` without those that cannot give another size for a tensor of this element size than one in front of them: a byte
+    shuffle of single bytes is no filter (it writes another flag byte, never a smaller chunk)"""
+    seen, out = set(), []
+    for kw in settings:
+        key = tuple(sorted(dict(kw, shuffle=0 if (element_size == 1 and kw.get("shuffle") == 1) else kw.get("shuffle")).items()))
+        if key not in seen:
+            seen.add(key)
+            out.append(kw)
+    return out
+
+
+def pack_tensors(lib, tensors, cname=b"lz4", clevel=5, shuffle=1, align=256, overrides=None, mem=None, stream=None, candidates=None):
     """Compress the device tensors `tensors` into one container with one call of blosc_gpu_compress_packed_params.
     Tensor i is chunk i: typesize = its element_size(); codec, clevel and filter are the call's unless overrides[i] (overrides: a dict
     index -> dict with any of cname / clevel / shuffle / blocksize / splitmode) says otherwise.
     Returns (container, offsets, meta): a uint8 device tensor of offsets[-1] bytes, the offset table [n + 1] (multiples of `align`), and
-    [(dtype, shape)] for unpack_tensors."""
+    [(dtype, shape)] for unpack_tensors.
+    candidates: a list of such dicts, each tried on top of every tensor's setting by one call of blosc_gpu_compress_packed_select - the
+    smallest chunk is the one written, the first of the list on a tie.  Candidates that cannot differ for a tensor are tried once
+    (_distinct); overrides[i] may carry a list "candidates" of its own, which is tried as it stands.  Then the result is
+    (container, offsets, meta, choices), choices[i] the setting tensor i was written with (a dict of cname / clevel / shuffle / ...)."""
     pkg = _sibling("", "__init__.py")
     mem = mem if mem is not None else _sibling("blpk", "blpk.py").TorchMem()
     pkg.declare_packed(lib)
@@ -46,23 +63,39 @@ def pack_tensors(lib, tensors, cname=b"lz4", clevel=5, shuffle=1, align=256, ove
     sizes = [t.numel() * t.element_size() for t in flat]
     if max(sizes) > MAX_CHUNK:
         raise ValueError("a tensor above 2 GiB - 17 bytes does not fit one chunk: split it")
-    rows = []
+    tried = []      # per tensor: the settings to try
     for k, t in enumerate(flat):
         kw = dict(cname=cname, clevel=clevel, shuffle=shuffle)
-        kw.update((overrides or {}).get(k, {}))
-        rows.append(pkg.cparams(t.element_size(), **kw))
+        own = dict((overrides or {}).get(k, {}))
+        listed = own.pop("candidates", None)
+        kw.update(own)
+        if listed is not None: tried.append([dict(kw, **c) for c in listed])
+        elif candidates is not None: tried.append(_distinct([dict(kw, **c) for c in candidates], t.element_size()))
+        else: tried.append([kw])
+    select = candidates is not None or any("candidates" in o for o in (overrides or {}).values())
+    rows = [pkg.cparams(t.element_size(), **kw) for t, kws in zip(flat, tried) for kw in kws]
     b = pkg.PackedBatch(n, lib=lib)
     cap = b.bound(sizes, align)
     if cap == 0 and any(sizes):
         raise ValueError("align must be a power of two up to 4096")
     dest, keep = mem.alloc(cap)
-    if b.compress_params([t.data_ptr() if s else 0 for t, s in zip(flat, sizes)], sizes, rows, dest, cap, align, stream) != 0:
+    ptrs = [t.data_ptr() if s else 0 for t, s in zip(flat, sizes)]
+    if select:
+        pkg.declare_select(lib)
+        first = [0]
+        for kws in tried: first.append(first[-1] + len(kws))
+        if b.compress_select(ptrs, sizes, first, rows, dest, cap, align, stream) != 0:
+            raise RuntimeError("blosc_gpu_compress_packed_select failed")
+    elif b.compress_params(ptrs, sizes, rows, dest, cap, align, stream) != 0:
         raise RuntimeError("blosc_gpu_compress_packed_params failed")
     bad = [(k, r) for k, r in enumerate(b.results()) if r <= 0]
     if bad:
         raise RuntimeError(f"tensors that did not compress (index, code): {bad}")
     off = b.offsets()
-    return keep[:off[-1]], off, [(t.dtype, tuple(t.shape)) for t in tensors]
+    meta = [(t.dtype, tuple(t.shape)) for t in tensors]
+    if select:
+        return keep[:off[-1]], off, meta, [kws[c] for kws, c in zip(tried, b.choices())]
+    return keep[:off[-1]], off, meta
 
 
 def unpack_tensors(lib, container, offsets, meta, mem=None, stream=None):

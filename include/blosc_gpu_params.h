@@ -24,6 +24,7 @@
  *   a compcode that is not built (BLOSC_SNAPPY, any unknown code)                                     cbytes_out[i] = -5
  * and in the packed call both take 0 bytes.  (In the single-parameter calls an unusable compressor fails every chunk, because it is
  * every chunk's compressor; here it is one chunk's.)
+ * Several candidate rows per chunk, of which the smallest result is written: include/blosc_gpu_select.h.
  */
 #ifndef BLOSC_AMD_BLOSC_GPU_PARAMS_H
 #define BLOSC_AMD_BLOSC_GPU_PARAMS_H

@@ -141,28 +141,30 @@ static int check_done(const uint32_t* fb, size_t expect, size_t expect_zstd, con
 // The persistent kernels: one-wave workgroups that draw tasks from queues, launched as many as stay resident - a workgroup beyond that starts when
 // the first ones leave, finds the queues empty and goes, and a grid below it leaves wave slots empty for the whole launch.  How many stay resident is
 // the runtime's to say (registers the compiler really used, LDS in the device's granules): hipOccupancyMaxActiveBlocksPerMultiprocessor, asked once per
-// kernel when a context meets its device; the constexpr bound next to each kernel caps it.  Entries 0 .. kEncModes - 1 are k_encode_streams_t's modes.
+// kernel when a context meets its device; the constexpr bound next to each kernel caps it.  Entries 0 .. kEncModes - 1 are k_encode_streams_t's modes, row by row of its table (k_encode.hip).
+// Every row states the LDS of one workgroup, and that as many workgroups as its bound says fit the CU's LDS in the device's granules.
 // (k_getitem_gather's grid is a choice, not a residency: 16 waves per CU saturate the copy it is)
-enum { GRID_DECODE = 11, GRID_ZSTD_EXEC, GRID_ZSTD_STREAMS, GRID_ZLIB_STREAMS, kGridKernels };
-struct GridKernel { const char* name; const void* fn; int threads; int bound; };
-static const GridKernel* grid_kernels() {
-#define BAMD_ENC_GRID(MODE) {"k_encode_streams_t<" #MODE ">", (const void*)k_encode_streams_t<MODE>, 64 * ENC_WAVES, enc_grid_bound(MODE)}
+enum { GRID_DECODE = kEncModes, GRID_ZSTD_EXEC, GRID_ZSTD_STREAMS, GRID_ZLIB_STREAMS, kGridKernels };
+struct GridKernel { const char* name; const void* fn; int threads; int bound; int lds; };      // lds: bytes of one workgroup
+template <int LDS, int BOUND>
+static GridKernel grid_row(const char* name, const void* fn, int threads) {
+  static_assert(lds_occupied(LDS) * BOUND <= LDS_BYTES_PER_CU, "the workgroups of one CU fit its LDS, granule by granule");
+  return {name, fn, threads, BOUND, LDS};
+}
+template <int... MODE>
+static const GridKernel* grid_kernels(std::integer_sequence<int, MODE...>) {
   static const GridKernel k[kGridKernels] = {
-    BAMD_ENC_GRID(ENC_LZ), BAMD_ENC_GRID(ENC_ZSTD), BAMD_ENC_GRID(ENC_ZLIB), BAMD_ENC_GRID(ENC_HC), BAMD_ENC_GRID(ENC_ZSTD_T), BAMD_ENC_GRID(ENC_ZSTD_HC),
-    BAMD_ENC_GRID(ENC_ZLIB_HC), BAMD_ENC_GRID(ENC_ZSTD_TH), BAMD_ENC_GRID(ENC_ZSTD_HCH), BAMD_ENC_GRID(ENC_ZLIB_DYN), BAMD_ENC_GRID(ENC_ZLIB_DYN_HC),
-    {"k_decode_streams", (const void*)k_decode_streams, 64 * DEC_WAVES, DEC_WAVES_PER_CU},
-    {"k_zstd_exec", (const void*)k_zstd_exec, 64, ZEXEC_WAVES_PER_CU},
-    {"k_zstd_streams", (const void*)k_zstd_streams, 64, ZSTD_WAVES_PER_CU},
-    {"k_zlib_streams", (const void*)k_zlib_streams, 64, ZLIB_WAVES_PER_CU}};
-#undef BAMD_ENC_GRID
+    grid_row<enc_lds_bytes(MODE), enc_grid_bound(MODE)>(kEncMode[MODE].name, (const void*)k_encode_streams_t<MODE>, 64 * ENC_WAVES)...,
+    grid_row<DEC_WAVES * (int)DR_LDS_BYTES, DEC_WAVES_PER_CU>("k_decode_streams", (const void*)k_decode_streams, 64 * DEC_WAVES),
+    grid_row<(int)sizeof(uint32_t) * (int)ZXB_WORDS, ZEXEC_WAVES_PER_CU>("k_zstd_exec", (const void*)k_zstd_exec, 64),
+    grid_row<(int)sizeof(ZstdLds), ZSTD_WAVES_PER_CU>("k_zstd_streams", (const void*)k_zstd_streams, 64),
+    grid_row<(int)sizeof(zi::Tabs), ZLIB_WAVES_PER_CU>("k_zlib_streams", (const void*)k_zlib_streams, 64)};
   return k;
 }
-static_assert(ENC_LZ == 0 && ENC_ZLIB_DYN_HC == 10, "the encoder's modes index the table above");
-// (k_encode_streams_t states the same for each of its modes)
-static_assert(lds_occupied(DEC_WAVES * (int)DR_LDS_BYTES) * DEC_WAVES_PER_CU <= LDS_BYTES_PER_CU, "k_decode_streams: the workgroups of one CU fit its LDS, granule by granule");
-static_assert(lds_occupied((int)sizeof(uint32_t) * (int)ZXB_WORDS) * ZEXEC_WAVES_PER_CU <= LDS_BYTES_PER_CU, "k_zstd_exec: the workgroups of one CU fit its LDS, granule by granule");
-static_assert(lds_occupied((int)sizeof(ZstdLds)) * ZSTD_WAVES_PER_CU <= LDS_BYTES_PER_CU, "k_zstd_streams: the workgroups of one CU fit its LDS, granule by granule");
-static_assert(lds_occupied((int)sizeof(zi::Tabs)) * ZLIB_WAVES_PER_CU <= LDS_BYTES_PER_CU, "k_zlib_streams: the workgroups of one CU fit its LDS, granule by granule");
+static const GridKernel* grid_kernels() { return grid_kernels(std::make_integer_sequence<int, kEncModes>{}); }
+// the kernel of an encoder mode as its launch wants it: the table's entry in its own type (the modes share one parameter list)
+using EncKernel = decltype(&k_encode_streams_t<0>);
+static EncKernel enc_kernel(int mode) { return reinterpret_cast<EncKernel>(const_cast<void*>(grid_kernels()[mode].fn)); }
 // launches nothing; occupancy[i] = 0 where the runtime gave no answer (the bound alone sizes that grid)
 static void query_persistent_grids(int* wpc, int* occupancy) {
   const GridKernel* k = grid_kernels();
@@ -577,42 +579,48 @@ struct StreamProfile {
 #endif
 
 // The variant of k_encode_streams_t that serves a (codec, clevel), and what its launch needs.  The switches are read per call, as ever.
-struct EncVariant {
-  int mode = ENC_LZ; const char* name = "k_encode_streams";
-  int waves_per_cu = 0;            // what stays resident on a CU (EngineState::grid_wpc)
-  bool zstd = false, zdyn = false; // Zstd: predefined FSE tables + one sequence scratch per persistent wave; zlib with dynamic codes: the token scratch
-  int detect = 0;                  // the periodic-plane shortcut of the shuffle tasks
-};
+// What a launch needs beyond the two comes from the mode's row (k_encode.hip): Zstd - the predefined FSE tables; Zstd and zlib with dynamic codes - one
+// sequence scratch per persistent wave (enc_seq_words); the LZ family - the periodic-plane shortcut of the shuffle tasks; the name its time is booked under.
+struct EncVariant { int mode = kEncModes; int waves_per_cu = 0; };      // waves_per_cu: what stays resident on a CU (EngineState::grid_wpc)
+static const char* enc_profile_name(int mode) {
+  return kEncMode[mode].family == FAM_ZSTD ? "k_zstd_encode" : (kEncMode[mode].family == FAM_ZLIB ? "k_zlib_encode" : (kEncMode[mode].search ? "k_lz4hc_encode" : "k_encode_streams"));
+}
+// The mode of the row the switches ask for (kEncModes: there is none); a family takes its own switches.  Zstd: the search comes with per-block
+// tables, and Huffman-coded literals count on top of either only.
+constexpr int enc_mode_wanted(int family, bool search, bool tables, bool huffman, bool dynamic) {
+  const bool zstd = family == FAM_ZSTD;
+  const EncMode want = {nullptr, family, search, zstd && (tables || search), zstd && huffman && (tables || search), family == FAM_ZLIB && dynamic};
+  int m = 0;
+  while (m < kEncModes && !(kEncMode[m].family == want.family && kEncMode[m].search == want.search && kEncMode[m].tables == want.tables &&
+                            kEncMode[m].huffman == want.huffman && kEncMode[m].dynamic == want.dynamic)) m++;
+  return m;
+}
+// how many rows the settings of the switches compose: 2 of the LZ family, 5 of Zstd, 4 of zlib; -1: a setting without its row
+constexpr int enc_modes_composed() {
+  unsigned seen = 0;
+  for (int s = 0; s < (FAM_ZLIB + 1) * 16; s++) {     // family s / 16, the four switches the bits of s % 16
+    const int m = enc_mode_wanted(s >> 4, s & 1, s & 2, s & 4, s & 8);
+    if (m == kEncModes) return -1;
+    seen |= 1u << m;
+  }
+  return __builtin_popcount(seen);
+}
+static_assert(enc_modes_composed() == kEncModes, "every setting of the encoder switches has its row, and every row a setting");
 static EncVariant encoder_variant(const EngineState& st, int codec, int clevel) {
   EncVariant v;
-  // "lz4hc": the LZ4HC-grade search of k_encode.hip (lz4hc_encode_wave), or the plain LZ4 match finder at its highest effort
-  const bool zstd = codec == kZstd, zlibc = codec == kZlib;
-  const bool hc = codec == kLZ4HC && lz4hc_search_enabled();
-  // Zstd: sequence tables made per block (k_encode.hip: zt_make_tables) instead of the predefined ones
-  const bool ztab = zstd && zstd_tables_enabled();
-  // the LZ4HC-grade search in front of the Zstd writer (with per-block tables) / the zlib writer.
-  // Defaults after the device timings of round 3 (profiles/r03/r03a_encopts_bench_*.json, 8 GiB bench19): Zstd - the search costs 2.6 x the
+  const int family = codec == kZstd ? FAM_ZSTD : (codec == kZlib ? FAM_ZLIB : FAM_LZ);
+  // "lz4hc": the LZ4HC-grade search of k_encode.hip (lz4hc_encode_wave), or the plain LZ4 match finder at its highest effort.
+  // The LZ4HC-grade search in front of the Zstd writer (with per-block tables) / the zlib writer:
+  // defaults after the device timings of round 3 (profiles/r03/r03a_encopts_bench_*.json, 8 GiB bench19): Zstd - the search costs 2.6 x the
   // encode time (35.8 -> 94.9 ms) for ratio 23.8 -> 35.1, so it serves the upper clevels (the reference maps clevel >= 6 to its
   // lazy / optimal strategies, blosc.c:502-504 + clevels.h) and stays off at the default clevel; zlib - whoever names zlib wants its
   // ratio: search + dynamic codes give 73.4 (reference 47.4, fixed codes without search 40.5) at 57 ms per 8 GiB, still 150 GB/s.
-  const bool zsearch = (zstd && zstd_search_enabled(clevel)) || (zlibc && zlib_search_enabled());
-  const bool zhuf = zstd && (ztab || zsearch) && zstd_huffman_enabled();      // Huffman-coded literals: on top of either switch
-  v.zstd = zstd;
-  v.zdyn = zlibc && zlib_dynamic_enabled();      // zlib with dynamic Huffman codes: two passes, the tokens in the sequence scratch
-  v.detect = (!zstd && !zlibc && periodic_enabled()) ? 1 : 0;
-  v.name = zstd ? "k_zstd_encode" : (zlibc ? "k_zlib_encode" : (hc ? "k_lz4hc_encode" : "k_encode_streams"));
-  if (zstd && zsearch) v.mode = zhuf ? ENC_ZSTD_HCH : ENC_ZSTD_HC;
-  else if (zstd && ztab) v.mode = zhuf ? ENC_ZSTD_TH : ENC_ZSTD_T;
-  else if (zstd) v.mode = ENC_ZSTD;
-  else if (zlibc && v.zdyn) v.mode = zsearch ? ENC_ZLIB_DYN_HC : ENC_ZLIB_DYN;
-  else if (zlibc && zsearch) v.mode = ENC_ZLIB_HC;
-  else if (zlibc) v.mode = ENC_ZLIB;
-  else if (hc) v.mode = ENC_HC;
-  else v.mode = ENC_LZ;
+  // Zstd tables: sequence tables made per block (k_encode.hip: zt_make_tables) instead of the predefined ones.
+  const bool search = family == FAM_ZSTD ? zstd_search_enabled(clevel) : (family == FAM_ZLIB ? zlib_search_enabled() : codec == kLZ4HC && lz4hc_search_enabled());
+  v.mode = enc_mode_wanted(family, search, zstd_tables_enabled(), zstd_huffman_enabled(), zlib_dynamic_enabled());
   v.waves_per_cu = st.grid_wpc[v.mode];
   return v;
 }
-constexpr int kEncModes = 11;      // ENC_LZ ... ENC_ZLIB_DYN_HC
 
 // What the per-chunk loop of a compress call adds up: the tables and the sizes of the scratch areas
 struct EncodeBatch {
@@ -705,7 +713,7 @@ int engine_enc_lz_occupancy(int dynamic_lds) {
   const int dev = wanted_device();
   int occ = -1;
   if (dev < 0 || hipSetDevice(dev) != hipSuccess) return -1;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)k_encode_streams_t<ENC_LZ>, 64 * ENC_WAVES, (size_t)dynamic_lds) != hipSuccess) { (void)hipGetLastError(); return -1; }
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, grid_kernels()[ENC_LZ].fn, 64 * ENC_WAVES, (size_t)dynamic_lds) != hipSuccess) { (void)hipGetLastError(); return -1; }
   return occ;
 #endif
 }
@@ -786,24 +794,33 @@ static int compress_entries(const CompressParams* params, bool per_chunk, int n,
   const size_t clear_bytes = cv.off - o_results;
   const size_t o_filt = cv.take(B.filt_bytes + 256);
   const size_t o_stage = cv.take(B.stage_bytes + 256);
-  // Zstd: the predefined FSE tables and one sequence scratch per persistent wave - per group that wants them (Zstd, zlib with dynamic codes)
-  size_t o_ctabs[kEncModes] = {0}, o_seqbufs[kEncModes] = {0};
-  bool any_zstd = false;
-  for (const EngineState::EncGroup& g : tc.groups) {
-    const EncVariant& v = B.variants[g.mode];
-    const size_t zwaves = (v.zstd || v.zdyn) ? (size_t)(st.cus > 0 ? st.cus : 256) * (size_t)v.waves_per_cu : 0;
-    if (v.zstd) { o_ctabs[g.mode] = cv.take(sizeof(zenc::CTabs) + 64); any_zstd = true; }
-    if (zwaves) o_seqbufs[g.mode] = cv.take(zwaves * (v.zdyn ? (size_t)ZD_SCRATCH_U64 : (size_t)ZS_SEQCAP) * sizeof(uint64_t) + 64);
+  // pinned memory, behind the tables of tc.begin(): what goes up with the call and what comes back from it
+  const size_t p_chunks = pc.take(sizeof(ChunkDesc) * (size_t)n);
+  const size_t p_results = pc.take(sel_bytes + sizeof(int32_t) * (size_t)n);
+  const size_t p_first = sel ? pc.take(sizeof(int32_t) * ((size_t)sel->nchunks + 1 + (size_t)n)) : 0;      // the range table and the entries' outcomes so far
+  const size_t p_cost = pc.take(sizeof(uint32_t) * kCostWords * ngrp);
+  const size_t p_offsets = packed ? pc.take(sizeof(uint64_t) * ((size_t)n + 1)) : 0;
+  // The groups of the call, for everything behind this layout.  Zstd: the predefined FSE tables; Zstd and zlib with dynamic codes: one sequence
+  // scratch per persistent wave
+  // (offsets: o_ctabs, o_seqbufs - 0: the variant wants none -, the group's ticket words and cost words in the device arena; the cost words in pinned memory)
+  struct GroupRun { const EngineState::EncGroup* g; EncVariant v; size_t o_ctabs, o_seqbufs, o_ticket, o_cost, p_cost; };
+  std::vector<GroupRun> runs;
+  for (size_t k = 0; k < tc.groups.size(); k++) {
+    GroupRun r{&tc.groups[k], B.variants[tc.groups[k].mode], 0, 0, o_results + ticket_offset((size_t)n) + sizeof(uint32_t) * kEncTicketWords * k,
+               o_cost + sizeof(uint32_t) * kCostWords * k, p_cost + sizeof(uint32_t) * kCostWords * k};
+    const size_t zwaves = (size_t)(st.cus > 0 ? st.cus : 256) * (size_t)r.v.waves_per_cu;
+    if (kEncMode[r.v.mode].family == FAM_ZSTD) r.o_ctabs = cv.take(sizeof(zenc::CTabs) + 64);
+    if (enc_seq_words(r.v.mode)) r.o_seqbufs = cv.take(zwaves * enc_seq_words(r.v.mode) * sizeof(uint64_t) + 64);
+    runs.push_back(r);
   }
   const size_t o_offsets = (packed || sel) ? cv.take(sizeof(uint64_t) * ((size_t)n + 1)) : 0;      // packed: the offset table k_packed_layout writes
   const size_t o_first = sel ? cv.take(sizeof(int32_t) * ((size_t)sel->nchunks + 1)) : 0;         // candidates: where every caller chunk's entries begin
   if (st.dev.ensure(cv.off)) return -1;
   uint8_t* D = st.dev.base;
-  if (any_zstd) {
-    static zenc::CTabs host_tabs; static bool built = false;
-    if (!built) { zenc::build_predefined(host_tabs); built = true; }
-    for (const EngineState::EncGroup& g : tc.groups)
-      if (B.variants[g.mode].zstd) HIP_TRY(hipMemcpyAsync(D + o_ctabs[g.mode], &host_tabs, sizeof host_tabs, hipMemcpyHostToDevice, stream));
+  for (const GroupRun& r : runs) {
+    if (!r.o_ctabs) continue;
+    static const zenc::CTabs host_tabs = [] { zenc::CTabs t; zenc::build_predefined(t); return t; }();
+    HIP_TRY(hipMemcpyAsync(D + r.o_ctabs, &host_tabs, sizeof host_tabs, hipMemcpyHostToDevice, stream));
   }
   // ---- stage the inputs of a host-pointer call, point every chunk at its scratch ----
   if (io.reserve(st.io)) return -1;
@@ -821,11 +838,6 @@ static int compress_entries(const CompressParams* params, bool per_chunk, int n,
   }
   ht.mark(1);     // queues, workspace, pointer patching
   // ---- upload the tables ----
-  const size_t p_chunks = pc.take(sizeof(ChunkDesc) * (size_t)n);
-  const size_t p_results = pc.take(sel_bytes + sizeof(int32_t) * (size_t)n);
-  const size_t p_first = sel ? pc.take(sizeof(int32_t) * ((size_t)sel->nchunks + 1 + (size_t)n)) : 0;      // ... and the entries' outcomes so far
-  const size_t p_cost = pc.take(sizeof(uint32_t) * kCostWords * ngrp);
-  const size_t p_offsets = packed ? pc.take(sizeof(uint64_t) * ((size_t)n + 1)) : 0;
   if (st.pin.ensure(pc.off)) return -1;
   uint8_t* P = st.pin.base;
   memcpy(P + p_chunks, chunks.data(), sizeof(ChunkDesc) * (size_t)n);
@@ -842,7 +854,6 @@ static int compress_entries(const CompressParams* params, bool per_chunk, int n,
 
   ChunkDesc* d_chunks = (ChunkDesc*)(D + o_chunks); BlockDesc* d_blocks = tc.d_blocks(); StreamDesc* d_streams = (StreamDesc*)(D + o_streams);
   int32_t* d_blkoff = (int32_t*)(D + o_blkoff); int32_t* d_results = (int32_t*)(D + o_results);
-  uint32_t* d_tickets = (uint32_t*)(D + o_results + ticket_offset((size_t)n));
   ht.mark(2);     // table copies to pinned memory + upload enqueues
   // ---- launch ----
   if (nstr) hipLaunchKernelGGL(k_encode_plan, grid1(nblk, 256), dim3(256), 0, stream, d_chunks, d_blocks, d_streams, (int)nblk);
@@ -857,28 +868,21 @@ static int compress_entries(const CompressParams* params, bool per_chunk, int n,
   }
   // one launch per group: its own queues, ticket words, cost words and scratch; the tables of chunks, blocks and streams and the
   // block-ready flags are the batch's (a group's queues name the blocks of its own chunks only)
-  for (size_t k = 0; nstr && k < tc.groups.size(); k++) {
-    const EngineState::EncGroup& g = tc.groups[k];
-    const EncVariant& v = B.variants[g.mode];
-    if (g.ntasks <= 0) continue;
-    ProfScope ps(st, stream, v.name);
+  for (const GroupRun& r : runs) {
+    const EngineState::EncGroup& g = *r.g;
+    if (!nstr || g.ntasks <= 0) continue;
+    ProfScope ps(st, stream, enc_profile_name(r.v.mode));
     const int32_t* d_qoff = tc.d_qoff() + g.q_at; const int32_t* d_qlist = d_qoff + 9; const int32_t* d_shoff = tc.d_qoff() + g.sh_at;
-    uint32_t* d_ticket = d_tickets + kEncTicketWords * k;
-    uint32_t* d_cost = (uint32_t*)(D + o_cost) + kCostWords * k;
+    uint32_t* d_ticket = (uint32_t*)(D + r.o_ticket);
+    uint32_t* d_cost = (uint32_t*)(D + r.o_cost);
     uint32_t* d_ready = (uint32_t*)(D + o_ready);
-    uint64_t* d_seqbufs = (v.zstd || v.zdyn) ? (uint64_t*)(D + o_seqbufs[g.mode]) : nullptr;
-    const zenc::CTabs* d_ctabs = v.zstd ? (const zenc::CTabs*)(D + o_ctabs[g.mode]) : nullptr;
-    const int detect = v.detect;
-    const dim3 grid(persistent_grid(st, (size_t)g.ntasks, v.waves_per_cu)), block(64 * ENC_WAVES);
+    uint64_t* d_seqbufs = r.o_seqbufs ? (uint64_t*)(D + r.o_seqbufs) : nullptr;
+    const zenc::CTabs* d_ctabs = r.o_ctabs ? (const zenc::CTabs*)(D + r.o_ctabs) : nullptr;
+    const int detect = (kEncMode[r.v.mode].family == FAM_LZ && periodic_enabled()) ? 1 : 0;     // the periodic-plane shortcut of the shuffle tasks
+    const dim3 grid(persistent_grid(st, (size_t)g.ntasks, r.v.waves_per_cu)), block(64 * ENC_WAVES);
     BAMD_STREAM_PROFILE(prof, "BLOSC_AMD_ENC_PROFILE", nstr);
     BAMD_WAVE_PROFILE(wprof, "BLOSC_AMD_ENC_PROFILE", grid.x);
-#define BAMD_ENC_LAUNCH(MODE) case MODE: hipLaunchKernelGGL(k_encode_streams_t<MODE>, grid, block, 0, stream, d_streams, d_ticket, d_qlist, d_qoff, d_shoff, d_chunks, d_blocks, d_ready, d_cost, st.single_queue ? 1 : 0, d_seqbufs, d_ctabs, detect BAMD_PROF_ARG(prof) BAMD_PROF_ARG(wprof)); break
-    switch (g.mode) {
-      BAMD_ENC_LAUNCH(ENC_ZSTD_HCH); BAMD_ENC_LAUNCH(ENC_ZSTD_HC); BAMD_ENC_LAUNCH(ENC_ZSTD_TH); BAMD_ENC_LAUNCH(ENC_ZSTD_T); BAMD_ENC_LAUNCH(ENC_ZSTD);
-      BAMD_ENC_LAUNCH(ENC_ZLIB_DYN_HC); BAMD_ENC_LAUNCH(ENC_ZLIB_DYN); BAMD_ENC_LAUNCH(ENC_ZLIB_HC); BAMD_ENC_LAUNCH(ENC_ZLIB);
-      BAMD_ENC_LAUNCH(ENC_HC); BAMD_ENC_LAUNCH(ENC_LZ);
-    }
-#undef BAMD_ENC_LAUNCH
+    hipLaunchKernelGGL(enc_kernel(r.v.mode), grid, block, 0, stream, d_streams, d_ticket, d_qlist, d_qoff, d_shoff, d_chunks, d_blocks, d_ready, d_cost, st.single_queue ? 1 : 0, d_seqbufs, d_ctabs, detect BAMD_PROF_ARG(prof) BAMD_PROF_ARG(wprof));
   }
   if (!packed && !sel) {
     ProfScope ps(st, stream, "k_chunk_scan");
@@ -923,17 +927,16 @@ static int compress_entries(const CompressParams* params, bool per_chunk, int n,
   HIP_TRY(hipStreamSynchronize(stream));
   ht.mark(4);     // waiting for the device
   prof_collect(st);
-  for (size_t k = 0; nstr && k < tc.groups.size(); k++)      // every group's launch took what was queued for it
-    if (check_done((const uint32_t*)(P + p_cost) + kCostWords * k, (size_t)tc.groups[k].ntasks, 0, "compress")) return -1;
-  if (packed) for (int i = 0; i <= n; i++) packed->offsets[i] = (size_t)((const uint64_t*)(P + p_offsets))[i];
-  if (nstr) {
-    uint32_t taken = 0, nshuf = 0;
-    for (size_t k = 0; k < tc.groups.size(); k++) {
-      taken += ((const uint32_t*)(P + p_cost) + kCostWords * k)[256];
-      nshuf += (uint32_t)tc.queues[tc.groups[k].sh_at + 8];      // shoff[8]: the entries of the group's eight shuffle lists
-    }
-    g_last_enc_tasks[0] = taken; g_last_enc_tasks[1] = (uint32_t)nstr; g_last_enc_tasks[2] = nshuf;
+  uint32_t taken = 0, nshuf = 0;
+  for (const GroupRun& r : runs) {
+    if (!nstr) break;
+    const uint32_t* cost = (const uint32_t*)(P + r.p_cost);
+    if (check_done(cost, (size_t)r.g->ntasks, 0, "compress")) return -1;      // every group's launch took what was queued for it
+    taken += cost[256];
+    nshuf += (uint32_t)tc.queues[r.g->sh_at + 8];      // shoff[8]: the entries of the group's eight shuffle lists
   }
+  if (packed) for (int i = 0; i <= n; i++) packed->offsets[i] = (size_t)((const uint64_t*)(P + p_offsets))[i];
+  if (nstr) { g_last_enc_tasks[0] = taken; g_last_enc_tasks[1] = (uint32_t)nstr; g_last_enc_tasks[2] = nshuf; }
   tc.commit(B.key);
   if (feedback && nstr >= 4096) { memcpy(st.enc_cost, P + p_cost, sizeof st.enc_cost); st.enc_cost_valid = true; }   // small calls say little
   const int32_t* r = (const int32_t*)(P + p_results + sel_bytes);

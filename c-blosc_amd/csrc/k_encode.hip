@@ -58,20 +58,40 @@ namespace bamd {
 #include "enc_zlib.h"
 #include "enc_shuffle.h"
 
-// one stream, not inlined into the queue loop (see decode_one_stream in k_decode.hip for why)
-// MODE: 0 = LZ4 / BloscLZ, 1 = Zstd, 2 = Zlib, 3 = LZ4 with the LZ4HC-grade search, 4 = Zstd with per-block sequence tables -
-// a batch has ONE codec, so every kernel carries only its own code path
-// 5 = Zstd with per-block tables behind the LZ4HC-grade search, 6 = zlib behind the LZ4HC-grade search
-// 7 / 8 = 4 / 5 with Huffman-coded literals
-// 9 / 10 = zlib with dynamic Huffman codes (two passes), plain match finder / LZ4HC-grade search
-enum { ENC_LZ = 0, ENC_ZSTD = 1, ENC_ZLIB = 2, ENC_HC = 3, ENC_ZSTD_T = 4, ENC_ZSTD_HC = 5, ENC_ZLIB_HC = 6, ENC_ZSTD_TH = 7, ENC_ZSTD_HCH = 8,
-       ENC_ZLIB_DYN = 9, ENC_ZLIB_DYN_HC = 10 };
-constexpr bool enc_mode_hc(int mode) { return mode == ENC_HC || mode == ENC_ZSTD_HC || mode == ENC_ZLIB_HC || mode == ENC_ZSTD_HCH || mode == ENC_ZLIB_DYN_HC; }
-constexpr bool enc_mode_zlib(int mode) { return mode == ENC_ZLIB || mode == ENC_ZLIB_HC || mode == ENC_ZLIB_DYN || mode == ENC_ZLIB_DYN_HC; }
-constexpr bool enc_mode_zstd(int mode) { return mode == ENC_ZSTD || mode == ENC_ZSTD_T || mode == ENC_ZSTD_HC || mode == ENC_ZSTD_TH || mode == ENC_ZSTD_HCH; }
+// The modes of k_encode_streams_t, one row each - a launch serves ONE variant, so every kernel carries only its own code path.  A row says which
+// writer the mode ends in (LZ: LZ4 / BloscLZ by the stream's format) and what stands in front of or inside it: `search` the LZ4HC-grade search
+// (enc_lz.h) instead of the plain match finder, `tables` Zstd sequence tables made per block instead of the predefined ones, `huffman`
+// Huffman-coded Zstd literals, `dynamic` zlib with dynamic Huffman codes (two passes).  Everything else that has to know a mode - the
+// dispatch, LDS, register budget and scratch below, the host's grid table, its choice of a variant and its launch (engine.hip) - reads the row.
+// The rows' order is the modes' numbering (kernel symbols, profiles/ and scripts/make_traffic_json.py count on it): new rows go to the end.
+enum { FAM_LZ, FAM_ZSTD, FAM_ZLIB };
+struct EncMode { const char* name; int family; bool search, tables, huffman, dynamic; };
+//    mode             family    search tables huffman dynamic
+#define BAMD_ENC_MODES(ROW) \
+  ROW(ENC_LZ,          FAM_LZ,   false, false, false, false) \
+  ROW(ENC_ZSTD,        FAM_ZSTD, false, false, false, false) \
+  ROW(ENC_ZLIB,        FAM_ZLIB, false, false, false, false) \
+  ROW(ENC_HC,          FAM_LZ,   true,  false, false, false) \
+  ROW(ENC_ZSTD_T,      FAM_ZSTD, false, true,  false, false) \
+  ROW(ENC_ZSTD_HC,     FAM_ZSTD, true,  true,  false, false) \
+  ROW(ENC_ZLIB_HC,     FAM_ZLIB, true,  false, false, false) \
+  ROW(ENC_ZSTD_TH,     FAM_ZSTD, false, true,  true,  false) \
+  ROW(ENC_ZSTD_HCH,    FAM_ZSTD, true,  true,  true,  false) \
+  ROW(ENC_ZLIB_DYN,    FAM_ZLIB, false, false, false, true)  \
+  ROW(ENC_ZLIB_DYN_HC, FAM_ZLIB, true,  false, false, true)
+#define BAMD_ENC_ENUMERATOR(NAME, ...) NAME,
+#define BAMD_ENC_ROW(NAME, ...) {"k_encode_streams_t<" #NAME ">", __VA_ARGS__},
+enum { BAMD_ENC_MODES(BAMD_ENC_ENUMERATOR) kEncModes };
+constexpr EncMode kEncMode[kEncModes] = {BAMD_ENC_MODES(BAMD_ENC_ROW)};      // (name: the kernel instance with the enumerator spelled out)
+#undef BAMD_ENC_ENUMERATOR
+#undef BAMD_ENC_ROW
+// sequence scratch of one persistent wave in 64-bit words: the Zstd writers' sequences, the tokens of dynamic zlib's first pass.  The kernel
+// strides by it, the host allocates by it.
+constexpr uint32_t enc_seq_words(int mode) { return kEncMode[mode].family == FAM_ZSTD ? ZS_SEQCAP : (kEncMode[mode].dynamic ? ZD_SCRATCH_U64 : 0u); }
 #ifndef BAMD_ENC_HELP
 #define BAMD_ENC_HELP 256     // a wave whose stream's block is not shuffled yet takes shuffle tasks instead of sleeping, up to this many blocks ahead (0: never)
 #endif
+// one stream, not inlined into the queue loop (see decode_one_stream in k_decode.hip for why)
 template <int MODE>
 __device__ __attribute__((noinline)) void encode_one_stream(StreamDesc* sd_, enc_entry_t* tab_, const ChunkDesc* chunks_, uint32_t* blk_ready_, int lane,
                                                             const BlockDesc* blocks_, uint32_t sid_, uint32_t* plane_cost_, uint64_t* seqbuf_
@@ -108,17 +128,12 @@ __device__ __attribute__((noinline)) void encode_one_stream(StreamDesc* sd_, enc
   const uint64_t cost_t0 = __builtin_amdgcn_s_memtime();
   uint32_t r;
   const int32_t hint = (int32_t)uni((uint32_t)sd->result);      // < 0: the shuffle task found this plane periodic (period -hint)
-  if (MODE == ENC_ZSTD) r = seqbuf ? zstd_encode_wave(uni_ptr(as_global(sd->in)), n, uni_ptr(as_global(sd->out)), cap, clevel, tab, (BAMD_GAS uint64_t*)seqbuf, lane EPROF_PASS) : 0u;
-  else if (MODE == ENC_ZSTD_HCH) r = seqbuf ? zstd_encode_wave<true, true, true>(uni_ptr(as_global(sd->in)), n, uni_ptr(as_global(sd->out)), cap, clevel, tab, (BAMD_GAS uint64_t*)seqbuf, lane EPROF_PASS) : 0u;
-  else if (MODE == ENC_ZSTD_TH) r = seqbuf ? zstd_encode_wave<true, false, true>(uni_ptr(as_global(sd->in)), n, uni_ptr(as_global(sd->out)), cap, clevel, tab, (BAMD_GAS uint64_t*)seqbuf, lane EPROF_PASS) : 0u;
-  else if (MODE == ENC_ZSTD_HC) r = seqbuf ? zstd_encode_wave<true, true>(uni_ptr(as_global(sd->in)), n, uni_ptr(as_global(sd->out)), cap, clevel, tab, (BAMD_GAS uint64_t*)seqbuf, lane EPROF_PASS) : 0u;
-  else if (MODE == ENC_ZLIB_DYN) r = seqbuf ? zlib_dyn_encode_wave<false>(uni_ptr(as_global(sd->in)), n, uni_ptr(as_global(sd->out)), cap, clevel, tab, (BAMD_GAS uint64_t*)seqbuf, lane EPROF_PASS) : 0u;
-  else if (MODE == ENC_ZLIB_DYN_HC) r = seqbuf ? zlib_dyn_encode_wave<true>(uni_ptr(as_global(sd->in)), n, uni_ptr(as_global(sd->out)), cap, clevel, tab, (BAMD_GAS uint64_t*)seqbuf, lane EPROF_PASS) : 0u;
-  else if (MODE == ENC_ZLIB_HC) r = zlib_encode_wave<true>(uni_ptr(as_global(sd->in)), n, uni_ptr(as_global(sd->out)), cap, clevel, tab, lane EPROF_PASS);
-  else if (MODE == ENC_ZSTD_T) r = seqbuf ? zstd_encode_wave<true>(uni_ptr(as_global(sd->in)), n, uni_ptr(as_global(sd->out)), cap, clevel, tab, (BAMD_GAS uint64_t*)seqbuf, lane EPROF_PASS) : 0u;
-  else if (MODE == ENC_ZLIB) r = zlib_encode_wave(uni_ptr(as_global(sd->in)), n, uni_ptr(as_global(sd->out)), cap, clevel, tab, lane EPROF_PASS);
+  constexpr EncMode M = kEncMode[MODE];
+  if (M.family == FAM_ZSTD) r = seqbuf ? zstd_encode_wave<M.tables, M.search, M.huffman>(uni_ptr(as_global(sd->in)), n, uni_ptr(as_global(sd->out)), cap, clevel, tab, (BAMD_GAS uint64_t*)seqbuf, lane EPROF_PASS) : 0u;
+  else if (M.dynamic) r = seqbuf ? zlib_dyn_encode_wave<M.search>(uni_ptr(as_global(sd->in)), n, uni_ptr(as_global(sd->out)), cap, clevel, tab, (BAMD_GAS uint64_t*)seqbuf, lane EPROF_PASS) : 0u;
+  else if (M.family == FAM_ZLIB) r = zlib_encode_wave<M.search>(uni_ptr(as_global(sd->in)), n, uni_ptr(as_global(sd->out)), cap, clevel, tab, lane EPROF_PASS);
   else if (hint < 0) r = emit_periodic_stream(uni_ptr(as_global(sd->in)), n, uni_ptr(as_global(sd->out)), cap, (uint32_t)-hint, uni((uint32_t)sd->fmt) == (uint32_t)FMT_LZ4, lane);
-  else if (MODE == ENC_HC) r = lz4hc_encode_wave(uni_ptr(as_global(sd->in)), n, uni_ptr(as_global(sd->out)), cap, tab, lane);
+  else if (M.search) r = lz4hc_encode_wave(uni_ptr(as_global(sd->in)), n, uni_ptr(as_global(sd->out)), cap, tab, lane);
   else if (sd->fmt == FMT_LZ4) r = BAMD_ENC_PAR ? lz4_encode_wave_auto(uni_ptr(as_global(sd->in)), n, uni_ptr(as_global(sd->out)), cap, clevel, tab, lane EPROF_PASS)
                                                 : lz_encode_wave<EF_LZ4>(uni_ptr(as_global(sd->in)), n, uni_ptr(as_global(sd->out)), cap, clevel, tab, lane EPROF_PASS);
   else r = lz_encode_wave<EF_BLOSCLZ>(uni_ptr(as_global(sd->in)), n, uni_ptr(as_global(sd->out)), cap, clevel, tab, lane EPROF_PASS);
@@ -140,14 +155,11 @@ __device__ __attribute__((noinline)) void encode_one_stream(StreamDesc* sd_, enc
 // build_encode_queues), so the bandwidth-bound transposes run underneath the latency/issue-bound match
 // finding of other waves instead of in a kernel of their own.
 // LDS of one workgroup: the match finder's table, the writers' LDS behind it (ENC_LZ: the 64 scratch dwords of the parallel LZ4 emitter, enc_lz4p.h)
-constexpr int enc_lds_bytes(int mode) {
-  return (enc_mode_hc(mode) ? HC_TAB_BYTES : ENC_TAB_BYTES) +
-         (enc_mode_zstd(mode) ? ZS_LDS_BYTES : (enc_mode_zlib(mode) ? DFL_LDS_BYTES : (mode == ENC_LZ ? ENC_SCR_BYTES : 0)));
-}
-// waves per SIMD the register allocator plans for: the 24 KiB table of the HC modes leaves room for 1.5, the Zstd modes' LDS for 5
-constexpr int enc_min_waves(int mode) {
-  return enc_mode_hc(mode) ? 2 : ((mode == ENC_ZSTD_T || mode == ENC_ZSTD_TH) ? 5 : (mode == ENC_LZ ? BAMD_ENC_LZ_MINWAVES : BAMD_ENC_MINWAVES));
-}
+constexpr int enc_tab_bytes(int mode) { return kEncMode[mode].search ? HC_TAB_BYTES : ENC_TAB_BYTES; }
+constexpr int enc_writer_lds_bytes(int mode) { return kEncMode[mode].family == FAM_ZSTD ? ZS_LDS_BYTES : (kEncMode[mode].family == FAM_ZLIB ? DFL_LDS_BYTES : (mode == ENC_LZ ? ENC_SCR_BYTES : 0)); }
+constexpr int enc_lds_bytes(int mode) { return enc_tab_bytes(mode) + enc_writer_lds_bytes(mode); }
+// waves per SIMD the register allocator plans for: the 24 KiB table of the search leaves room for 1.5, the LDS of Zstd with per-block tables for 5
+constexpr int enc_min_waves(int mode) { return kEncMode[mode].search ? 2 : (kEncMode[mode].tables ? 5 : (mode == ENC_LZ ? BAMD_ENC_LZ_MINWAVES : BAMD_ENC_MINWAVES)); }
 // upper bound of the persistent grid per CU: whole LDS granules (enc_lz.h), and no more waves than the CU has slots for.  The launch takes the
 // runtime's occupancy figure (engine.hip: query_persistent_grids), which also knows the registers the compiler really used.
 constexpr int enc_grid_bound(int mode) { return lds_workgroups_per_cu(enc_lds_bytes(mode)) < 32 ? lds_workgroups_per_cu(enc_lds_bytes(mode)) : 32; }
@@ -171,21 +183,19 @@ __global__ __launch_bounds__(64 * ENC_WAVES, enc_min_waves(MODE)) void k_encode_
 #define WPROF_BEGIN(t)
 #define WPROF_END(acc, t)
 #endif
-  constexpr bool ZSTD = enc_mode_zstd(MODE);
-  constexpr int TABBYTES = enc_mode_hc(MODE) ? HC_TAB_BYTES : ENC_TAB_BYTES;      // the match finder's table; the writers' LDS sits behind it
+  constexpr bool ZSTD = kEncMode[MODE].family == FAM_ZSTD;
+  constexpr uint32_t SEQWORDS = enc_seq_words(MODE);
+  constexpr int TABBYTES = enc_tab_bytes(MODE);      // the match finder's table; the writers' LDS sits behind it
   // declared in whole granules, which is what the workgroup occupies anyway: the runtime's occupancy figure divides the CU's LDS by the declared size
   // (profiles/r07b_lds_granule.txt) and is the resident count only then
   __shared__ __attribute__((aligned(16))) enc_entry_t tabs[ENC_WAVES][lds_occupied(enc_lds_bytes(MODE)) / 4];
   static_assert(ENC_WAVES == 1, "one stream per wave, one wave per workgroup");
-  static_assert(lds_occupied(enc_lds_bytes(MODE)) * enc_grid_bound(MODE) <= LDS_BYTES_PER_CU, "the workgroups of one CU fit its LDS, granule by granule");
   const int lane = threadIdx.x & 63;
-  uint64_t* seqbuf = nullptr;
   if (ZSTD) {       // the predefined FSE tables of the sequence coder, once per persistent wave
     const uint32_t* g = (const uint32_t*)ctabs;
     for (uint32_t k = (uint32_t)lane; k < sizeof(zenc::CTabs) / 4u; k += 64u) tabs[0][TABBYTES / 4 + k] = g[k];
-    seqbuf = seqbufs + (size_t)blockIdx.x * ZS_SEQCAP;
   }
-  if (MODE == ENC_ZLIB_DYN || MODE == ENC_ZLIB_DYN_HC) seqbuf = seqbufs + (size_t)blockIdx.x * ZD_SCRATCH_U64;   // the tokens of the first pass
+  uint64_t* seqbuf = SEQWORDS ? seqbufs + (size_t)blockIdx.x * SEQWORDS : nullptr;      // this wave's sequence scratch
   // HW_REG_XCC_ID[3:0]; queue 0 for everybody in the single-queue fallback (no in-kernel hand-offs there)
   const uint32_t xcc = single_queue ? 0u : (__builtin_amdgcn_s_getreg((3 << 11) | 20) & 7u);
   const uint32_t qbase = (uint32_t)qoff[xcc], qlen = (uint32_t)qoff[xcc + 1] - qbase;

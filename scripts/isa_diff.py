@@ -21,8 +21,8 @@ def functions(path):
         if name is None:
             continue
         s = line.strip()
-        if s.startswith(".Lfunc_end"):
-            name = None
+        if s.startswith(".Lfunc_end") or s.startswith(".size\t" + name + ",") or s.startswith(".size " + name + ","):
+            name = None                                     # (a data symbol has no .Lfunc_end: its body ends at its .size line)
             continue
         if not s or s.startswith((";", ".loc", ".file", ".cfi", ".p2align")):
             continue

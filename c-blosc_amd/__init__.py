@@ -1,7 +1,7 @@
 """c-blosc_amd — Python-side loader for libblosc_amd.so (ctypes; test / bench plumbing only).
 
 The product is the C-ABI shared library built from ``csrc/`` (see ``include/blosc.h`` and
-``include/blosc_gpu.h``, ``include/blosc_gpu_packed.h``, ``include/blosc_gpu_params.h``, ``include/blosc_gpu_select.h``, ``include/blosc_gpu_getitem.h``, ``include/blosc_gpu_checksum.h``).  This module only locates it, declares argument types and offers small
+``include/blosc_gpu.h``, ``include/blosc_gpu_packed.h``, ``include/blosc_gpu_params.h``, ``include/blosc_gpu_select.h``, ``include/blosc_gpu_getitem.h``, ``include/blosc_gpu_take.h``, ``include/blosc_gpu_checksum.h``).  This module only locates it, declares argument types and offers small
 numpy conveniences that mirror how the reference is driven from Python through ctypes
 (SURVEY.md §A.8).  There is no CPU implementation here: if the library is missing, ``load()``
 raises; if there is no GPU, the library's calls return errors.
@@ -44,6 +44,9 @@ PARAMS_SYMBOLS = [      # include/blosc_gpu_params.h
 ]
 SELECT_SYMBOLS = [      # include/blosc_gpu_select.h
     "blosc_gpu_compress_batch_select", "blosc_gpu_compress_packed_select",
+]
+TAKE_SYMBOLS = [        # include/blosc_gpu_take.h
+    "blosc_gpu_take_batch", "blosc_gpu_take_packed",
 ]
 CHECKSUM_ADLER32, CHECKSUM_CRC32 = 1, 2
 COMPCODES = {b"blosclz": 0, b"lz4": 1, b"lz4hc": 2, b"snappy": 3, b"zlib": 4, b"zstd": 5}      # include/blosc.h
@@ -148,6 +151,9 @@ def _signatures():
         # include/blosc_gpu_getitem.h
         "blosc_gpu_getitem_batch": ([i, pp, i, ip, ip, ip, pp, ip, vp], i),
         "blosc_gpu_getitem_packed": ([i, vp, sz, zp, i, ip, ip, ip, vp, sz, zp, ip, vp], i),
+        # include/blosc_gpu_take.h
+        "blosc_gpu_take_batch": ([i, pp, sz, sz, vp, vp, vp, ip, zp, vp], i),
+        "blosc_gpu_take_packed": ([i, vp, sz, zp, sz, sz, vp, vp, vp, ip, zp, vp], i),
         # include/blosc_gpu_checksum.h
         "blosc_gpu_checksum_batch": ([i, i, pp, zp, P(C.c_uint), vp], i),
         "blosc_gpu_checksum_packed": ([i, i, vp, sz, zp, zp, P(C.c_uint), vp], i),
@@ -178,7 +184,7 @@ def declare(L):
     return L
 
 
-declare_packed = declare_params = declare_select = declare_getitem = declare_checksum = declare      # the names from when every header had a function of its own
+declare_packed = declare_params = declare_select = declare_getitem = declare_take = declare_checksum = declare      # the names from when every header had a function of its own
 
 
 # ---- numpy conveniences (host buffers through the stock entry points) --------------------------
@@ -343,6 +349,43 @@ class ItemRanges:
 
     def results(self):
         return list(self.res)
+
+
+class RowTake:
+    """Helper for include/blosc_gpu_take.h: rows of row_bytes bytes of many chunks by an index table on the device.
+
+    batch(): chunk i at src_ptrs[i].  packed(): the chunks in a container with its offset table [n + 1].  Both take the device addresses
+    of the int64 indices, of dest (nidx * row_bytes bytes) and of the int32 status table (0 / None: no status wanted) and return the
+    call's answer.  chunk_rows() gives every chunk's row count (or its negative census code), failed() the rows with a negative status.
+    The library handle may be given (an emulator build in the CPU tests); default: the product."""
+
+    def __init__(self, row_bytes, lib=None):
+        self.row_bytes = row_bytes
+        self.lib = lib if lib is not None else load()
+        self.rows = (C.c_int * 1)()
+        self.nchunks = 0
+        self.nfailed = C.c_size_t(0)
+
+    def _outputs(self, nchunks):
+        self.nchunks = nchunks
+        self.rows = (C.c_int * max(nchunks, 1))()
+        self.nfailed = C.c_size_t(0)
+
+    def batch(self, src_ptrs, index, nidx, dest, status=None, stream=None):
+        self._outputs(len(src_ptrs))
+        return self.lib.blosc_gpu_take_batch(self.nchunks, (C.c_void_p * max(self.nchunks, 1))(*src_ptrs), self.row_bytes, nidx, index, dest, status,
+                                             self.rows, C.byref(self.nfailed), stream)
+
+    def packed(self, container, containersize, offsets, index, nidx, dest, status=None, stream=None):
+        self._outputs(len(offsets) - 1)
+        return self.lib.blosc_gpu_take_packed(self.nchunks, container, containersize, (C.c_size_t * (self.nchunks + 1))(*offsets), self.row_bytes, nidx,
+                                              index, dest, status, self.rows, C.byref(self.nfailed), stream)
+
+    def chunk_rows(self):
+        return list(self.rows)[:self.nchunks]
+
+    def failed(self):
+        return int(self.nfailed.value)
 
 
 def checksums(kind, ptrs, sizes, lib=None, stream=None):

@@ -1,5 +1,5 @@
 // blosc_api.hip — the exported C ABI (include/blosc.h, include/blosc_gpu.h, include/blosc_gpu_packed.h, include/blosc_gpu_params.h,
-// include/blosc_gpu_getitem.h, include/blosc_gpu_checksum.h).
+// include/blosc_gpu_getitem.h, include/blosc_gpu_take.h, include/blosc_gpu_checksum.h).
 //
 // Host-side mirror of the reference's public layer (blosc/blosc.c:1282-1703, :1951-2317):
 // process globals, the per-call environment overrides, name/code tables and cbuffer introspection
@@ -20,6 +20,7 @@
 #include "../../include/blosc_gpu_params.h"
 #include "../../include/blosc_gpu_select.h"
 #include "../../include/blosc_gpu_getitem.h"
+#include "../../include/blosc_gpu_take.h"
 #include "../../include/blosc_gpu_checksum.h"
 #include "blosc_format.h"
 #include "engine.h"
@@ -48,6 +49,8 @@ static bool codec_built(int code) { return code == BLOSC_BLOSCLZ || code == BLOS
 //                                           then every array must be there.  `dest` may be NULL: the compress calls size (destsize must be 0
 //                                           then), the reading calls size whatever destsize says.
 //   getitem_batch                           a negative count is unusable, nranges == 0 answers 0, then every array (`src` when there are chunks).
+//   take_*                                  take_opening(): a negative nchunks, row_bytes outside 1 ... 65536, no `index` or `dest` for nidx > 0 are
+//                                           unusable; then `src` / the container and its offsets where there are chunks; no chunks and no indices answer 0.
 //   checksum_*                              checksum_opening(): `kind` first, then nruns <= 0 answers 0; then the arrays (`length` may be NULL,
 //                                           the container where every run is empty).
 //   cbuffer_sizes_batch                     n < 0 is unusable, n == 0 answers 0, then `src`; every output may be NULL.
@@ -587,6 +590,34 @@ int blosc_gpu_getitem_packed(int nchunks, const void* container, size_t containe
   const PackedBuffer pk{dest, dest ? destsize : 0, 0, dest_offsets_out};
   return getitem_call(nchunks, jobs_from_spans(nchunks, container, containersize, offsets, nullptr, BLOSC_MIN_HEADER_LENGTH), nranges, chunk, start, nitems,
                       nullptr, result_out, stream, &pk);
+}
+
+// ---- rows by a device index table (include/blosc_gpu_take.h) ---------------------------------------
+static int take_opening(int nchunks, size_t row_bytes, size_t nidx, const void* index, const void* dest) {
+  if (nchunks < 0 || row_bytes < 1 || row_bytes > 65536) return -1;
+  if (nidx && (!index || !dest)) return -1;
+  return kGo;
+}
+static int take_call(int nchunks, const Table<Job>& jobs, size_t row_bytes, size_t nidx, const int64_t* index, void* dest, int* status,
+                     int* chunk_rows_out, size_t* failed_out, void* stream) {
+  if (!jobs) return -1;
+  if (nchunks == 0 && nidx == 0) return 0;      // no chunk to count, no row to answer
+  return engine_take(nchunks, jobs.get(), row_bytes, nidx, index, dest, status, chunk_rows_out, failed_out, (hipStream_t)stream);
+}
+int blosc_gpu_take_batch(int nchunks, const void* const* src, size_t row_bytes, size_t nidx, const int64_t* index, void* dest, int* status,
+                         int* chunk_rows_out, size_t* failed_out, void* stream) {
+  const int c = take_opening(nchunks, row_bytes, nidx, index, dest);
+  if (c != kGo) return c;
+  if (nchunks > 0 && !src) return -1;
+  return take_call(nchunks, jobs_from_arrays(nchunks, src, nullptr, nullptr, nullptr), row_bytes, nidx, index, dest, status, chunk_rows_out, failed_out, stream);
+}
+int blosc_gpu_take_packed(int nchunks, const void* container, size_t containersize, const size_t* offsets, size_t row_bytes, size_t nidx,
+                          const int64_t* index, void* dest, int* status, int* chunk_rows_out, size_t* failed_out, void* stream) {
+  const int c = take_opening(nchunks, row_bytes, nidx, index, dest);
+  if (c != kGo) return c;
+  if (nchunks > 0 && (!container || !offsets)) return -1;
+  return take_call(nchunks, jobs_from_spans(nchunks, container, containersize, offsets, nullptr, BLOSC_MIN_HEADER_LENGTH), row_bytes, nidx, index, dest, status,
+                   chunk_rows_out, failed_out, stream);
 }
 
 // ---- adler32 / crc32 of many runs (include/blosc_gpu_checksum.h) ---------------------------------------

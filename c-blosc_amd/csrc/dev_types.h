@@ -101,6 +101,22 @@ struct GatherRange {
   int32_t pad_;
 };
 
+// The tables of k_take_mark / k_take_gather (k_take.hip; include/blosc_gpu_take.h).  TakeChunk[nchunks + 1]: the call's chunks as ONE array of
+// rows - chunk c holds rows [row_first, next row_first) and the entries [block_first, next block_first) of the block table, one per block of
+// `blocksize` bytes; a MEMCPYED chunk has blocksize 0 and one entry.  The last entry closes both prefixes (row_first: the call's rows).
+struct TakeChunk {
+  int64_t row_first;
+  int32_t block_first;
+  int32_t blocksize;
+};
+// TakeBlock, one per block and pass: where the block's first byte lies - in a slot of decoded blocks, its verdict the status word `status`;
+// for a MEMCPYED chunk the payload, status -1: nothing to ask - or nullptr: not in this pass (another pass's chunk, or a block no row touches).
+struct TakeBlock {
+  const uint8_t* base;
+  int32_t status;
+  int32_t pad_;
+};
+
 // Negative per-chunk status codes written by kernels (host maps them to the reference's
 // return values, blosc/blosc.c:762-782): -1 bad csize chain / bounds, -2 codec produced wrong size.
 enum : int32_t { ST_OK = 0, ST_BADCHAIN = -1, ST_BADCODEC = -2 };

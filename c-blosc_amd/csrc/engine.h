@@ -72,6 +72,12 @@ struct ItemRange { int chunk, start, nitems; void* dst; };
 int engine_getitem_batch(int nchunks, const Job* chunks, int nranges, const ItemRange* ranges, int* results, hipStream_t stream,
                          const PackedBuffer* packed = nullptr);
 void engine_getitem_pass_bytes(size_t bytes);   // test hook: decoded bytes per pass of engine_getitem_batch (0: the default, 256 MiB)
+// Rows of row_bytes bytes by a DEVICE index table (include/blosc_gpu_take.h): the chunks are one array of rows, row index[k] goes to
+// dest + k * row_bytes and status[k] (device, may be nullptr) is row_bytes or the row's negative code.  chunk_rows_out (host, may be nullptr):
+// every chunk's rows or its negative census code - with one of those the call answers -1 and decodes nothing.  failed_out (host, may be
+// nullptr): the rows with a negative status.  The passes are engine_getitem_batch's, under the same bound.
+int engine_take(int nchunks, const Job* chunks, size_t row_bytes, size_t nidx, const int64_t* index, void* dest, int* status,
+                int* chunk_rows_out, size_t* failed_out, hipStream_t stream);
 
 // zlib's adler32 (kind 1) / crc32 (kind 2) of n runs in device memory (include/blosc_gpu_checksum.h): runs[i].src and runs[i].srcsize;
 // an empty run's pointer is never read.  digests[] is written only when the call answers 0.

@@ -25,6 +25,7 @@
 #include "k_zstd2.hip"
 #include "k_zlib.hip"
 #include "k_checksum.hip"
+#include "k_take.hip"
 
 namespace bamd {
 
@@ -1445,14 +1446,24 @@ static size_t merge_runs(std::vector<BlockRun>& runs, size_t bs) {      // retur
   return bytes;
 }
 
-// one pass: decodes the runs of the chunks dealt to `pass` and gathers the ranges of those chunks
-static int getitem_pass(EngineState& st, int pass, std::vector<RangeChunk>& uc, const std::vector<Header>& hdrs, const std::vector<Job>& jobs,
-                        int nranges, const std::vector<PlacedRange>& pr, int* results, hipStream_t stream) {
-  // ---- lay out the runs: one table entry per block ----
-  std::vector<ChunkDesc> entries; std::vector<BlockDesc> blocks;
+// "Decode the runs of one pass", shared by getitem_pass and take_pass (which differ in their gather tables and gather kernel alone):
+// lay_out_runs, then decode_runs up to launch_decode, then - behind the caller's read_back_decode and gather launch - finish_pass.
+struct PassRuns {
+  std::vector<ChunkDesc> entries; std::vector<BlockDesc> blocks;      // one table entry per block decoded (+ the caller's extra status words)
   size_t nstr = 0, nstr_z = 0, nstr_zlib = 0, span = 0;
   bool any_filt = false;
-  DecodeLaunch L{};
+  DecodeLaunch L{}; DecodeAreas A{};
+  size_t t_gather = 0;                 // the caller's gather tables inside the pass's table area: A.extra + t_gather on the device
+  size_t p_status = 0, p_cost = 0;     // what read_back_decode brings into the pinned arena
+};
+
+// the runs of the chunks dealt to `pass`: their slots, one table entry per block.  extra_status: status words behind the blocks' that the
+// caller's gather kernel counts in (cleared and read back with them); they are entries without blocks
+static void lay_out_runs(EngineState& st, int pass, std::vector<RangeChunk>& uc, const std::vector<Header>& hdrs, int extra_status, PassRuns& R) {
+  std::vector<ChunkDesc>& entries = R.entries; std::vector<BlockDesc>& blocks = R.blocks;
+  size_t &nstr = R.nstr, &nstr_z = R.nstr_z, &nstr_zlib = R.nstr_zlib, &span = R.span;
+  bool& any_filt = R.any_filt;
+  DecodeLaunch& L = R.L;
   for (size_t k = 0; k < uc.size(); k++) {
     RangeChunk& u = uc[k];
     if (u.pass != pass) continue;
@@ -1473,20 +1484,17 @@ static int getitem_pass(EngineState& st, int pass, std::vector<RangeChunk>& uc, 
       }
     }
   }
-  const size_t n = entries.size(), nblk = blocks.size();
-  // ---- the gather table: the ranges of this pass's chunks, in the caller's order ----
-  std::vector<GatherRange> gr((size_t)nranges);
-  std::vector<uint32_t> tile_first((size_t)nranges + 1, 0);
-  for (int r = 0; r < nranges; r++) {
-    GatherRange& g = gr[(size_t)r];
-    memset(&g, 0, sizeof g);
-    const PlacedRange& p = pr[(size_t)r];
-    uint32_t tiles = 0;
-    if (p.slot >= 0 && uc[(size_t)p.slot].pass == pass) { g.nbytes = p.want; g.dst = p.dst; tiles = (p.want + GI_TILE - 1) / GI_TILE; }
-    tile_first[(size_t)r + 1] = tile_first[(size_t)r] + tiles;
-  }
-  const uint32_t ntiles = tile_first[(size_t)nranges];
-  if (!nblk && !ntiles) return 0;
+  for (int k = 0; k < extra_status; k++) { ChunkDesc c; memset(&c, 0, sizeof c); entries.push_back(c); }
+}
+
+// Queues, workspace, every table of the pass - fill_gather(host image of the caller's gather_bytes of tables), called once the slots have
+// their addresses (R.A) - in one upload, and the decode launches.  The status words are cleared whenever there is one.
+template <class FillGather>
+static int decode_runs(EngineState& st, int pass, const std::vector<RangeChunk>& uc, const std::vector<Header>& hdrs, const std::vector<Job>& jobs,
+                       PassRuns& R, size_t gather_bytes, FillGather&& fill_gather, hipStream_t stream) {
+  std::vector<ChunkDesc>& entries = R.entries; const std::vector<BlockDesc>& blocks = R.blocks;
+  const size_t n = entries.size(), nblk = blocks.size(), nstr = R.nstr, span = R.span;
+  DecodeLaunch& L = R.L; DecodeAreas& A = R.A;
   // ---- queues, as engine_decompress_batch builds them (a few blocks each time: the table cache stays the decompress path's alone) ----
   const int nq = st.single_queue ? 1 : 8;
   std::vector<int32_t> queues, zqueues;
@@ -1498,13 +1506,11 @@ static int getitem_pass(EngineState& st, int pass, std::vector<RangeChunk>& uc, 
   const size_t t_blocks = tv.take(sizeof(BlockDesc) * (nblk ? nblk : 1));
   const size_t t_queues = tv.take(sizeof(int32_t) * queues.size());
   const size_t t_zqueues = tv.take(sizeof(int32_t) * (zqueues.size() + 1));
-  const size_t t_ranges = tv.take(sizeof(GatherRange) * (size_t)nranges);
-  const size_t t_tiles = tv.take(sizeof(uint32_t) * ((size_t)nranges + 1));
+  R.t_gather = tv.take(gather_bytes);
   const size_t table_bytes = tv.off;
-  const size_t p_status = tv.take(sizeof(int32_t) * (n ? n : 1));      // (pinned only: what comes back)
-  const size_t p_cost = tv.take(sizeof(uint32_t) * kCostWords);
-  DecodeAreas A;
-  if (decode_workspace(st, DecodeShape{(int)n, nblk, nstr, any_filt ? span : 0, L.any_zstd ? span : 0, L.any_zstd, /*two_phase*/ false, /*out_bytes*/ span, table_bytes}, L, A)) return -1;
+  R.p_status = tv.take(sizeof(int32_t) * (n ? n : 1));      // (pinned only: what comes back)
+  R.p_cost = tv.take(sizeof(uint32_t) * kCostWords);
+  if (decode_workspace(st, DecodeShape{(int)n, nblk, nstr, R.any_filt ? span : 0, L.any_zstd ? span : 0, L.any_zstd, /*two_phase*/ false, /*out_bytes*/ span, table_bytes}, L, A)) return -1;
   if (st.pin.ensure(tv.off)) return -1;
   uint8_t* P = st.pin.base;
   // kernels address block j at base + j * blocksize: bias the bases so that block r.j0 lands at the run's slot
@@ -1520,44 +1526,78 @@ static int getitem_pass(EngineState& st, int pass, std::vector<RangeChunk>& uc, 
         c.filt = (c.mode & (CH_SHUFFLE | CH_BITSHUFFLE)) ? A.filt + r.off - (size_t)r.j0 * filt_block_stride(c) : nullptr;
       }
   }
-  for (int r = 0; r < nranges; r++) {
-    GatherRange& g = gr[(size_t)r];
-    if (!g.nbytes) continue;
-    const PlacedRange& p = pr[(size_t)r];
-    const RangeChunk& u = uc[(size_t)p.slot];
-    if (u.memcpyed) { g.src = (const uint8_t*)jobs[(size_t)p.slot].src + kMaxOverhead + p.lo; continue; }
-    // the run that holds block j0 (every block of the range lies in it: runs are unions of the ranges' intervals)
-    auto it = std::upper_bound(u.runs.begin(), u.runs.end(), p.j0, [](int32_t j, const BlockRun& b) { return j < b.j0; });
-    const BlockRun& run = *(it - 1);
-    g.src = A.out + run.off + (size_t)(p.lo - (int64_t)run.j0 * hdrs[(size_t)p.slot].blocksize);
-    g.status0 = run.entry0 + (p.j0 - run.j0); g.nstatus = p.j1 - p.j0;
-  }
   memcpy(P + t_chunks, entries.data(), sizeof(ChunkDesc) * n);
   memcpy(P + t_blocks, blocks.data(), sizeof(BlockDesc) * nblk);
   memcpy(P + t_queues, queues.data(), sizeof(int32_t) * queues.size());
   memcpy(P + t_zqueues, zqueues.data(), sizeof(int32_t) * zqueues.size());
-  memcpy(P + t_ranges, gr.data(), sizeof(GatherRange) * (size_t)nranges);
-  memcpy(P + t_tiles, tile_first.data(), sizeof(uint32_t) * ((size_t)nranges + 1));
+  fill_gather(P + R.t_gather);
   HIP_TRY(hipMemcpyAsync(A.extra, P, table_bytes, hipMemcpyHostToDevice, stream));
   L.d_chunks = (ChunkDesc*)(A.extra + t_chunks); L.d_blocks = (BlockDesc*)(A.extra + t_blocks);
   L.d_qoff = (const int32_t*)(A.extra + t_queues); L.d_qlist = L.d_qoff + 9;
-  L.d_zqoff = (const int32_t*)(A.extra + t_zqueues); L.d_zqlist = L.d_zqoff + 9; L.nstr_zlib = nstr_zlib;
-  L.nstr_queued = nstr - nstr_z;
-  // ---- launch, collect ----
-  if (nblk) {
-    if (clear_decode_counters(L, stream) || launch_decode(st, L, stream) || read_back_decode(L, P + p_status, P + p_cost, stream)) return -1;
+  L.d_zqoff = (const int32_t*)(A.extra + t_zqueues); L.d_zqlist = L.d_zqoff + 9; L.nstr_zlib = R.nstr_zlib;
+  L.nstr_queued = nstr - R.nstr_z;
+  if ((nblk || n) && clear_decode_counters(L, stream)) return -1;
+  if (nblk && launch_decode(st, L, stream)) return -1;
+  return 0;
+}
+
+// the pass's one synchronisation; the decode kernels took every task they were queued
+static int finish_pass(EngineState& st, const PassRuns& R, const char* what, hipStream_t stream) {
+  HIP_TRY(hipStreamSynchronize(stream));
+  prof_collect(st);
+  return R.blocks.empty() ? 0 : decode_feedback(st, R.L, st.pin.base + R.p_cost, what);
+}
+
+// one pass: decodes the runs of the chunks dealt to `pass` and gathers the ranges of those chunks
+static int getitem_pass(EngineState& st, int pass, std::vector<RangeChunk>& uc, const std::vector<Header>& hdrs, const std::vector<Job>& jobs,
+                        int nranges, const std::vector<PlacedRange>& pr, int* results, hipStream_t stream) {
+  PassRuns R;
+  lay_out_runs(st, pass, uc, hdrs, 0, R);
+  const size_t nblk = R.blocks.size();
+  // ---- the gather table: the ranges of this pass's chunks, in the caller's order ----
+  std::vector<GatherRange> gr((size_t)nranges);
+  std::vector<uint32_t> tile_first((size_t)nranges + 1, 0);
+  for (int r = 0; r < nranges; r++) {
+    GatherRange& g = gr[(size_t)r];
+    memset(&g, 0, sizeof g);
+    const PlacedRange& p = pr[(size_t)r];
+    uint32_t tiles = 0;
+    if (p.slot >= 0 && uc[(size_t)p.slot].pass == pass) { g.nbytes = p.want; g.dst = p.dst; tiles = (p.want + GI_TILE - 1) / GI_TILE; }
+    tile_first[(size_t)r + 1] = tile_first[(size_t)r] + tiles;
   }
+  const uint32_t ntiles = tile_first[(size_t)nranges];
+  if (!nblk && !ntiles) return 0;
+  // (the two tables 256 bytes apart, as every table of the pass)
+  const size_t g_tiles = align_up(sizeof(GatherRange) * (size_t)nranges, 256), gather_bytes = g_tiles + sizeof(uint32_t) * ((size_t)nranges + 1);
+  const auto fill_gather = [&](uint8_t* G) {
+    for (int r = 0; r < nranges; r++) {
+      GatherRange& g = gr[(size_t)r];
+      if (!g.nbytes) continue;
+      const PlacedRange& p = pr[(size_t)r];
+      const RangeChunk& u = uc[(size_t)p.slot];
+      if (u.memcpyed) { g.src = (const uint8_t*)jobs[(size_t)p.slot].src + kMaxOverhead + p.lo; continue; }
+      // the run that holds block j0 (every block of the range lies in it: runs are unions of the ranges' intervals)
+      auto it = std::upper_bound(u.runs.begin(), u.runs.end(), p.j0, [](int32_t j, const BlockRun& b) { return j < b.j0; });
+      const BlockRun& run = *(it - 1);
+      g.src = R.A.out + run.off + (size_t)(p.lo - (int64_t)run.j0 * hdrs[(size_t)p.slot].blocksize);
+      g.status0 = run.entry0 + (p.j0 - run.j0); g.nstatus = p.j1 - p.j0;
+    }
+    memcpy(G, gr.data(), sizeof(GatherRange) * (size_t)nranges);
+    memcpy(G + g_tiles, tile_first.data(), sizeof(uint32_t) * ((size_t)nranges + 1));
+  };
+  if (decode_runs(st, pass, uc, hdrs, jobs, R, gather_bytes, fill_gather, stream)) return -1;
+  // ---- collect ----
+  uint8_t* P = st.pin.base;
+  if (nblk && read_back_decode(R.L, P + R.p_status, P + R.p_cost, stream)) return -1;
   if (ntiles) {
     ProfScope ps(st, stream, "k_getitem_gather");
     hipLaunchKernelGGL(k_getitem_gather, dim3(persistent_grid(st, ntiles, GI_WAVES_PER_CU)), dim3(GI_THREADS), 0, stream,
-                       (const GatherRange*)(A.extra + t_ranges), (const uint32_t*)(A.extra + t_tiles), nranges, (const int32_t*)L.d_status);
+                       (const GatherRange*)(R.A.extra + R.t_gather), (const uint32_t*)(R.A.extra + R.t_gather + g_tiles), nranges, (const int32_t*)R.L.d_status);
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipStreamSynchronize(stream));
-  prof_collect(st);
+  if (finish_pass(st, R, "getitem", stream)) return -1;
   if (!nblk) return 0;
-  if (decode_feedback(st, L, P + p_cost, "getitem")) return -1;
-  const int32_t* stt = (const int32_t*)(P + p_status);
+  const int32_t* stt = (const int32_t*)(P + R.p_status);
   for (int r = 0; r < nranges; r++) {
     const GatherRange& g = gr[(size_t)r];
     for (int32_t k = 0; k < g.nstatus; k++)
@@ -1644,6 +1684,159 @@ int engine_getitem_batch(int nchunks, const Job* chunks, int nranges, const Item
   CtxGuard ctx; EngineState& st = *ctx.st;
   if (ensure_device(st)) return -1;
   return getitem_ranges(st, nchunks, chunks, nullptr, nranges, ranges, results, stream, packed, /*say*/ false);
+}
+
+// ---------------------------------------------------------------------------------------------
+// take (include/blosc_gpu_take.h): rows of the chunks by an index table that lies on the device
+// ---------------------------------------------------------------------------------------------
+// The getitem pipeline with another front end and another gather.  The indices are never brought to the host:
+//   1. one header fetch for all chunks, the census on the host (classify_for_getitem's checks, the packed form's slot checks, nbytes a
+//      multiple of row_bytes) and the chunk table (dev_types.h: TakeChunk) - a call with an unusable chunk ends here;
+//   2. k_take_mark sets a byte per block some row lies in; the flags come down, one synchronisation;
+//   3. the maximal intervals of touched blocks are the chunks' runs - merge_runs, the dealing to passes and decode_runs as in getitem_ranges;
+//   4. per pass k_take_gather over ALL indices, with a table over the blocks of the call (dev_types.h: TakeBlock) that says where a block lies
+//      in this pass's slots; rows of other passes' chunks are skipped, indices outside the rows are answered by the first pass;
+//   5. the rows that failed are counted in one more status word behind the blocks', which comes down with them: one synchronisation per pass.
+// Synchronisations: 2 + the passes, whatever nidx.
+namespace {
+struct TakeCall {
+  std::vector<TakeChunk> chunks;      // [nchunks + 1]
+  uint32_t row_bytes; int lanes_log2;
+  size_t nidx; const int64_t* index; uint8_t* dest; int32_t* status;
+  size_t failed = 0;
+};
+}  // namespace
+
+static unsigned take_grid(const EngineState& st, size_t nidx, int lanes_log2) {
+  const size_t per_group = (size_t)(TK_THREADS >> lanes_log2);
+  return persistent_grid(st, (nidx + per_group - 1) / per_group, TK_WAVES_PER_CU / (TK_THREADS / 64));
+}
+
+static int take_pass(EngineState& st, int pass, std::vector<RangeChunk>& uc, const std::vector<Header>& hdrs, const std::vector<Job>& jobs,
+                     TakeCall& tc, hipStream_t stream) {
+  PassRuns R;
+  lay_out_runs(st, pass, uc, hdrs, /*extra_status: the rows that failed*/ 1, R);
+  const size_t nchunks = uc.size(), nblocks = (size_t)tc.chunks[nchunks].block_first;
+  const size_t g_blocks = align_up(sizeof(TakeChunk) * (nchunks + 1), 256), gather_bytes = g_blocks + sizeof(TakeBlock) * (nblocks ? nblocks : 1);
+  const auto fill_gather = [&](uint8_t* G) {
+    memcpy(G, tc.chunks.data(), sizeof(TakeChunk) * (nchunks + 1));
+    TakeBlock* tb = (TakeBlock*)(G + g_blocks);
+    memset(tb, 0, sizeof(TakeBlock) * (nblocks ? nblocks : 1));      // base nullptr: not in this pass
+    for (size_t k = 0; k < nchunks; k++) {
+      if (uc[k].pass != pass) continue;
+      TakeBlock* cb = tb + tc.chunks[k].block_first;
+      if (uc[k].memcpyed) { cb[0].base = (const uint8_t*)jobs[k].src + kMaxOverhead; cb[0].status = -1; continue; }
+      const size_t bs = (size_t)hdrs[k].blocksize;
+      for (const BlockRun& r : uc[k].runs)
+        for (int32_t j = r.j0; j < r.j1; j++) { cb[j].base = R.A.out + r.off + (size_t)(j - r.j0) * bs; cb[j].status = r.entry0 + (j - r.j0); }
+    }
+  };
+  if (decode_runs(st, pass, uc, hdrs, jobs, R, gather_bytes, fill_gather, stream)) return -1;
+  const size_t n = R.entries.size();
+  {
+    ProfScope ps(st, stream, "k_take_gather");
+    hipLaunchKernelGGL(k_take_gather, dim3(take_grid(st, tc.nidx, tc.lanes_log2)), dim3(TK_THREADS), 0, stream,
+                       (const TakeChunk*)(R.A.extra + R.t_gather), (int)nchunks, (const TakeBlock*)(R.A.extra + R.t_gather + g_blocks),
+                       (const int32_t*)R.L.d_status, tc.index, tc.nidx, tc.row_bytes, tc.lanes_log2, tc.dest, tc.status,
+                       (uint32_t*)(R.L.d_status + (n - 1)), pass == 0 ? 1 : 0);
+    HIP_TRY(hipGetLastError());
+  }
+  if (read_back_decode(R.L, st.pin.base + R.p_status, st.pin.base + R.p_cost, stream) || finish_pass(st, R, "take", stream)) return -1;
+  tc.failed += (size_t)((const uint32_t*)(st.pin.base + R.p_status))[n - 1];
+  return 0;
+}
+
+int engine_take(int nchunks, const Job* chunks, size_t row_bytes, size_t nidx, const int64_t* index, void* dest, int* status,
+                int* chunk_rows_out, size_t* failed_out, hipStream_t stream) {
+  CtxGuard ctx; EngineState& st = *ctx.st;
+  if (ensure_device(st)) return -1;
+  const size_t n = (size_t)(nchunks > 0 ? nchunks : 0);
+  std::vector<Header> hdrs;
+  if (n && fetch_headers(st, (int)n, chunks, true, stream, hdrs)) return -1;
+  // ---- the census: which chunks are usable, and the rows and blocks in front of each ----
+  std::vector<Job> jobs(chunks, chunks + n);
+  std::vector<RangeChunk> uc(n);
+  TakeCall tc;
+  tc.chunks.resize(n + 1);
+  int64_t rows = 0, blocks = 0;
+  bool unusable = false;
+  for (size_t k = 0; k < n; k++) {
+    RangeChunk& u = uc[k];
+    const Header& h = hdrs[k];
+    const size_t srcsize = jobs[k].srcsize;      // packed: what lies between two offsets is all a chunk may claim
+    const bool fits = !srcsize || (h.cbytes >= 0 && (size_t)h.cbytes <= srcsize);
+    int32_t nblk = 0;
+    u.verdict = -1;
+    if (srcsize && srcsize < (size_t)kMaxOverhead) {}
+    else if (h.version == kVersionFormat && h.nbytes == 0) u.usable = fits;      // no rows: no range blosc_getitem could be asked for
+    else if (!classify_for_getitem(h, &u.verdict, &u.fmt)) {}
+    else if (fits && (size_t)h.nbytes % row_bytes == 0) {
+      u.usable = true; u.memcpyed = (h.flags & kFlagMemcpyed) != 0;
+      nblk = u.memcpyed ? 1 : h.nbytes / h.blocksize + ((h.nbytes % h.blocksize) ? 1 : 0);
+    } else u.verdict = -1;
+    const int64_t mine = u.usable ? (int64_t)((size_t)h.nbytes / row_bytes) : 0;
+    if (chunk_rows_out) chunk_rows_out[k] = u.usable ? (int)mine : u.verdict;
+    unusable |= !u.usable;
+    tc.chunks[k] = TakeChunk{rows, (int32_t)blocks, (u.usable && !u.memcpyed && h.nbytes) ? h.blocksize : 0};
+    rows += mine; blocks += nblk;
+  }
+  tc.chunks[n] = TakeChunk{rows, (int32_t)blocks, 0};
+  if (unusable || blocks > (int64_t)INT32_MAX) return -1;
+  if (failed_out) *failed_out = 0;
+  if (!nidx) return 0;
+  tc.row_bytes = (uint32_t)row_bytes; tc.nidx = nidx; tc.index = index; tc.dest = (uint8_t*)dest; tc.status = status;
+  // lanes per row: one up to 16 bytes; above, one per 16-byte piece (a power of two, at most the wave), and at least 16 where rows have
+  // head and tail bytes - where dest or row_bytes is no multiple of 16
+  tc.lanes_log2 = 0;
+  if (row_bytes > 16) {
+    while (((size_t)16 << tc.lanes_log2) < row_bytes && tc.lanes_log2 < 6) tc.lanes_log2++;
+    if ((((uintptr_t)dest | row_bytes) & 15) && tc.lanes_log2 < 4) tc.lanes_log2 = 4;
+  }
+  // ---- the blocks the rows touch ----
+  if (blocks) {
+    Carver cv;
+    const size_t o_chunks = cv.take(sizeof(TakeChunk) * (n + 1));
+    const size_t o_touched = cv.take((size_t)blocks);
+    if (st.dev.ensure(cv.off) || st.pin.ensure(cv.off)) return -1;
+    uint8_t *D = st.dev.base, *P = st.pin.base;
+    memcpy(P + o_chunks, tc.chunks.data(), sizeof(TakeChunk) * (n + 1));
+    HIP_TRY(hipMemcpyAsync(D + o_chunks, P + o_chunks, sizeof(TakeChunk) * (n + 1), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemsetAsync(D + o_touched, 0, (size_t)blocks, stream));
+    {
+      ProfScope ps(st, stream, "k_take_mark");
+      hipLaunchKernelGGL(k_take_mark, dim3(take_grid(st, nidx, 0)), dim3(TK_THREADS), 0, stream, (const TakeChunk*)(D + o_chunks), (int)n, index, nidx,
+                         tc.row_bytes, D + o_touched);
+      HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(P + o_touched, D + o_touched, (size_t)blocks, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    prof_collect(st);
+    // ---- runs: the maximal intervals of touched blocks of every chunk (a row's blocks are all marked, so they lie in one run) ----
+    for (size_t k = 0; k < n; k++) {
+      if (uc[k].memcpyed || !tc.chunks[k].blocksize) continue;
+      const uint8_t* t = P + o_touched + tc.chunks[k].block_first;
+      const int32_t nblk = tc.chunks[k + 1].block_first - tc.chunks[k].block_first;
+      for (int32_t j = 0; j < nblk; j++) {
+        if (!t[j]) continue;
+        int32_t e = j + 1;
+        while (e < nblk && t[e]) e++;
+        uc[k].runs.push_back(BlockRun{j, e, 0, 0});
+        j = e;
+      }
+    }
+  }
+  // ---- chunks dealt to passes, as getitem_ranges deals them (a chunk that decodes nothing never opens a pass: a pass is a gather over all indices) ----
+  const size_t bound = g_getitem_pass_bytes.load();
+  size_t in_pass = 0; int pass = 0;
+  for (size_t k = 0; k < n; k++) {
+    const size_t bytes = merge_runs(uc[k].runs, (size_t)(hdrs[k].blocksize > 0 ? hdrs[k].blocksize : 1));
+    if (in_pass && bytes && in_pass + bytes > bound) { pass++; in_pass = 0; }
+    uc[k].pass = pass; in_pass += bytes;
+  }
+  for (int p = 0; p <= pass; p++)
+    if (take_pass(st, p, uc, hdrs, jobs, tc, stream)) return -1;
+  if (failed_out) *failed_out = tc.failed;
+  return 0;
 }
 
 // blosc_getitem / blosc_gpu_getitem: one chunk, one range, one result, each pointer host or device memory.  What only this call has: a stream

@@ -5,6 +5,8 @@ A state dict, a table's columns, a cache line of activations: float32, bfloat16,
 c-blosc chunk whose typesize is the tensor's element size, with the codec, filter and clevel of the call or of its own; the chunks lie
 back to back in one device buffer with an offset table (include/blosc_gpu_packed.h), in the caller's order.  `unpack_tensors` is the
 reverse through blosc_gpu_decompress_packed, which reads chunks of any format, typesize and filter in one call anyway.
+`pack_rows` / `take_rows` keep ONE tensor as a table of rows in such a container - cut along dim 0 into chunks of whole rows - and read rows
+back by a device index tensor: index_select on the compressed table, one blosc_gpu_take_packed (include/blosc_gpu_take.h).
 
 Like blpk.py's device functions this module only drives the library: `lib` is the ctypes handle (load() of the package), memory comes
 from a `mem` with blpk.TorchMem's alloc().  There is no CPU implementation: without the library and a GPU the calls fail.
@@ -118,3 +120,51 @@ def unpack_tensors(lib, container, offsets, meta, mem=None, stream=None):
     at = b.offsets()
     # a slice of the byte buffer begins wherever the tensors in front of it end: each tensor gets storage of its own, aligned for its dtype
     return [keep[at[k]:at[k + 1]].clone().view(dt).reshape(shape) for k, (dt, shape) in enumerate(meta)]
+
+
+def pack_rows(lib, tensor, rows_per_chunk=None, **settings):
+    """A device tensor as a table of rows along dim 0, cut into chunks of whole rows and packed by pack_tensors(lib, slices, **settings):
+    (container, offsets, meta), meta[i] the dtype and shape of slice i.  rows_per_chunk: default the largest count that keeps a chunk
+    under MAX_CHUNK - so a table above 2 GiB, which is no tensor for pack_tensors, has a home.  take_rows reads rows back by index,
+    unpack_tensors the slices."""
+    if tensor.dim() < 1:
+        raise ValueError("a table has a dim 0 to cut along")
+    t = tensor.contiguous()
+    row_bytes = t.element_size() * int(t[0].numel()) if t.shape[0] else 0
+    if t.shape[0] and (row_bytes < 1 or row_bytes > MAX_CHUNK):
+        raise ValueError(f"rows of {row_bytes} bytes do not fit a chunk")
+    if rows_per_chunk is None:
+        rows_per_chunk = max(MAX_CHUNK // max(row_bytes, 1), 1)
+    if rows_per_chunk < 1:
+        raise ValueError("rows_per_chunk must be positive")
+    slices = [t[a:a + rows_per_chunk] for a in range(0, t.shape[0], rows_per_chunk)] or [t]
+    return pack_tensors(lib, slices, **settings)
+
+
+def take_rows(lib, container, offsets, meta, index, mem=None, stream=None):
+    """tensor.index_select(0, index) for the table pack_rows packed, by ONE blosc_gpu_take_packed: `index` is an int64 tensor on the device,
+    the result has the shape [len(index), *row shape] and the table's dtype.  Raises if any row failed (an index outside the table, a
+    block that does not decode), naming how many."""
+    import torch
+    pkg = _sibling("", "__init__.py")
+    mem = mem if mem is not None else _sibling("blpk", "blpk.py").TorchMem()
+    pkg.declare_take(lib)
+    dtype, row_shape = meta[0][0], tuple(meta[0][1][1:])
+    if any(dt != dtype or tuple(shape[1:]) != row_shape for dt, shape in meta):
+        raise ValueError("the container's chunks are not slices of one table")
+    row_bytes = int(torch.empty(0, dtype=dtype).element_size()) * int(torch.Size(row_shape).numel())
+    if not 1 <= row_bytes <= 65536:
+        raise ValueError(f"rows of {row_bytes} bytes: blosc_gpu_take_packed takes 1 ... 65536")
+    if index.dtype != torch.int64 or index.dim() != 1 or not index.is_cuda:
+        raise ValueError("index: a one-dimensional int64 tensor on the device")
+    idx = index.contiguous()
+    n = int(idx.numel())
+    dest, keep = mem.alloc(n * row_bytes)
+    take = pkg.RowTake(row_bytes, lib=lib)
+    if take.packed(container.data_ptr(), int(container.numel()), list(offsets), idx.data_ptr(), n, dest, None, stream) != 0:
+        raise RuntimeError(f"blosc_gpu_take_packed failed; rows per chunk (negative: the chunk's code): {take.chunk_rows()}")
+    if take.chunk_rows() != [int(shape[0]) for _, shape in meta]:
+        raise RuntimeError(f"the container does not hold this table: rows per chunk {take.chunk_rows()}")
+    if take.failed():
+        raise RuntimeError(f"{take.failed()} of {n} rows failed (an index outside 0 ... {sum(take.chunk_rows()) - 1}, or a block that does not decode)")
+    return keep[:n * row_bytes].view(dtype).reshape((n,) + row_shape)

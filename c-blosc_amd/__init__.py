@@ -1,7 +1,7 @@
 """c-blosc_amd — Python-side loader for libblosc_amd.so (ctypes; test / bench plumbing only).
 
 The product is the C-ABI shared library built from ``csrc/`` (see ``include/blosc.h`` and
-``include/blosc_gpu.h``, ``include/blosc_gpu_packed.h``, ``include/blosc_gpu_params.h``, ``include/blosc_gpu_select.h``, ``include/blosc_gpu_getitem.h``, ``include/blosc_gpu_take.h``, ``include/blosc_gpu_checksum.h``).  This module only locates it, declares argument types and offers small
+``include/blosc_gpu.h``, ``include/blosc_gpu_packed.h``, ``include/blosc_gpu_params.h``, ``include/blosc_gpu_select.h``, ``include/blosc_gpu_getitem.h``, ``include/blosc_gpu_take.h``, ``include/blosc_gpu_put.h``, ``include/blosc_gpu_checksum.h``).  This module only locates it, declares argument types and offers small
 numpy conveniences that mirror how the reference is driven from Python through ctypes
 (SURVEY.md §A.8).  There is no CPU implementation here: if the library is missing, ``load()``
 raises; if there is no GPU, the library's calls return errors.
@@ -47,6 +47,9 @@ SELECT_SYMBOLS = [      # include/blosc_gpu_select.h
 ]
 TAKE_SYMBOLS = [        # include/blosc_gpu_take.h
     "blosc_gpu_take_batch", "blosc_gpu_take_packed",
+]
+PUT_SYMBOLS = [         # include/blosc_gpu_put.h
+    "blosc_gpu_put_batch", "blosc_gpu_put_packed",
 ]
 CHECKSUM_ADLER32, CHECKSUM_CRC32 = 1, 2
 COMPCODES = {b"blosclz": 0, b"lz4": 1, b"lz4hc": 2, b"snappy": 3, b"zlib": 4, b"zstd": 5}      # include/blosc.h
@@ -154,6 +157,9 @@ def _signatures():
         # include/blosc_gpu_take.h
         "blosc_gpu_take_batch": ([i, pp, sz, sz, vp, vp, vp, ip, zp, vp], i),
         "blosc_gpu_take_packed": ([i, vp, sz, zp, sz, sz, vp, vp, vp, ip, zp, vp], i),
+        # include/blosc_gpu_put.h
+        "blosc_gpu_put_batch": ([i, pp, sz, sz, vp, vp, P(CParams), vp, sz, sz, zp, ip, ip, vp, ip, zp, vp], i),
+        "blosc_gpu_put_packed": ([i, vp, sz, zp, sz, sz, vp, vp, P(CParams), vp, sz, sz, zp, ip, ip, vp, ip, zp, vp], i),
         # include/blosc_gpu_checksum.h
         "blosc_gpu_checksum_batch": ([i, i, pp, zp, P(C.c_uint), vp], i),
         "blosc_gpu_checksum_packed": ([i, i, vp, sz, zp, zp, P(C.c_uint), vp], i),
@@ -184,7 +190,7 @@ def declare(L):
     return L
 
 
-declare_packed = declare_params = declare_select = declare_getitem = declare_take = declare_checksum = declare      # the names from when every header had a function of its own
+declare_packed = declare_params = declare_select = declare_getitem = declare_take = declare_put = declare_checksum = declare      # the names from when every header had a function of its own
 
 
 # ---- numpy conveniences (host buffers through the stock entry points) --------------------------
@@ -380,6 +386,58 @@ class RowTake:
         self._outputs(len(offsets) - 1)
         return self.lib.blosc_gpu_take_packed(self.nchunks, container, containersize, (C.c_size_t * (self.nchunks + 1))(*offsets), self.row_bytes, nidx,
                                               index, dest, status, self.rows, C.byref(self.nfailed), stream)
+
+    def chunk_rows(self):
+        return list(self.rows)[:self.nchunks]
+
+    def failed(self):
+        return int(self.nfailed.value)
+
+
+class RowPut:
+    """Helper for include/blosc_gpu_put.h: rows of row_bytes bytes written into many chunks by an index table on the device; the result is a
+    new packed container in `dest`.
+
+    batch(): chunk i at src_ptrs[i].  packed(): the chunks in a container with its offset table [n + 1].  Both take the device addresses of
+    the int64 indices, of the rows (nidx * row_bytes bytes), of dest and of the int32 status table (0 / None: no status wanted), and the
+    parameters of every chunk (see params_table); they return the call's answer.  offsets() is the new offset table [n + 1], results() the
+    per-chunk cbytes, rewritten() 1 / 0 / -1 per chunk, chunk_rows() every chunk's row count (or its negative census code), failed() the
+    indices with a negative status.
+    The library handle may be given (an emulator build in the CPU tests); default: the product."""
+
+    def __init__(self, row_bytes, lib=None):
+        self.row_bytes = row_bytes
+        self.lib = lib if lib is not None else load()
+        self._outputs(0)
+
+    def _outputs(self, nchunks):
+        self.nchunks = nchunks
+        self.off = (C.c_size_t * (nchunks + 1))()
+        self.res = (C.c_int * max(nchunks, 1))()
+        self.rew = (C.c_int * max(nchunks, 1))()
+        self.rows = (C.c_int * max(nchunks, 1))()
+        self.nfailed = C.c_size_t(0)
+
+    def batch(self, src_ptrs, index, nidx, rows, params, dest, destsize, align=1, status=None, stream=None):
+        self._outputs(len(src_ptrs))
+        return self.lib.blosc_gpu_put_batch(self.nchunks, (C.c_void_p * max(self.nchunks, 1))(*src_ptrs), self.row_bytes, nidx, index, rows,
+                                            params_table(params), dest, destsize, align, self.off, self.res, self.rew, status, self.rows,
+                                            C.byref(self.nfailed), stream)
+
+    def packed(self, container, containersize, offsets, index, nidx, rows, params, dest, destsize, align=1, status=None, stream=None):
+        self._outputs(len(offsets) - 1)
+        return self.lib.blosc_gpu_put_packed(self.nchunks, container, containersize, (C.c_size_t * (self.nchunks + 1))(*offsets), self.row_bytes,
+                                             nidx, index, rows, params_table(params), dest, destsize, align, self.off, self.res, self.rew, status,
+                                             self.rows, C.byref(self.nfailed), stream)
+
+    def offsets(self):
+        return list(self.off)
+
+    def results(self):
+        return list(self.res)[:self.nchunks]
+
+    def rewritten(self):
+        return list(self.rew)[:self.nchunks]
 
     def chunk_rows(self):
         return list(self.rows)[:self.nchunks]

@@ -1,5 +1,5 @@
 // blosc_api.hip — the exported C ABI (include/blosc.h, include/blosc_gpu.h, include/blosc_gpu_packed.h, include/blosc_gpu_params.h,
-// include/blosc_gpu_getitem.h, include/blosc_gpu_take.h, include/blosc_gpu_checksum.h).
+// include/blosc_gpu_getitem.h, include/blosc_gpu_take.h, include/blosc_gpu_put.h, include/blosc_gpu_checksum.h).
 //
 // Host-side mirror of the reference's public layer (blosc/blosc.c:1282-1703, :1951-2317):
 // process globals, the per-call environment overrides, name/code tables and cbuffer introspection
@@ -21,6 +21,7 @@
 #include "../../include/blosc_gpu_select.h"
 #include "../../include/blosc_gpu_getitem.h"
 #include "../../include/blosc_gpu_take.h"
+#include "../../include/blosc_gpu_put.h"
 #include "../../include/blosc_gpu_checksum.h"
 #include "blosc_format.h"
 #include "engine.h"
@@ -51,6 +52,8 @@ static bool codec_built(int code) { return code == BLOSC_BLOSCLZ || code == BLOS
 //   getitem_batch                           a negative count is unusable, nranges == 0 answers 0, then every array (`src` when there are chunks).
 //   take_*                                  take_opening(): a negative nchunks, row_bytes outside 1 ... 65536, no `index` or `dest` for nidx > 0 are
 //                                           unusable; then `src` / the container and its offsets where there are chunks; no chunks and no indices answer 0.
+//   put_*                                   put_opening(): take_opening() with `rows` for dest, then nidx above UINT32_MAX - 1, an unusable `align`, no `offsets_out`, a NULL
+//                                           dest that claims bytes, no `params` or `cbytes_out` where there are chunks; then as take_*, and dest against the container.
 //   checksum_*                              checksum_opening(): `kind` first, then nruns <= 0 answers 0; then the arrays (`length` may be NULL,
 //                                           the container where every run is empty).
 //   cbuffer_sizes_batch                     n < 0 is unusable, n == 0 answers 0, then `src`; every output may be NULL.
@@ -618,6 +621,49 @@ int blosc_gpu_take_packed(int nchunks, const void* container, size_t containersi
   if (nchunks > 0 && (!container || !offsets)) return -1;
   return take_call(nchunks, jobs_from_spans(nchunks, container, containersize, offsets, nullptr, BLOSC_MIN_HEADER_LENGTH), row_bytes, nidx, index, dest, status,
                    chunk_rows_out, failed_out, stream);
+}
+
+// ---- rows written by a device index table (include/blosc_gpu_put.h) --------------------------------
+// put_opening(): take_opening()'s checks with `rows` in dest's place, then nidx, `align`, the tables the call writes and reads, a dest of no
+// bytes that claims some; no chunks and no indices write an empty offset table and answer 0
+static int put_opening(int nchunks, size_t row_bytes, size_t nidx, const void* index, const void* rows, const blosc_gpu_cparams* params, void* dest,
+                       size_t destsize, size_t* align, size_t* offsets_out, int* cbytes_out) {
+  const int c = take_opening(nchunks, row_bytes, nidx, index, rows);
+  if (c != kGo) return c;
+  if (nidx > (size_t)UINT32_MAX - 1 || !packed_align(align) || !offsets_out || (!dest && destsize)) return -1;
+  if (nchunks > 0 && (!params || !cbytes_out)) return -1;
+  return kGo;
+}
+static int put_call(int nchunks, const Table<Job>& jobs, size_t row_bytes, size_t nidx, const int64_t* index, const void* rows, const blosc_gpu_cparams* params,
+                    void* dest, size_t destsize, size_t align, size_t* offsets_out, int* cbytes_out, int* rewritten_out, int* status, int* chunk_rows_out,
+                    size_t* failed_out, void* stream) {
+  if (!jobs) return -1;
+  if (nchunks == 0 && nidx == 0) { offsets_out[0] = 0; if (failed_out) *failed_out = 0; return 0; }
+  Table<CompressParams> p = chunk_params(nchunks, params);
+  if (!p) return -1;
+  const PackedBuffer pk{dest, destsize, align, offsets_out};
+  return engine_put(nchunks, jobs.get(), row_bytes, nidx, index, rows, p.get(), &pk, cbytes_out, rewritten_out, status, chunk_rows_out, failed_out, (hipStream_t)stream);
+}
+int blosc_gpu_put_batch(int nchunks, const void* const* src, size_t row_bytes, size_t nidx, const int64_t* index, const void* rows,
+                        const blosc_gpu_cparams* params, void* dest, size_t destsize, size_t align, size_t* offsets_out, int* cbytes_out,
+                        int* rewritten_out, int* status, int* chunk_rows_out, size_t* failed_out, void* stream) {
+  const int c = put_opening(nchunks, row_bytes, nidx, index, rows, params, dest, destsize, &align, offsets_out, cbytes_out);
+  if (c != kGo) return c;
+  if (nchunks > 0 && !src) return -1;
+  return put_call(nchunks, jobs_from_arrays(nchunks, src, nullptr, nullptr, nullptr), row_bytes, nidx, index, rows, params, dest, destsize, align, offsets_out,
+                  cbytes_out, rewritten_out, status, chunk_rows_out, failed_out, stream);
+}
+int blosc_gpu_put_packed(int nchunks, const void* container, size_t containersize, const size_t* offsets, size_t row_bytes, size_t nidx,
+                         const int64_t* index, const void* rows, const blosc_gpu_cparams* params, void* dest, size_t destsize, size_t align,
+                         size_t* offsets_out, int* cbytes_out, int* rewritten_out, int* status, int* chunk_rows_out, size_t* failed_out, void* stream) {
+  const int c = put_opening(nchunks, row_bytes, nidx, index, rows, params, dest, destsize, &align, offsets_out, cbytes_out);
+  if (c != kGo) return c;
+  if (nchunks > 0 && (!container || !offsets)) return -1;
+  // dest against the source container as a whole (the engine checks it against every chunk)
+  const uintptr_t s0 = (uintptr_t)container, s1 = s0 + containersize, d0 = (uintptr_t)dest, d1 = d0 + destsize;
+  if (nchunks > 0 && destsize && containersize && s0 < d1 && d0 < s1) return -1;
+  return put_call(nchunks, jobs_from_spans(nchunks, container, containersize, offsets, nullptr, BLOSC_MIN_HEADER_LENGTH), row_bytes, nidx, index, rows, params,
+                  dest, destsize, align, offsets_out, cbytes_out, rewritten_out, status, chunk_rows_out, failed_out, stream);
 }
 
 // ---- adler32 / crc32 of many runs (include/blosc_gpu_checksum.h) ---------------------------------------

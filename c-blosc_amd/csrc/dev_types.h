@@ -117,6 +117,23 @@ struct TakeBlock {
   int32_t pad_;
 };
 
+// The tables of k_put_claim / k_put_scatter / k_put_assemble (k_put.hip; include/blosc_gpu_put.h), next to the call's TakeChunk table.
+// PutChunk, one per chunk of a pass: the slot its plaintext was decoded into - nullptr: no index names the chunk -, the first of the owner
+// words of its rows, and the decoder's verdict (negative: the chunk is carried over, its indices answer -1).
+struct PutChunk {
+  uint8_t* slot;
+  uint64_t owner_first;
+  int32_t status;
+  int32_t pad_;
+};
+// PutCopy, one per chunk of a pass: nbytes from src to dst, then `pad` zero bytes (both 0: the chunk ends behind the caller's buffer).
+struct PutCopy {
+  const uint8_t* src;
+  uint8_t* dst;
+  uint32_t nbytes;
+  uint32_t pad;
+};
+
 // Negative per-chunk status codes written by kernels (host maps them to the reference's
 // return values, blosc/blosc.c:762-782): -1 bad csize chain / bounds, -2 codec produced wrong size.
 enum : int32_t { ST_OK = 0, ST_BADCHAIN = -1, ST_BADCODEC = -2 };

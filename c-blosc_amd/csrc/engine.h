@@ -78,6 +78,14 @@ void engine_getitem_pass_bytes(size_t bytes);   // test hook: decoded bytes per 
 // nullptr): the rows with a negative status.  The passes are engine_getitem_batch's, under the same bound.
 int engine_take(int nchunks, const Job* chunks, size_t row_bytes, size_t nidx, const int64_t* index, void* dest, int* status,
                 int* chunk_rows_out, size_t* failed_out, hipStream_t stream);
+// Rows written INTO the chunks (include/blosc_gpu_put.h): index_copy_ on the array of rows engine_take reads, `index` [nidx] and `rows`
+// (nidx * row_bytes) device memory, the last occurrence of a row winning.  The chunks some valid index names are decoded, updated and
+// compressed again with params[i] (one per chunk, all of them checked); the others are copied.  out: the new container as the packed compress
+// call lays it out (base, size, align; offsets [nchunks + 1] written).  cbytes_out / rewritten_out (may be nullptr) [nchunks], status (device,
+// may be nullptr) [nidx], chunk_rows_out and failed_out as in engine_take.  With a census failure the call answers -1 and writes nothing
+// but chunk_rows_out.
+int engine_put(int nchunks, const Job* chunks, size_t row_bytes, size_t nidx, const int64_t* index, const void* rows, const CompressParams* params,
+               const PackedBuffer* out, int* cbytes_out, int* rewritten_out, int* status, int* chunk_rows_out, size_t* failed_out, hipStream_t stream);
 
 // zlib's adler32 (kind 1) / crc32 (kind 2) of n runs in device memory (include/blosc_gpu_checksum.h): runs[i].src and runs[i].srcsize;
 // an empty run's pointer is never read.  digests[] is written only when the call answers 0.

@@ -26,6 +26,7 @@
 #include "k_zlib.hip"
 #include "k_checksum.hip"
 #include "k_take.hip"
+#include "k_put.hip"
 
 namespace bamd {
 
@@ -187,6 +188,7 @@ struct EngineState {
   DeviceArena dev;      // descriptors + scratch
   DeviceArena io;       // staging for host-pointer calls
   PinnedArena pin;
+  PinnedArena put_pin; // engine_put's own tables: they outlive the decode and encode calls inside it, which carve `pin` anew
   // profiling (switched on for all contexts at once: g_prof)
   std::map<std::string, ProfEntry> prof_acc;
   struct Pending { std::string name; hipEvent_t a, b; };
@@ -728,11 +730,11 @@ void engine_last_compress_tasks(uint32_t out[3]) { for (int i = 0; i < 3; i++) o
 struct SelectRun { int nchunks; const int* first; int* choice; int* answers; };
 
 // The compress call over a table of n chunks.  sel == nullptr: engine_compress_batch as it is without candidates - not a launch, not a byte more.
-static int compress_entries(const CompressParams* params, bool per_chunk, int n, const Job* jobs, int* results, bool device_ptrs,
-                            hipStream_t stream, const PackedBuffer* packed, const SelectRun* sel) {
+// compress_entries_in is the call in a context its caller holds (engine_put runs its decode and its encode in ONE context); compress_entries takes one.
+static int compress_entries_in(EngineState& st, const CompressParams* params, bool per_chunk, int n, const Job* jobs, int* results, bool device_ptrs,
+                               hipStream_t stream, const PackedBuffer* packed, const SelectRun* sel) {
   if (n <= 0) return 0;
   if ((packed || sel) && !device_ptrs) return -1;
-  CtxGuard ctx; EngineState& st = *ctx.st;
   if (ensure_device(st) || call_stream(st, !device_ptrs, &stream)) return -1;
   HostPhases ht(0);
   // ---- check and lay out the chunks ----
@@ -947,6 +949,14 @@ static int compress_entries(const CompressParams* params, bool per_chunk, int n,
     memcpy(sel->answers, P + p_results + sizeof(int32_t) * (size_t)sel->nchunks, sizeof(int32_t) * (size_t)n);
   }
   return io.collect(n, jobs, chunks, B.live, results, stream);
+}
+
+static int compress_entries(const CompressParams* params, bool per_chunk, int n, const Job* jobs, int* results, bool device_ptrs,
+                            hipStream_t stream, const PackedBuffer* packed, const SelectRun* sel) {
+  if (n <= 0) return 0;
+  if ((packed || sel) && !device_ptrs) return -1;
+  CtxGuard ctx;
+  return compress_entries_in(*ctx.st, params, per_chunk, n, jobs, results, device_ptrs, stream, packed, sel);
 }
 
 int engine_compress_batch(const CompressParams* params, bool per_chunk, int n, const Job* jobs, int* results, bool device_ptrs,
@@ -1278,10 +1288,10 @@ int engine_chunk_headers(int n, const void* const* src, Header* out, hipStream_t
   return 0;
 }
 
-int engine_decompress_batch(int n, const Job* jobs, int* results, bool device_ptrs, hipStream_t stream, const PackedBuffer* packed) {
+// The call in a context its caller holds (engine_decompress_batch takes one; engine_put brings its own).
+static int decompress_batch_in(EngineState& st, int n, const Job* jobs, int* results, bool device_ptrs, hipStream_t stream, const PackedBuffer* packed) {
   if (n <= 0) return 0;
   if (packed && !device_ptrs) return -1;
-  CtxGuard ctx; EngineState& st = *ctx.st;
   if (ensure_device(st) || call_stream(st, !device_ptrs, &stream)) return -1;
   HostPhases ht(1);
   std::vector<Header> hdrs;
@@ -1378,6 +1388,13 @@ int engine_decompress_batch(int n, const Job* jobs, int* results, bool device_pt
   const int32_t* stt = (const int32_t*)(P + p_status);
   for (int i = 0; i < n; i++) if (live[(size_t)i] && stt[i] < 0) results[i] = -1;       // blosc.c:1511-1514: every block-level error surfaces as -1
   return io.collect(n, jobs, chunks, live, results, stream);
+}
+
+int engine_decompress_batch(int n, const Job* jobs, int* results, bool device_ptrs, hipStream_t stream, const PackedBuffer* packed) {
+  if (n <= 0) return 0;
+  if (packed && !device_ptrs) return -1;
+  CtxGuard ctx;
+  return decompress_batch_in(*ctx.st, n, jobs, results, device_ptrs, stream, packed);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1707,6 +1724,42 @@ struct TakeCall {
 };
 }  // namespace
 
+// The census of the row calls (take, and put below), before anything is decoded: which chunks are usable - classify_for_getitem's checks, the
+// packed form's slot checks, nbytes a multiple of row_bytes -, and the rows and table entries in front of each (table: [n + 1]).
+// chunk_rows_out[k] (may be nullptr): the chunk's rows or its negative code.  whole_chunks (put): every chunk is ONE block of nbytes, so
+// k_take_mark's flags are per chunk - a MEMCPYED chunk too, which take gives blocksize 0 because it decodes nothing of it.
+// false: a chunk is unusable, the rows cannot be numbered.
+static bool rows_census(const std::vector<Job>& jobs, const std::vector<Header>& hdrs, size_t row_bytes, bool whole_chunks,
+                        std::vector<RangeChunk>& uc, std::vector<TakeChunk>& table, int* chunk_rows_out) {
+  const size_t n = jobs.size();
+  table.resize(n + 1);
+  int64_t rows = 0, blocks = 0;
+  bool unusable = false;
+  for (size_t k = 0; k < n; k++) {
+    RangeChunk& u = uc[k];
+    const Header& h = hdrs[k];
+    const size_t srcsize = jobs[k].srcsize;      // packed: what lies between two offsets is all a chunk may claim
+    const bool fits = !srcsize || (h.cbytes >= 0 && (size_t)h.cbytes <= srcsize);
+    int32_t nblk = 0;
+    u.verdict = -1;
+    if (srcsize && srcsize < (size_t)kMaxOverhead) {}
+    else if (h.version == kVersionFormat && h.nbytes == 0) u.usable = fits;      // no rows: no range blosc_getitem could be asked for
+    else if (!classify_for_getitem(h, &u.verdict, &u.fmt)) {}
+    else if (fits && (size_t)h.nbytes % row_bytes == 0) {
+      u.usable = true; u.memcpyed = (h.flags & kFlagMemcpyed) != 0;
+      nblk = u.memcpyed ? 1 : h.nbytes / h.blocksize + ((h.nbytes % h.blocksize) ? 1 : 0);
+    } else u.verdict = -1;
+    const int64_t mine = u.usable ? (int64_t)((size_t)h.nbytes / row_bytes) : 0;
+    if (chunk_rows_out) chunk_rows_out[k] = u.usable ? (int)mine : u.verdict;
+    unusable |= !u.usable;
+    if (whole_chunks) { table[k] = TakeChunk{rows, (int32_t)k, mine ? h.nbytes : 0}; nblk = 1; }
+    else table[k] = TakeChunk{rows, (int32_t)blocks, (u.usable && !u.memcpyed && h.nbytes) ? h.blocksize : 0};
+    rows += mine; blocks += nblk;
+  }
+  table[n] = TakeChunk{rows, (int32_t)blocks, 0};
+  return !unusable && blocks <= (int64_t)INT32_MAX;
+}
+
 static unsigned take_grid(const EngineState& st, size_t nidx, int lanes_log2) {
   const size_t per_group = (size_t)(TK_THREADS >> lanes_log2);
   return persistent_grid(st, (nidx + per_group - 1) / per_group, TK_WAVES_PER_CU / (TK_THREADS / 64));
@@ -1757,31 +1810,8 @@ int engine_take(int nchunks, const Job* chunks, size_t row_bytes, size_t nidx, c
   std::vector<Job> jobs(chunks, chunks + n);
   std::vector<RangeChunk> uc(n);
   TakeCall tc;
-  tc.chunks.resize(n + 1);
-  int64_t rows = 0, blocks = 0;
-  bool unusable = false;
-  for (size_t k = 0; k < n; k++) {
-    RangeChunk& u = uc[k];
-    const Header& h = hdrs[k];
-    const size_t srcsize = jobs[k].srcsize;      // packed: what lies between two offsets is all a chunk may claim
-    const bool fits = !srcsize || (h.cbytes >= 0 && (size_t)h.cbytes <= srcsize);
-    int32_t nblk = 0;
-    u.verdict = -1;
-    if (srcsize && srcsize < (size_t)kMaxOverhead) {}
-    else if (h.version == kVersionFormat && h.nbytes == 0) u.usable = fits;      // no rows: no range blosc_getitem could be asked for
-    else if (!classify_for_getitem(h, &u.verdict, &u.fmt)) {}
-    else if (fits && (size_t)h.nbytes % row_bytes == 0) {
-      u.usable = true; u.memcpyed = (h.flags & kFlagMemcpyed) != 0;
-      nblk = u.memcpyed ? 1 : h.nbytes / h.blocksize + ((h.nbytes % h.blocksize) ? 1 : 0);
-    } else u.verdict = -1;
-    const int64_t mine = u.usable ? (int64_t)((size_t)h.nbytes / row_bytes) : 0;
-    if (chunk_rows_out) chunk_rows_out[k] = u.usable ? (int)mine : u.verdict;
-    unusable |= !u.usable;
-    tc.chunks[k] = TakeChunk{rows, (int32_t)blocks, (u.usable && !u.memcpyed && h.nbytes) ? h.blocksize : 0};
-    rows += mine; blocks += nblk;
-  }
-  tc.chunks[n] = TakeChunk{rows, (int32_t)blocks, 0};
-  if (unusable || blocks > (int64_t)INT32_MAX) return -1;
+  if (!rows_census(jobs, hdrs, row_bytes, /*whole_chunks*/ false, uc, tc.chunks, chunk_rows_out)) return -1;
+  const int64_t blocks = tc.chunks[n].block_first;
   if (failed_out) *failed_out = 0;
   if (!nidx) return 0;
   tc.row_bytes = (uint32_t)row_bytes; tc.nidx = nidx; tc.index = index; tc.dest = (uint8_t*)dest; tc.status = status;
@@ -1836,6 +1866,206 @@ int engine_take(int nchunks, const Job* chunks, size_t row_bytes, size_t nidx, c
   for (int p = 0; p <= pass; p++)
     if (take_pass(st, p, uc, hdrs, jobs, tc, stream)) return -1;
   if (failed_out) *failed_out = tc.failed;
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// put (include/blosc_gpu_put.h): rows written into the chunks by an index table that lies on the device; the result is a new container
+// ---------------------------------------------------------------------------------------------
+// Take's front end around the two whole-chunk pipelines the engine has, in ONE context (decompress_batch_in, compress_entries_in):
+//   1. one header fetch, rows_census with every chunk as one block, every chunk's parameters, dest against the sources;
+//   2. k_take_mark, UNCHANGED, over that table: a flag per chunk some valid index names.  The flags come down, second synchronisation;
+//   3. the chunks are dealt to passes in chunk order, under engine_take's bound counted over the plaintext of the touched chunks - so a pass
+//      is a range [c0, c1) of chunks, and every chunk's place in dest is known once the sizes of its pass are;
+//   4. per pass with a touched chunk: the touched chunks decode into plaintext slots (the decompress call's two synchronisations, headers
+//      and verdicts - the verdicts are on the host, so the scatter needs no status words of the device and no synchronisation of its own),
+//      k_put_claim and k_put_scatter over all indices, the chunks that decoded are compressed into slots of nbytes + 16 (the compress call's
+//      synchronisation); per pass, touched chunk or not: the host sets the offsets, k_put_assemble writes the pass's piece of dest;
+//   5. the count of failed rows comes down, last synchronisation; the caller's host tables are written.
+// Synchronisations: 3 + 3 per pass that has a touched chunk, whatever nidx.
+// Memory.  The slots, the owner words and the put tables live in st.io, which a device-pointer call leaves alone - the decode and the encode
+// carve st.dev anew and may move it -, sized once for the largest pass: its plaintext (up to the bound, or one chunk), one owner word per
+// row of it, and nbytes + 16 per chunk for the encoder's output.  The tables' host images live in st.put_pin for the same reason.
+int engine_put(int nchunks, const Job* chunks, size_t row_bytes, size_t nidx, const int64_t* index, const void* rows, const CompressParams* params,
+               const PackedBuffer* out, int* cbytes_out, int* rewritten_out, int* status, int* chunk_rows_out, size_t* failed_out, hipStream_t stream) {
+  CtxGuard ctx; EngineState& st = *ctx.st;
+  if (ensure_device(st)) return -1;
+  const size_t n = (size_t)(nchunks > 0 ? nchunks : 0);
+  std::vector<Header> hdrs;
+  if (n && fetch_headers(st, (int)n, chunks, true, stream, hdrs)) return -1;
+  // ---- the census: take's, then every chunk's parameters (add_encode_chunk's checks in its order), then dest against every source ----
+  std::vector<Job> jobs(chunks, chunks + n);
+  std::vector<RangeChunk> uc(n);
+  std::vector<TakeChunk> table;
+  bool usable = rows_census(jobs, hdrs, row_bytes, /*whole_chunks*/ true, uc, table, chunk_rows_out);
+  for (size_t k = 0; k < n; k++) {
+    if (!uc[k].usable) continue;
+    const CompressParams& p = params[k];
+    int code = 0;
+    if (hdrs[k].nbytes > kMaxBufferSize || hdrs[k].cbytes < kMaxOverhead) code = -1;      // (no chunk the compress call would write; no chunk to copy)
+    else if (p.clevel < 0 || p.clevel > 9 || (p.doshuffle != 0 && p.doshuffle != 1 && p.doshuffle != 2) || p.typesize == 0) code = -10;
+    else if (p.codec != kBloscLZ && p.codec != kLZ4 && p.codec != kLZ4HC && p.codec != kZlib && p.codec != kZstd) code = -5;
+    if (!code) continue;
+    if (chunk_rows_out) chunk_rows_out[k] = code;
+    usable = false;
+  }
+  if (!usable) return -1;
+  const uintptr_t d0 = (uintptr_t)out->base, d1 = d0 + out->size;
+  for (size_t k = 0; k < n && out->base && out->size; k++) {
+    const uintptr_t s0 = (uintptr_t)jobs[k].src, s1 = s0 + (jobs[k].srcsize ? jobs[k].srcsize : (size_t)hdrs[k].cbytes);
+    if (s0 < d1 && d0 < s1) return -1;
+  }
+  // ---- the chunks some valid index names: k_take_mark over one block per chunk ----
+  std::vector<uint8_t> touched(n, 0);
+  if (nidx && n) {
+    Carver cv;
+    const size_t o_chunks = cv.take(sizeof(TakeChunk) * (n + 1));
+    const size_t o_touched = cv.take(n);
+    if (st.dev.ensure(cv.off) || st.pin.ensure(cv.off)) return -1;
+    uint8_t *D = st.dev.base, *P = st.pin.base;
+    memcpy(P + o_chunks, table.data(), sizeof(TakeChunk) * (n + 1));
+    HIP_TRY(hipMemcpyAsync(D + o_chunks, P + o_chunks, sizeof(TakeChunk) * (n + 1), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemsetAsync(D + o_touched, 0, n, stream));
+    {
+      ProfScope ps(st, stream, "k_take_mark");
+      hipLaunchKernelGGL(k_take_mark, dim3(take_grid(st, nidx, 0)), dim3(TK_THREADS), 0, stream, (const TakeChunk*)(D + o_chunks), (int)n, index, nidx,
+                         (uint32_t)row_bytes, D + o_touched);
+      HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(P + o_touched, D + o_touched, n, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    prof_collect(st);
+    memcpy(touched.data(), P + o_touched, n);
+  }
+  // ---- chunks dealt to passes in chunk order; the workspace of the largest pass ----
+  const size_t bound = g_getitem_pass_bytes.load();
+  std::vector<int> pass_of(n, 0);
+  std::vector<size_t> ws_of(1, 0);      // per pass: plaintext slots + owner words + encoder slots
+  bool any_touched = false;
+  {
+    size_t in_pass = 0; int pass = 0;
+    for (size_t k = 0; k < n; k++) {
+      const size_t nb = (size_t)hdrs[k].nbytes, bytes = touched[k] ? align_up(nb, 256) : 0;
+      if (in_pass && bytes && in_pass + bytes > bound) { pass++; in_pass = 0; ws_of.push_back(0); }
+      pass_of[k] = pass; in_pass += bytes;
+      if (touched[k]) { any_touched = true; ws_of[(size_t)pass] += bytes + align_up(sizeof(uint32_t) * (nb / row_bytes), 256) + align_up(nb + kMaxOverhead, 256); }
+    }
+  }
+  const size_t npass = ws_of.size();
+  Carver cv;
+  const size_t o_table = cv.take(sizeof(TakeChunk) * (n + 1));
+  const size_t o_put = cv.take(sizeof(PutChunk) * (n ? n : 1));
+  const size_t o_copy = cv.take(sizeof(PutCopy) * (n ? n : 1));
+  const size_t o_tiles = cv.take(sizeof(uint32_t) * (n + npass));      // pass p over chunks [c0, c1): entries [c0 + p, c1 + p]
+  const size_t o_failed = cv.take(sizeof(uint32_t));
+  const size_t table_bytes = cv.take(0);
+  const size_t o_ws = cv.take(*std::max_element(ws_of.begin(), ws_of.end()) + 256);
+  if (st.io.ensure(cv.off) || st.put_pin.ensure(table_bytes)) return -1;
+  uint8_t *D = st.io.base, *P = st.put_pin.base;
+  memcpy(P + o_table, table.data(), sizeof(TakeChunk) * (n + 1));
+  HIP_TRY(hipMemcpyAsync(D + o_table, P + o_table, sizeof(TakeChunk) * (n + 1), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemsetAsync(D + o_failed, 0, sizeof(uint32_t), stream));
+  // lanes per index: one up to 16 bytes; above, one per 16-byte piece (a power of two, at most the wave), and at least 16 where rows have
+  // head and tail bytes - where row_bytes is no multiple of 16 (the slots are aligned)
+  int lanes_log2 = 0;
+  if (row_bytes > 16) {
+    while (((size_t)16 << lanes_log2) < row_bytes && lanes_log2 < 6) lanes_log2++;
+    if ((row_bytes & 15) && lanes_log2 < 4) lanes_log2 = 4;
+  }
+  const TakeChunk* d_table = (const TakeChunk*)(D + o_table);
+  uint32_t* d_failed = (uint32_t*)(D + o_failed);
+  PutChunk* h_put = (PutChunk*)(P + o_put); PutCopy* h_copy = (PutCopy*)(P + o_copy); uint32_t* h_tiles = (uint32_t*)(P + o_tiles);
+  const auto scatter = [&](size_t c0, size_t c1, const uint32_t* owner, bool first) {
+    ProfScope ps(st, stream, "k_put_scatter");
+    hipLaunchKernelGGL(k_put_scatter, dim3(take_grid(st, nidx, lanes_log2)), dim3(TK_THREADS), 0, stream, d_table, (int)n, (const PutChunk*)(D + o_put) + c0,
+                       (int)c0, (int)c1, owner, index, nidx, (uint32_t)row_bytes, lanes_log2, (const uint8_t*)rows, status, d_failed, first ? 1 : 0);
+  };
+  std::vector<size_t> offsets(n + 1, 0);
+  std::vector<int> cbytes(n, 0), rewritten(n, 0);
+  std::vector<Job> djobs, cjobs; std::vector<int> dres, cres; std::vector<CompressParams> cpar; std::vector<size_t> live;
+  bool answered = false;      // the indices outside the rows have their -1
+  for (size_t p = 0, c0 = 0; p < npass; p++) {
+    size_t c1 = c0;
+    while (c1 < n && pass_of[c1] == (int)p) c1++;
+    // ---- the touched chunks of the pass: decode, claim, scatter, encode ----
+    size_t at = o_ws, nrows = 0;
+    djobs.clear(); live.clear();
+    for (size_t k = c0; k < c1; k++) {
+      h_put[k] = PutChunk{nullptr, 0, 0, 0};
+      if (!touched[k]) continue;
+      h_put[k].slot = D + at; h_put[k].owner_first = nrows;
+      djobs.push_back(Job{jobs[k].src, D + at, jobs[k].srcsize, (size_t)hdrs[k].nbytes});
+      live.push_back(k);
+      at += align_up((size_t)hdrs[k].nbytes, 256); nrows += (size_t)hdrs[k].nbytes / row_bytes;
+    }
+    if (!live.empty()) {
+      dres.assign(live.size(), -1);
+      if (decompress_batch_in(st, (int)live.size(), djobs.data(), dres.data(), true, stream, nullptr)) return -1;
+      uint32_t* owner = (uint32_t*)(D + at);
+      at += align_up(sizeof(uint32_t) * nrows, 256);
+      cjobs.clear(); cpar.clear();
+      for (size_t i = 0; i < live.size(); i++) {
+        const size_t k = live[i], nb = (size_t)hdrs[k].nbytes;
+        if (dres[i] != hdrs[k].nbytes) { h_put[k].status = -1; rewritten[k] = -1; continue; }      // blosc.c:1511-1514: carried over as it is
+        rewritten[k] = 1;
+        cjobs.push_back(Job{h_put[k].slot, D + at, nb, nb + kMaxOverhead});
+        cpar.push_back(params[k]);
+        at += align_up(nb + kMaxOverhead, 256);
+      }
+      HIP_TRY(hipMemcpyAsync(D + o_put + sizeof(PutChunk) * c0, h_put + c0, sizeof(PutChunk) * (c1 - c0), hipMemcpyHostToDevice, stream));
+      HIP_TRY(hipMemsetAsync(owner, 0xff, sizeof(uint32_t) * nrows, stream));
+      {
+        ProfScope ps(st, stream, "k_put_claim");
+        hipLaunchKernelGGL(k_put_claim, dim3(take_grid(st, nidx, 0)), dim3(TK_THREADS), 0, stream, d_table, (int)n, (const PutChunk*)(D + o_put) + c0, (int)c0, (int)c1,
+                           index, nidx, owner);
+      }
+      scatter(c0, c1, owner, !answered);
+      answered = true;
+      HIP_TRY(hipGetLastError());
+      cres.assign(cjobs.size(), 0);
+      if (compress_entries_in(st, cpar.data(), true, (int)cjobs.size(), cjobs.data(), cres.data(), true, stream, nullptr, nullptr)) return -1;
+      for (size_t i = 0, j = 0; i < live.size(); i++) {
+        const size_t k = live[i];
+        if (rewritten[k] != 1) continue;
+        if (cres[j] <= 0) return -1;      // (with destsize nbytes + 16 and checked parameters the call has no such answer)
+        cbytes[k] = cres[j]; h_copy[k].src = (const uint8_t*)cjobs[j].dst; j++;
+      }
+    } else if (nidx && !any_touched) {      // no index names a row: the one scatter launch answers them all
+      scatter(0, 0, nullptr, true);
+      HIP_TRY(hipGetLastError());
+      answered = true;
+    }
+    // ---- the pass's piece of dest ----
+    uint32_t* tiles = h_tiles + c0 + p;
+    tiles[0] = 0;
+    for (size_t k = c0; k < c1; k++) {
+      if (rewritten[k] != 1) { cbytes[k] = hdrs[k].cbytes; h_copy[k].src = (const uint8_t*)jobs[k].src; }
+      const size_t end = offsets[k] + (size_t)cbytes[k];
+      offsets[k + 1] = align_up(end, out->align);
+      h_copy[k].dst = (uint8_t*)out->base + offsets[k]; h_copy[k].nbytes = 0; h_copy[k].pad = 0;
+      if (end <= out->size) { h_copy[k].nbytes = (uint32_t)cbytes[k]; h_copy[k].pad = (uint32_t)(std::min(offsets[k + 1], out->size) - end); }
+      else cbytes[k] = 0;
+      tiles[k - c0 + 1] = tiles[k - c0] + (h_copy[k].nbytes + h_copy[k].pad + PA_TILE - 1) / PA_TILE;
+    }
+    const uint32_t ntiles = tiles[c1 - c0];
+    if (ntiles) {
+      HIP_TRY(hipMemcpyAsync(D + o_copy + sizeof(PutCopy) * c0, h_copy + c0, sizeof(PutCopy) * (c1 - c0), hipMemcpyHostToDevice, stream));
+      HIP_TRY(hipMemcpyAsync(D + o_tiles + sizeof(uint32_t) * (c0 + p), tiles, sizeof(uint32_t) * (c1 - c0 + 1), hipMemcpyHostToDevice, stream));
+      ProfScope ps(st, stream, "k_put_assemble");
+      hipLaunchKernelGGL(k_put_assemble, dim3(persistent_grid(st, ntiles, PA_WAVES_PER_CU)), dim3(PA_THREADS), 0, stream, (const PutCopy*)(D + o_copy) + c0,
+                         (const uint32_t*)(D + o_tiles) + c0 + p, (int)(c1 - c0));
+      HIP_TRY(hipGetLastError());
+    }
+    c0 = c1;
+  }
+  // ---- collect ----
+  uint32_t* h_failed = (uint32_t*)(P + o_failed);
+  HIP_TRY(hipMemcpyAsync(h_failed, d_failed, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  prof_collect(st);
+  for (size_t k = 0; k < n; k++) { out->offsets[k] = offsets[k]; if (cbytes_out) cbytes_out[k] = cbytes[k]; if (rewritten_out) rewritten_out[k] = rewritten[k]; }
+  out->offsets[n] = offsets[n];
+  if (failed_out) *failed_out = (size_t)*h_failed;
   return 0;
 }
 
@@ -2015,7 +2245,7 @@ void engine_release() {
     EngineState& st = g_ctx[i];
     std::lock_guard<std::mutex> lock(st.mu);
     if (!st.device_ok) continue;
-    st.dev.release(); st.io.release(); st.pin.release(); st.enc_tabs.drop(); st.dec_tabs.drop();
+    st.dev.release(); st.io.release(); st.pin.release(); st.put_pin.release(); st.enc_tabs.drop(); st.dec_tabs.drop();
     if (st.own) { (void)hipStreamDestroy(st.own); st.own = nullptr; }
   }
 }

@@ -7,6 +7,8 @@ back to back in one device buffer with an offset table (include/blosc_gpu_packed
 reverse through blosc_gpu_decompress_packed, which reads chunks of any format, typesize and filter in one call anyway.
 `pack_rows` / `take_rows` keep ONE tensor as a table of rows in such a container - cut along dim 0 into chunks of whole rows - and read rows
 back by a device index tensor: index_select on the compressed table, one blosc_gpu_take_packed (include/blosc_gpu_take.h).
+`put_rows` writes rows by a device index tensor - index_copy_ on the compressed table - into a new container, one blosc_gpu_put_packed
+(include/blosc_gpu_put.h): only the chunks a row lands in are decoded and compressed again.
 
 Like blpk.py's device functions this module only drives the library: `lib` is the ctypes handle (load() of the package), memory comes
 from a `mem` with blpk.TorchMem's alloc().  There is no CPU implementation: without the library and a GPU the calls fail.
@@ -168,3 +170,48 @@ def take_rows(lib, container, offsets, meta, index, mem=None, stream=None):
     if take.failed():
         raise RuntimeError(f"{take.failed()} of {n} rows failed (an index outside 0 ... {sum(take.chunk_rows()) - 1}, or a block that does not decode)")
     return keep[:n * row_bytes].view(dtype).reshape((n,) + row_shape)
+
+
+def put_rows(lib, container, offsets, meta, index, rows, mem=None, stream=None, align=256, **settings):
+    """table.index_copy_(0, index, rows) for the table pack_rows packed, by ONE blosc_gpu_put_packed (include/blosc_gpu_put.h): `index` is an
+    int64 tensor on the device, `rows` a device tensor of the shape [len(index), *row shape] and the table's dtype; of an index that occurs
+    several times the last occurrence wins.  Returns (new_container, new_offsets) - the container given is not written and `meta` stays what
+    it is.  Only the chunks some row lands in are decoded and compressed again, with the typesize of the table's dtype and `settings`
+    (cname / clevel / shuffle / blocksize / splitmode, pack_tensors' defaults); the others are copied.  Raises if any row failed (an index
+    outside the table, a chunk that does not decode), naming how many."""
+    import torch
+    pkg = _sibling("", "__init__.py")
+    mem = mem if mem is not None else _sibling("blpk", "blpk.py").TorchMem()
+    pkg.declare_put(lib)
+    pkg.declare_packed(lib)
+    dtype, row_shape = meta[0][0], tuple(meta[0][1][1:])
+    if any(dt != dtype or tuple(shape[1:]) != row_shape for dt, shape in meta):
+        raise ValueError("the container's chunks are not slices of one table")
+    element = int(torch.empty(0, dtype=dtype).element_size())
+    row_bytes = element * int(torch.Size(row_shape).numel())
+    if not 1 <= row_bytes <= 65536:
+        raise ValueError(f"rows of {row_bytes} bytes: blosc_gpu_put_packed takes 1 ... 65536")
+    if index.dtype != torch.int64 or index.dim() != 1 or not index.is_cuda:
+        raise ValueError("index: a one-dimensional int64 tensor on the device")
+    n = int(index.numel())
+    if rows.dtype != dtype or tuple(rows.shape) != (n,) + row_shape or not rows.is_cuda:
+        raise ValueError(f"rows: a device tensor of dtype {dtype} and shape {(n,) + row_shape}")
+    idx, new = index.contiguous(), rows.contiguous()
+    kw = dict(cname=b"lz4", clevel=5, shuffle=1)
+    kw.update(settings)
+    params = [pkg.cparams(element, **kw) for _ in meta]
+    sizes = [element * int(torch.Size(shape).numel()) for _, shape in meta]
+    cap = pkg.PackedBatch(len(meta), lib=lib).bound(sizes, align)
+    if cap == 0 and any(sizes):
+        raise ValueError("align must be a power of two up to 4096")
+    dest, keep = mem.alloc(cap)
+    put = pkg.RowPut(row_bytes, lib=lib)
+    if put.packed(container.data_ptr(), int(container.numel()), list(offsets), idx.data_ptr() if n else None, n, new.data_ptr() if n else None, params,
+                  dest, cap, align, None, stream) != 0:
+        raise RuntimeError(f"blosc_gpu_put_packed failed; rows per chunk (negative: the chunk's code): {put.chunk_rows()}")
+    if put.chunk_rows() != [int(shape[0]) for _, shape in meta]:
+        raise RuntimeError(f"the container does not hold this table: rows per chunk {put.chunk_rows()}")
+    if put.failed():
+        raise RuntimeError(f"{put.failed()} of {n} rows failed (an index outside 0 ... {sum(put.chunk_rows()) - 1}, or a chunk that does not decode)")
+    off = put.offsets()
+    return keep[:off[-1]], off

@@ -1,7 +1,7 @@
 """c-blosc_amd — Python-side loader for libblosc_amd.so (ctypes; test / bench plumbing only).
 
 The product is the C-ABI shared library built from ``csrc/`` (see ``include/blosc.h`` and
-``include/blosc_gpu.h``, ``include/blosc_gpu_packed.h``, ``include/blosc_gpu_params.h``, ``include/blosc_gpu_select.h``, ``include/blosc_gpu_getitem.h``, ``include/blosc_gpu_take.h``, ``include/blosc_gpu_put.h``, ``include/blosc_gpu_checksum.h``).  This module only locates it, declares argument types and offers small
+``include/blosc_gpu.h``, ``include/blosc_gpu_packed.h``, ``include/blosc_gpu_params.h``, ``include/blosc_gpu_select.h``, ``include/blosc_gpu_getitem.h``, ``include/blosc_gpu_take.h``, ``include/blosc_gpu_put.h``, ``include/blosc_gpu_where.h``, ``include/blosc_gpu_checksum.h``).  This module only locates it, declares argument types and offers small
 numpy conveniences that mirror how the reference is driven from Python through ctypes
 (SURVEY.md §A.8).  There is no CPU implementation here: if the library is missing, ``load()``
 raises; if there is no GPU, the library's calls return errors.
@@ -51,6 +51,11 @@ TAKE_SYMBOLS = [        # include/blosc_gpu_take.h
 PUT_SYMBOLS = [         # include/blosc_gpu_put.h
     "blosc_gpu_put_batch", "blosc_gpu_put_packed",
 ]
+WHERE_SYMBOLS = [       # include/blosc_gpu_where.h
+    "blosc_gpu_where_batch", "blosc_gpu_where_packed",
+]
+WHERE_EQ, WHERE_NE, WHERE_LT, WHERE_LE, WHERE_GT, WHERE_GE = range(6)
+FIELD_UINT, FIELD_INT, FIELD_FLOAT, FIELD_BFLOAT16 = range(4)
 CHECKSUM_ADLER32, CHECKSUM_CRC32 = 1, 2
 COMPCODES = {b"blosclz": 0, b"lz4": 1, b"lz4hc": 2, b"snappy": 3, b"zlib": 4, b"zstd": 5}      # include/blosc.h
 
@@ -70,6 +75,34 @@ def cparams(typesize, clevel=5, shuffle=1, cname=b"lz4", blocksize=0, splitmode=
     else:
         code = COMPCODES[cname.encode() if isinstance(cname, str) else cname]
     return CParams(clevel, shuffle, code, splitmode, typesize, blocksize)
+
+
+class Predicate(C.Structure):
+    """blosc_gpu_predicate (include/blosc_gpu_where.h): field `op` value on `bytes` bytes at `offset` of every row"""
+    _fields_ = [("offset", C.c_uint32), ("bytes", C.c_uint32), ("kind", C.c_int32), ("op", C.c_int32), ("value", C.c_uint8 * 8)]
+
+
+def predicate(kind, nbytes, op, value, offset=0):
+    """A Predicate.  value: a Python or numpy scalar, packed into the field's own little-endian representation - an integer of nbytes bytes
+    (FIELD_UINT / FIELD_INT; it must fit), binary16 / 32 / 64 (FIELD_FLOAT), the upper half of the binary32 nearest to it (FIELD_BFLOAT16;
+    a value that is no bfloat16 is rounded to nearest even, a NaN stays one) - or the `nbytes` bytes themselves as bytes."""
+    import struct
+    if isinstance(value, (bytes, bytearray)):
+        raw = bytes(value)
+    elif kind in (FIELD_UINT, FIELD_INT):
+        raw = int(value).to_bytes(nbytes, "little", signed=(kind == FIELD_INT))
+    elif kind == FIELD_FLOAT:
+        raw = struct.pack({2: "<e", 4: "<f", 8: "<d"}[nbytes], float(value))
+    elif kind == FIELD_BFLOAT16:
+        bits = struct.unpack("<I", struct.pack("<f", float(value)))[0]
+        if (bits & 0x7fffffff) > 0x7f800000: bits |= 0x00400000                  # a NaN keeps a mantissa bit in its upper half
+        else: bits = (bits + 0x7fff + ((bits >> 16) & 1)) & 0xffffffff
+        raw = struct.pack("<H", bits >> 16)
+    else:
+        raise ValueError(f"kind {kind}")
+    if len(raw) != nbytes or nbytes > 8:
+        raise ValueError(f"{len(raw)} bytes of value for a field of {nbytes}")
+    return Predicate(offset, nbytes, kind, op, (C.c_uint8 * 8)(*raw))
 
 
 def params_table(params):
@@ -160,6 +193,9 @@ def _signatures():
         # include/blosc_gpu_put.h
         "blosc_gpu_put_batch": ([i, pp, sz, sz, vp, vp, P(CParams), vp, sz, sz, zp, ip, ip, vp, ip, zp, vp], i),
         "blosc_gpu_put_packed": ([i, vp, sz, zp, sz, sz, vp, vp, P(CParams), vp, sz, sz, zp, ip, ip, vp, ip, zp, vp], i),
+        # include/blosc_gpu_where.h
+        "blosc_gpu_where_batch": ([i, pp, sz, P(Predicate), vp, sz, zp, ip, ip, zp, vp], i),
+        "blosc_gpu_where_packed": ([i, vp, sz, zp, sz, P(Predicate), vp, sz, zp, ip, ip, zp, vp], i),
         # include/blosc_gpu_checksum.h
         "blosc_gpu_checksum_batch": ([i, i, pp, zp, P(C.c_uint), vp], i),
         "blosc_gpu_checksum_packed": ([i, i, vp, sz, zp, zp, P(C.c_uint), vp], i),
@@ -190,7 +226,7 @@ def declare(L):
     return L
 
 
-declare_packed = declare_params = declare_select = declare_getitem = declare_take = declare_put = declare_checksum = declare      # the names from when every header had a function of its own
+declare_packed = declare_params = declare_select = declare_getitem = declare_take = declare_put = declare_where = declare_checksum = declare     # the names from when every header had a function of its own
 
 
 # ---- numpy conveniences (host buffers through the stock entry points) --------------------------
@@ -444,6 +480,52 @@ class RowPut:
 
     def failed(self):
         return int(self.nfailed.value)
+
+
+class RowWhere:
+    """Helper for include/blosc_gpu_where.h: the rows of row_bytes bytes of many chunks whose field satisfies a Predicate (see predicate()),
+    as an int64 index table on the device.
+
+    batch(): chunk i at src_ptrs[i].  packed(): the chunks in a container with its offset table [n + 1].  Both take the predicate, the device
+    address of the int64 table (0 / None with capacity 0: the count alone) and its capacity in entries, and return the call's answer.
+    total() is the number of matches whatever the capacity, chunk_matches() every chunk's matches (or the negative answer of the decoder),
+    chunk_rows() every chunk's row count (or its negative census code), unread() the rows of the chunks that did not decode.
+    The library handle may be given (an emulator build in the CPU tests); default: the product."""
+
+    def __init__(self, row_bytes, lib=None):
+        self.row_bytes = row_bytes
+        self.lib = lib if lib is not None else load()
+        self._outputs(0)
+
+    def _outputs(self, nchunks):
+        self.nchunks = nchunks
+        self.matches = (C.c_int * max(nchunks, 1))()
+        self.rows = (C.c_int * max(nchunks, 1))()
+        self.ntotal = C.c_size_t(0)
+        self.nunread = C.c_size_t(0)
+
+    def batch(self, src_ptrs, pred, index_out, capacity, stream=None):
+        self._outputs(len(src_ptrs))
+        return self.lib.blosc_gpu_where_batch(self.nchunks, (C.c_void_p * max(self.nchunks, 1))(*src_ptrs), self.row_bytes, C.byref(pred), index_out,
+                                              capacity, C.byref(self.ntotal), self.matches, self.rows, C.byref(self.nunread), stream)
+
+    def packed(self, container, containersize, offsets, pred, index_out, capacity, stream=None):
+        self._outputs(len(offsets) - 1)
+        return self.lib.blosc_gpu_where_packed(self.nchunks, container, containersize, (C.c_size_t * (self.nchunks + 1))(*offsets), self.row_bytes,
+                                               C.byref(pred), index_out, capacity, C.byref(self.ntotal), self.matches, self.rows,
+                                               C.byref(self.nunread), stream)
+
+    def total(self):
+        return int(self.ntotal.value)
+
+    def chunk_matches(self):
+        return list(self.matches)[:self.nchunks]
+
+    def chunk_rows(self):
+        return list(self.rows)[:self.nchunks]
+
+    def unread(self):
+        return int(self.nunread.value)
 
 
 def checksums(kind, ptrs, sizes, lib=None, stream=None):

@@ -22,8 +22,10 @@
 #include "../../include/blosc_gpu_getitem.h"
 #include "../../include/blosc_gpu_take.h"
 #include "../../include/blosc_gpu_put.h"
+#include "../../include/blosc_gpu_where.h"
 #include "../../include/blosc_gpu_checksum.h"
 #include "blosc_format.h"
+#include "dev_types.h"
 #include "engine.h"
 
 using namespace bamd;
@@ -54,6 +56,9 @@ static bool codec_built(int code) { return code == BLOSC_BLOSCLZ || code == BLOS
 //                                           unusable; then `src` / the container and its offsets where there are chunks; no chunks and no indices answer 0.
 //   put_*                                   put_opening(): take_opening() with `rows` for dest, then nidx above UINT32_MAX - 1, an unusable `align`, no `offsets_out`, a NULL
 //                                           dest that claims bytes, no `params` or `cbytes_out` where there are chunks; then as take_*, and dest against the container.
+//   where_*                                 where_opening(): a negative nchunks, row_bytes outside 1 ... 65536, no predicate or one outside the header's table, a field
+//                                           that ends behind the row, a capacity without `index_out` are unusable; then as take_*, and index_out against the
+//                                           container; no chunks answer 0 with a total of 0.
 //   checksum_*                              checksum_opening(): `kind` first, then nruns <= 0 answers 0; then the arrays (`length` may be NULL,
 //                                           the container where every run is empty).
 //   cbuffer_sizes_batch                     n < 0 is unusable, n == 0 answers 0, then `src`; every output may be NULL.
@@ -664,6 +669,57 @@ int blosc_gpu_put_packed(int nchunks, const void* container, size_t containersiz
   if (nchunks > 0 && destsize && containersize && s0 < d1 && d0 < s1) return -1;
   return put_call(nchunks, jobs_from_spans(nchunks, container, containersize, offsets, nullptr, BLOSC_MIN_HEADER_LENGTH), row_bytes, nidx, index, rows, params,
                   dest, destsize, align, offsets_out, cbytes_out, rewritten_out, status, chunk_rows_out, failed_out, stream);
+}
+
+// ---- rows by a field predicate (include/blosc_gpu_where.h) -----------------------------------------
+// where_opening(): the whole-call checks, and the predicate as the kernels evaluate it (dev_types.h: WherePred)
+static int where_opening(int nchunks, size_t row_bytes, const blosc_gpu_predicate* pred, const int64_t* index_out, size_t capacity, WherePred* q) {
+  if (nchunks < 0 || row_bytes < 1 || row_bytes > 65536 || !pred) return -1;
+  if (pred->op < BLOSC_GPU_WHERE_EQ || pred->op > BLOSC_GPU_WHERE_GE) return -1;
+  const uint32_t b = pred->bytes;
+  uint64_t inf = 0;
+  switch (pred->kind) {
+    case BLOSC_GPU_FIELD_UINT: case BLOSC_GPU_FIELD_INT: if (b != 1 && b != 2 && b != 4 && b != 8) return -1; break;
+    case BLOSC_GPU_FIELD_FLOAT: if (b != 2 && b != 4 && b != 8) return -1; inf = b == 2 ? 0x7c00ull : (b == 4 ? 0x7f800000ull : 0x7ff0000000000000ull); break;
+    case BLOSC_GPU_FIELD_BFLOAT16: if (b != 2) return -1; inf = 0x7f80ull; break;
+    default: return -1;
+  }
+  if ((size_t)pred->offset + b > row_bytes) return -1;
+  if (capacity && (!index_out || capacity > SIZE_MAX / sizeof(int64_t))) return -1;
+  uint64_t v = 0;
+  for (uint32_t i = 0; i < b; i++) v |= (uint64_t)pred->value[i] << (8 * i);
+  const int32_t kind = pred->kind == BLOSC_GPU_FIELD_UINT ? 0 : (pred->kind == BLOSC_GPU_FIELD_INT ? 1 : 2);
+  bool nan = false;
+  const int64_t key = where_key(v, kind, b, inf, &nan);
+  *q = WherePred{pred->offset, b, kind, pred->op, key, inf, nan ? 1 : 0, 0};
+  return kGo;
+}
+static int where_call(int nchunks, const Table<Job>& jobs, size_t row_bytes, const WherePred& q, int64_t* index_out, size_t capacity, size_t* total_out,
+                      int* chunk_matches_out, int* chunk_rows_out, size_t* unread_out, void* stream) {
+  if (!jobs) return -1;
+  if (nchunks == 0) { if (total_out) *total_out = 0; if (unread_out) *unread_out = 0; return 0; }      // no chunk to count, no row to read
+  return engine_where(nchunks, jobs.get(), row_bytes, q, index_out, capacity, total_out, chunk_matches_out, chunk_rows_out, unread_out, (hipStream_t)stream);
+}
+int blosc_gpu_where_batch(int nchunks, const void* const* src, size_t row_bytes, const blosc_gpu_predicate* pred, int64_t* index_out, size_t capacity,
+                          size_t* total_out, int* chunk_matches_out, int* chunk_rows_out, size_t* unread_out, void* stream) {
+  WherePred q;
+  const int c = where_opening(nchunks, row_bytes, pred, index_out, capacity, &q);
+  if (c != kGo) return c;
+  if (nchunks > 0 && !src) return -1;
+  return where_call(nchunks, jobs_from_arrays(nchunks, src, nullptr, nullptr, nullptr), row_bytes, q, index_out, capacity, total_out, chunk_matches_out,
+                    chunk_rows_out, unread_out, stream);
+}
+int blosc_gpu_where_packed(int nchunks, const void* container, size_t containersize, const size_t* offsets, size_t row_bytes, const blosc_gpu_predicate* pred,
+                           int64_t* index_out, size_t capacity, size_t* total_out, int* chunk_matches_out, int* chunk_rows_out, size_t* unread_out, void* stream) {
+  WherePred q;
+  const int c = where_opening(nchunks, row_bytes, pred, index_out, capacity, &q);
+  if (c != kGo) return c;
+  if (nchunks > 0 && (!container || !offsets)) return -1;
+  // index_out against the source container as a whole (the engine checks it against every chunk)
+  const uintptr_t s0 = (uintptr_t)container, s1 = s0 + containersize, d0 = (uintptr_t)index_out, d1 = d0 + capacity * sizeof(int64_t);
+  if (nchunks > 0 && capacity && containersize && s0 < d1 && d0 < s1) return -1;
+  return where_call(nchunks, jobs_from_spans(nchunks, container, containersize, offsets, nullptr, BLOSC_MIN_HEADER_LENGTH), row_bytes, q, index_out, capacity,
+                    total_out, chunk_matches_out, chunk_rows_out, unread_out, stream);
 }
 
 // ---- adler32 / crc32 of many runs (include/blosc_gpu_checksum.h) ---------------------------------------

@@ -134,6 +134,43 @@ struct PutCopy {
   uint32_t pad;
 };
 
+// The tables of k_where_mark / k_where_scan / k_where_write (k_where.hip; include/blosc_gpu_where.h).
+// WhereChunk, one per chunk of a pass: the slot its plaintext was decoded into, the call's number of its first row, its rows and the
+// decoder's verdict (negative: its tiles count nothing).  Next to it lies the prefix of the chunks' tiles, as k_put_assemble has it.
+struct WhereChunk {
+  const uint8_t* slot;
+  int64_t row_first;
+  uint32_t rows;
+  int32_t status;
+};
+// WherePred: the caller's predicate as the kernels evaluate it.  Every kind compares ONE signed 64-bit key (where_key below), so a row costs
+// one load and integer instructions whatever its type, and the floating-point mode of the device plays no part:
+//   UINT   the value with bit 63 flipped;   INT   the value sign-extended;
+//   FLOAT, BFLOAT16   the magnitude bits, negated under the sign bit - the order of IEEE 754 with -0 = +0 = key 0, the same for binary16,
+//          bfloat16, binary32 and binary64 (widening is exact and monotone: the order of the narrow patterns IS the order of the widened values);
+//          a pattern above `inf` is a NaN, and a NaN on either side makes every comparison false but NE.
+struct WherePred {
+  uint32_t offset, bytes;
+  int32_t kind, op;      // kind: 0 UINT, 1 INT, 2 the floating-point formats;  op: 0 ... 5 = EQ NE LT LE GT GE
+  int64_t key;           // the constant's key
+  uint64_t inf;          // floating point: the pattern of +infinity
+  int32_t nan;           // the constant is a NaN
+  int32_t pad_;
+};
+// v: the field's `bytes` bytes, little endian, zero-extended.  *nan (floating point): the pattern is a NaN
+#if defined(__HIPCC__) || defined(__HIP__)
+__host__ __device__
+#endif
+inline int64_t where_key(uint64_t v, int32_t kind, uint32_t bytes, uint64_t inf, bool* nan) {
+  const uint32_t up = 64u - 8u * bytes;
+  *nan = false;
+  if (kind == 0) return (int64_t)(v ^ 0x8000000000000000ull);
+  if (kind == 1) return (int64_t)(v << up) >> up;
+  const uint64_t sign = 1ull << (8u * bytes - 1u), mag = v & (sign - 1ull);
+  *nan = mag > inf;
+  return (v & sign) ? -(int64_t)mag : (int64_t)mag;
+}
+
 // Negative per-chunk status codes written by kernels (host maps them to the reference's
 // return values, blosc/blosc.c:762-782): -1 bad csize chain / bounds, -2 codec produced wrong size.
 enum : int32_t { ST_OK = 0, ST_BADCHAIN = -1, ST_BADCODEC = -2 };

@@ -86,6 +86,14 @@ int engine_take(int nchunks, const Job* chunks, size_t row_bytes, size_t nidx, c
 // but chunk_rows_out.
 int engine_put(int nchunks, const Job* chunks, size_t row_bytes, size_t nidx, const int64_t* index, const void* rows, const CompressParams* params,
                const PackedBuffer* out, int* cbytes_out, int* rewritten_out, int* status, int* chunk_rows_out, size_t* failed_out, hipStream_t stream);
+// The rows whose field satisfies a predicate (include/blosc_gpu_where.h), over the array of rows engine_take reads: their numbers, ascending,
+// go to index_out (device, `capacity` entries; nullptr with capacity 0: the count alone).  pred: the caller's predicate as the kernels
+// evaluate it (dev_types.h: WherePred).  total_out: the matches, whatever the capacity; chunk_matches_out [nchunks]: per chunk, or the negative
+// answer of the decoder for a chunk that does not decode, whose rows are counted in unread_out; chunk_rows_out as in engine_take (all host, may
+// be nullptr).  With a census failure the call answers -1 and writes nothing but chunk_rows_out; with index_out inside a source, nothing at all.
+struct WherePred;
+int engine_where(int nchunks, const Job* chunks, size_t row_bytes, const WherePred& pred, int64_t* index_out, size_t capacity, size_t* total_out,
+                 int* chunk_matches_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream);
 
 // zlib's adler32 (kind 1) / crc32 (kind 2) of n runs in device memory (include/blosc_gpu_checksum.h): runs[i].src and runs[i].srcsize;
 // an empty run's pointer is never read.  digests[] is written only when the call answers 0.

@@ -27,6 +27,7 @@
 #include "k_checksum.hip"
 #include "k_take.hip"
 #include "k_put.hip"
+#include "k_where.hip"
 
 namespace bamd {
 
@@ -2066,6 +2067,147 @@ int engine_put(int nchunks, const Job* chunks, size_t row_bytes, size_t nidx, co
   for (size_t k = 0; k < n; k++) { out->offsets[k] = offsets[k]; if (cbytes_out) cbytes_out[k] = cbytes[k]; if (rewritten_out) rewritten_out[k] = rewritten[k]; }
   out->offsets[n] = offsets[n];
   if (failed_out) *failed_out = (size_t)*h_failed;
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// where (include/blosc_gpu_where.h): the rows whose field satisfies a predicate, as the index table take and put read
+// ---------------------------------------------------------------------------------------------
+// Put's front end and its whole-chunk decode, in ONE context, around the three kernels of k_where.hip:
+//   1. one header fetch, rows_census with every chunk as one block, index_out against every source;
+//   2. the chunks that hold rows are dealt to passes in chunk order under engine_take's bound (at most 1 GiB, so that the counts of a pass stay
+//      in 32 bits; a single chunk beyond the bound is a pass of its own), and the workspace is sized once for the largest pass;
+//   3. per pass: the chunks decode into plaintext slots (the decompress call's two synchronisations, headers and verdicts - the verdicts are on
+//      the host, so a chunk that did not decode enters the table with a negative status and its tiles count nothing), then k_where_mark,
+//      and - where the caller gave a table - k_where_scan and k_where_write.  The running total stays on the device: no pass waits for a count;
+//   4. the chunks' counters come down, last synchronisation; the caller's host tables are written.
+// Synchronisations: 2 + 2 per pass that holds a row, whatever the rows and the matches.
+// Memory.  As in engine_put the workspace lives in st.io and the tables' host images in st.put_pin, which the decode calls inside leave alone:
+// the plaintext of the largest pass, and per tile of WH_TILE rows of it WH_WORDS mask words, a count and a base (140 bytes per 1024 rows).
+int engine_where(int nchunks, const Job* chunks, size_t row_bytes, const WherePred& pred, int64_t* index_out, size_t capacity, size_t* total_out,
+                 int* chunk_matches_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream) {
+  CtxGuard ctx; EngineState& st = *ctx.st;
+  if (ensure_device(st)) return -1;
+  const size_t n = (size_t)(nchunks > 0 ? nchunks : 0);
+  std::vector<Header> hdrs;
+  if (n && fetch_headers(st, (int)n, chunks, true, stream, hdrs)) return -1;
+  // ---- the census: take's; then index_out against every source - a call that fails the second writes nothing at all ----
+  std::vector<Job> jobs(chunks, chunks + n);
+  std::vector<RangeChunk> uc(n);
+  std::vector<TakeChunk> table;
+  std::vector<int> rows_of(n ? n : 1, 0);
+  const bool usable = rows_census(jobs, hdrs, row_bytes, /*whole_chunks*/ true, uc, table, rows_of.data());
+  if (!usable) {
+    if (chunk_rows_out) std::copy(rows_of.begin(), rows_of.begin() + (ptrdiff_t)n, chunk_rows_out);
+    return -1;
+  }
+  const uintptr_t d0 = (uintptr_t)index_out, d1 = d0 + capacity * sizeof(int64_t);
+  for (size_t k = 0; k < n && capacity; k++) {
+    const uintptr_t s0 = (uintptr_t)jobs[k].src, s1 = s0 + (jobs[k].srcsize ? jobs[k].srcsize : (size_t)hdrs[k].cbytes);
+    if (s0 < d1 && d0 < s1) return -1;
+  }
+  if (chunk_rows_out) std::copy(rows_of.begin(), rows_of.begin() + (ptrdiff_t)n, chunk_rows_out);
+  // ---- chunks dealt to passes in chunk order; the workspace of the largest pass ----
+  const size_t bound = std::min(g_getitem_pass_bytes.load(), (size_t)1 << 30);
+  const size_t tile_bytes = sizeof(uint64_t) * WH_WORDS + sizeof(uint32_t) + sizeof(uint64_t);
+  std::vector<int> pass_of(n, 0);
+  std::vector<uint32_t> tiles_of(n, 0);
+  std::vector<size_t> ws_of(1, 0);      // per pass: plaintext slots + the tiles' words
+  {
+    size_t in_pass = 0; int pass = 0;
+    for (size_t k = 0; k < n; k++) {
+      const size_t bytes = rows_of[k] ? align_up((size_t)hdrs[k].nbytes, 256) : 0;
+      if (in_pass && bytes && in_pass + bytes > bound) { pass++; in_pass = 0; ws_of.push_back(0); }
+      pass_of[k] = pass; in_pass += bytes;
+      tiles_of[k] = (uint32_t)(((size_t)rows_of[k] + WH_TILE - 1) / WH_TILE);
+      ws_of[(size_t)pass] += bytes + tile_bytes * tiles_of[k];
+    }
+  }
+  const size_t npass = ws_of.size();
+  Carver cv;
+  const size_t o_chunks = cv.take(sizeof(WhereChunk) * (n ? n : 1));
+  const size_t o_tiles = cv.take(sizeof(uint32_t) * (n + npass));      // pass p over chunks [c0, c1): entries [c0 + p, c1 + p]
+  const size_t o_back = cv.take(sizeof(uint64_t) + sizeof(uint32_t) * (n ? n : 1));      // the running total, then the chunks' counters
+  const size_t table_bytes = cv.take(0);
+  const size_t o_ws = cv.take(*std::max_element(ws_of.begin(), ws_of.end()) + 4 * 256);
+  if (st.io.ensure(cv.off) || st.put_pin.ensure(table_bytes)) return -1;
+  uint8_t *D = st.io.base, *P = st.put_pin.base;
+  WhereChunk* h_chunks = (WhereChunk*)(P + o_chunks);
+  uint32_t* h_tiles = (uint32_t*)(P + o_tiles);
+  uint64_t* d_running = (uint64_t*)(D + o_back);
+  uint32_t* d_count = (uint32_t*)(D + o_back + sizeof(uint64_t));
+  HIP_TRY(hipMemsetAsync(D + o_back, 0, sizeof(uint64_t) + sizeof(uint32_t) * (n ? n : 1), stream));
+  std::vector<int> code(n, 0);      // negative: what the decoder answered for the chunk
+  size_t unread = 0;
+  std::vector<Job> djobs; std::vector<int> dres; std::vector<size_t> live;
+  for (size_t p = 0, c0 = 0; p < npass; p++) {
+    size_t c1 = c0;
+    while (c1 < n && pass_of[c1] == (int)p) c1++;
+    // ---- the pass's chunks decode into their slots ----
+    size_t at = o_ws;
+    uint32_t* tiles = h_tiles + c0 + p;
+    tiles[0] = 0;
+    djobs.clear(); live.clear();
+    for (size_t k = c0; k < c1; k++) {
+      h_chunks[k] = WhereChunk{nullptr, table[k].row_first, (uint32_t)rows_of[k], -1};
+      tiles[k - c0 + 1] = tiles[k - c0] + tiles_of[k];
+      if (!rows_of[k]) continue;
+      h_chunks[k].slot = D + at;
+      djobs.push_back(Job{jobs[k].src, D + at, jobs[k].srcsize, (size_t)hdrs[k].nbytes});
+      live.push_back(k);
+      at += align_up((size_t)hdrs[k].nbytes, 256);
+    }
+    const uint32_t ntiles = tiles[c1 - c0];
+    if (!live.empty()) {
+      dres.assign(live.size(), -1);
+      if (decompress_batch_in(st, (int)live.size(), djobs.data(), dres.data(), true, stream, nullptr)) return -1;
+      for (size_t i = 0; i < live.size(); i++) {
+        const size_t k = live[i];
+        if (dres[i] == hdrs[k].nbytes) { h_chunks[k].status = 0; continue; }
+        code[k] = dres[i] < 0 ? dres[i] : -1;      // blosc.c:1511-1514: the chunk holds no row anybody can read
+        unread += (size_t)rows_of[k];
+      }
+      Carver wv; wv.off = at;
+      uint64_t* d_masks = (uint64_t*)(D + wv.take(sizeof(uint64_t) * WH_WORDS * ntiles));
+      uint32_t* d_tile_count = (uint32_t*)(D + wv.take(sizeof(uint32_t) * ntiles));
+      uint64_t* d_tile_base = (uint64_t*)(D + wv.take(sizeof(uint64_t) * ntiles));
+      const WhereChunk* d_chunks = (const WhereChunk*)(D + o_chunks) + c0;
+      const uint32_t* d_tiles = (const uint32_t*)(D + o_tiles) + c0 + p;
+      HIP_TRY(hipMemcpyAsync(D + o_chunks + sizeof(WhereChunk) * c0, h_chunks + c0, sizeof(WhereChunk) * (c1 - c0), hipMemcpyHostToDevice, stream));
+      HIP_TRY(hipMemcpyAsync(D + o_tiles + sizeof(uint32_t) * (c0 + p), tiles, sizeof(uint32_t) * (c1 - c0 + 1), hipMemcpyHostToDevice, stream));
+      const dim3 grid(persistent_grid(st, ntiles, WH_WAVES_PER_CU / WH_WAVES));
+      {
+        ProfScope ps(st, stream, "k_where_mark");
+        hipLaunchKernelGGL(k_where_mark, grid, dim3(WH_THREADS), 0, stream, d_chunks, d_tiles, (int)(c1 - c0), (uint32_t)row_bytes, pred, d_masks, d_tile_count,
+                           d_count + c0);
+        HIP_TRY(hipGetLastError());
+      }
+      if (capacity) {
+        {
+          ProfScope ps(st, stream, "k_where_scan");
+          hipLaunchKernelGGL(k_where_scan, dim3(1), dim3(WH_SCAN_THREADS), 0, stream, (const uint32_t*)d_tile_count, ntiles, d_tile_base, d_running);
+          HIP_TRY(hipGetLastError());
+        }
+        ProfScope ps(st, stream, "k_where_write");
+        hipLaunchKernelGGL(k_where_write, grid, dim3(WH_THREADS), 0, stream, d_chunks, d_tiles, (int)(c1 - c0), (const uint64_t*)d_masks,
+                           (const uint32_t*)d_tile_count, (const uint64_t*)d_tile_base, index_out, (uint64_t)capacity);
+        HIP_TRY(hipGetLastError());
+      }
+    }
+    c0 = c1;
+  }
+  // ---- collect ----
+  const uint32_t* h_count = (const uint32_t*)(P + o_back + sizeof(uint64_t));
+  if (n) HIP_TRY(hipMemcpyAsync(P + o_back + sizeof(uint64_t), d_count, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  prof_collect(st);
+  size_t total = 0;
+  for (size_t k = 0; k < n; k++) {
+    if (code[k] >= 0) total += (size_t)h_count[k];
+    if (chunk_matches_out) chunk_matches_out[k] = code[k] < 0 ? code[k] : (int)h_count[k];
+  }
+  if (total_out) *total_out = total;
+  if (unread_out) *unread_out = unread;
   return 0;
 }
 

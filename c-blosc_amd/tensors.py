@@ -9,6 +9,8 @@ reverse through blosc_gpu_decompress_packed, which reads chunks of any format, t
 back by a device index tensor: index_select on the compressed table, one blosc_gpu_take_packed (include/blosc_gpu_take.h).
 `put_rows` writes rows by a device index tensor - index_copy_ on the compressed table - into a new container, one blosc_gpu_put_packed
 (include/blosc_gpu_put.h): only the chunks a row lands in are decoded and compressed again.
+`where_rows` makes the index tensor both read - the rows whose column satisfies a comparison with a scalar, torch.nonzero on the compressed
+table - by blosc_gpu_where_packed (include/blosc_gpu_where.h), holding one pass of plaintext at a time.
 
 Like blpk.py's device functions this module only drives the library: `lib` is the ctypes handle (load() of the package), memory comes
 from a `mem` with blpk.TorchMem's alloc().  There is no CPU implementation: without the library and a GPU the calls fail.
@@ -170,6 +172,67 @@ def take_rows(lib, container, offsets, meta, index, mem=None, stream=None):
     if take.failed():
         raise RuntimeError(f"{take.failed()} of {n} rows failed (an index outside 0 ... {sum(take.chunk_rows()) - 1}, or a block that does not decode)")
     return keep[:n * row_bytes].view(dtype).reshape((n,) + row_shape)
+
+
+_WHERE_OPS = {"eq": 0, "ne": 1, "lt": 2, "le": 3, "gt": 4, "ge": 5, "==": 0, "!=": 1, "<": 2, "<=": 3, ">": 4, ">=": 5}
+
+
+def where_rows(lib, container, offsets, meta, op, value, column=0, max_matches=None, mem=None, stream=None):
+    """torch.nonzero(op(table.reshape(nrows, -1)[:, column], value)).flatten() for the table pack_rows packed, without its plaintext:
+    blosc_gpu_where_packed (include/blosc_gpu_where.h) decodes pass by pass and keeps the row numbers alone.  op: "eq" / "ne" / "lt" / "le" /
+    "gt" / "ge" (or "==", "!=", ...; the functions of `operator` and the torch comparisons are taken by their name), value: a scalar of the
+    table's dtype, column: the flat element number inside a row.  The predicate's type is the table's dtype: torch.uint8 and bool are
+    unsigned bytes, int8 ... int64, float16 / float32 / float64, bfloat16; any other raises ValueError.
+    Returns (index, total): an int64 device tensor - what take_rows and put_rows read - and the number of matches.  With max_matches the
+    table has min(total, max_matches) entries, the first ones, and one call is made.  With max_matches=None TWO calls are made: one with
+    capacity 0 that counts, one that fills a table of exactly `total` (none if nothing matches).
+    Raises, like take_rows, if the container does not hold this table or if any row was unread (a chunk that does not decode)."""
+    import torch
+    pkg = _sibling("", "__init__.py")
+    mem = mem if mem is not None else _sibling("blpk", "blpk.py").TorchMem()
+    pkg.declare_where(lib)
+    dtype, row_shape = meta[0][0], tuple(meta[0][1][1:])
+    if any(dt != dtype or tuple(shape[1:]) != row_shape for dt, shape in meta):
+        raise ValueError("the container's chunks are not slices of one table")
+    kinds = {torch.uint8: pkg.FIELD_UINT, torch.bool: pkg.FIELD_UINT, torch.int8: pkg.FIELD_INT, torch.int16: pkg.FIELD_INT, torch.int32: pkg.FIELD_INT,
+             torch.int64: pkg.FIELD_INT, torch.float16: pkg.FIELD_FLOAT, torch.float32: pkg.FIELD_FLOAT, torch.float64: pkg.FIELD_FLOAT,
+             torch.bfloat16: pkg.FIELD_BFLOAT16}
+    if dtype not in kinds:
+        raise ValueError(f"no predicate for a table of {dtype}")
+    element = int(torch.empty(0, dtype=dtype).element_size())
+    per_row = int(torch.Size(row_shape).numel())
+    row_bytes = element * per_row
+    if not 1 <= row_bytes <= 65536:
+        raise ValueError(f"rows of {row_bytes} bytes: blosc_gpu_where_packed takes 1 ... 65536")
+    if not 0 <= column < per_row:
+        raise ValueError(f"column {column} of rows of {per_row} elements")
+    name = getattr(op, "__name__", op)
+    if name not in _WHERE_OPS:
+        raise ValueError(f"op {op!r}: one of {sorted(_WHERE_OPS)}")
+    # the constant in the table's own representation: torch rounds it as it would round the scalar of the comparison
+    raw = bytes(torch.tensor([value], dtype=dtype).view(torch.uint8).tolist())
+    pred = pkg.predicate(kinds[dtype], element, _WHERE_OPS[name], raw, offset=column * element)
+    where = pkg.RowWhere(row_bytes, lib=lib)
+
+    def call(ptr, capacity):
+        if where.packed(container.data_ptr(), int(container.numel()), list(offsets), pred, ptr, capacity, stream) != 0:
+            raise RuntimeError(f"blosc_gpu_where_packed failed; rows per chunk (negative: the chunk's code): {where.chunk_rows()}")
+        if where.chunk_rows() != [int(shape[0]) for _, shape in meta]:
+            raise RuntimeError(f"the container does not hold this table: rows per chunk {where.chunk_rows()}")
+        if where.unread():
+            raise RuntimeError(f"{where.unread()} of {sum(where.chunk_rows())} rows were not read (chunks that do not decode: {where.chunk_matches()})")
+        return where.total()
+
+    if max_matches is not None and max_matches < 0:
+        raise ValueError("max_matches must not be negative")
+    total = call(None, 0) if max_matches is None else None      # the counting call
+    capacity = total if max_matches is None else int(max_matches)
+    dest, keep = mem.alloc(capacity * 8)
+    if capacity:
+        total = call(dest, capacity)
+    elif total is None:
+        total = call(None, 0)
+    return keep[:min(total, capacity) * 8].view(torch.int64), total
 
 
 def put_rows(lib, container, offsets, meta, index, rows, mem=None, stream=None, align=256, **settings):

@@ -1,7 +1,7 @@
 """c-blosc_amd — Python-side loader for libblosc_amd.so (ctypes; test / bench plumbing only).
 
 The product is the C-ABI shared library built from ``csrc/`` (see ``include/blosc.h`` and
-``include/blosc_gpu.h``, ``include/blosc_gpu_packed.h``, ``include/blosc_gpu_params.h``, ``include/blosc_gpu_select.h``, ``include/blosc_gpu_getitem.h``, ``include/blosc_gpu_take.h``, ``include/blosc_gpu_put.h``, ``include/blosc_gpu_where.h``, ``include/blosc_gpu_checksum.h``).  This module only locates it, declares argument types and offers small
+``include/blosc_gpu.h``, ``include/blosc_gpu_packed.h``, ``include/blosc_gpu_params.h``, ``include/blosc_gpu_select.h``, ``include/blosc_gpu_getitem.h``, ``include/blosc_gpu_take.h``, ``include/blosc_gpu_put.h``, ``include/blosc_gpu_where.h``, ``include/blosc_gpu_aggregate.h``, ``include/blosc_gpu_checksum.h``).  This module only locates it, declares argument types and offers small
 numpy conveniences that mirror how the reference is driven from Python through ctypes
 (SURVEY.md §A.8).  There is no CPU implementation here: if the library is missing, ``load()``
 raises; if there is no GPU, the library's calls return errors.
@@ -54,6 +54,9 @@ PUT_SYMBOLS = [         # include/blosc_gpu_put.h
 WHERE_SYMBOLS = [       # include/blosc_gpu_where.h
     "blosc_gpu_where_batch", "blosc_gpu_where_packed",
 ]
+AGGREGATE_SYMBOLS = [   # include/blosc_gpu_aggregate.h
+    "blosc_gpu_aggregate_batch", "blosc_gpu_aggregate_packed",
+]
 WHERE_EQ, WHERE_NE, WHERE_LT, WHERE_LE, WHERE_GT, WHERE_GE = range(6)
 FIELD_UINT, FIELD_INT, FIELD_FLOAT, FIELD_BFLOAT16 = range(4)
 CHECKSUM_ADLER32, CHECKSUM_CRC32 = 1, 2
@@ -103,6 +106,27 @@ def predicate(kind, nbytes, op, value, offset=0):
     if len(raw) != nbytes or nbytes > 8:
         raise ValueError(f"{len(raw)} bytes of value for a field of {nbytes}")
     return Predicate(offset, nbytes, kind, op, (C.c_uint8 * 8)(*raw))
+
+
+class Field(C.Structure):
+    """blosc_gpu_field (include/blosc_gpu_aggregate.h): the `bytes` bytes at `offset` of every row, read as `kind`"""
+    _fields_ = [("offset", C.c_uint32), ("bytes", C.c_uint32), ("kind", C.c_int32), ("pad_", C.c_int32)]
+
+
+def field(kind, nbytes, offset=0):
+    """A Field: FIELD_UINT / FIELD_INT of 1, 2, 4, 8 bytes, FIELD_FLOAT of 2, 4, 8, FIELD_BFLOAT16 of 2"""
+    return Field(offset, nbytes, kind, 0)
+
+
+class AggregateSum(C.Union):
+    _fields_ = [("i", C.c_int64), ("u", C.c_uint64), ("f", C.c_double)]
+
+
+class Aggregate(C.Structure):
+    """blosc_gpu_aggregate (include/blosc_gpu_aggregate.h): rows read, rows counted, NaNs among them, the lowest rows holding the extremes (-1:
+    none) with their bytes, and the sum - sum.u / sum.i / sum.f by the field's kind"""
+    _fields_ = [("rows", C.c_uint64), ("count", C.c_uint64), ("nans", C.c_uint64), ("min_row", C.c_int64), ("max_row", C.c_int64),
+                ("min", C.c_uint8 * 8), ("max", C.c_uint8 * 8), ("sum", AggregateSum)]
 
 
 def params_table(params):
@@ -196,6 +220,9 @@ def _signatures():
         # include/blosc_gpu_where.h
         "blosc_gpu_where_batch": ([i, pp, sz, P(Predicate), vp, sz, zp, ip, ip, zp, vp], i),
         "blosc_gpu_where_packed": ([i, vp, sz, zp, sz, P(Predicate), vp, sz, zp, ip, ip, zp, vp], i),
+        # include/blosc_gpu_aggregate.h
+        "blosc_gpu_aggregate_batch": ([i, pp, sz, P(Field), P(Predicate), P(Aggregate), P(Aggregate), ip, ip, zp, vp], i),
+        "blosc_gpu_aggregate_packed": ([i, vp, sz, zp, sz, P(Field), P(Predicate), P(Aggregate), P(Aggregate), ip, ip, zp, vp], i),
         # include/blosc_gpu_checksum.h
         "blosc_gpu_checksum_batch": ([i, i, pp, zp, P(C.c_uint), vp], i),
         "blosc_gpu_checksum_packed": ([i, i, vp, sz, zp, zp, P(C.c_uint), vp], i),
@@ -226,7 +253,7 @@ def declare(L):
     return L
 
 
-declare_packed = declare_params = declare_select = declare_getitem = declare_take = declare_put = declare_where = declare_checksum = declare     # the names from when every header had a function of its own
+declare_packed = declare_params = declare_select = declare_getitem = declare_take = declare_put = declare_where = declare_aggregate = declare_checksum = declare    # the names from when every header had a function of its own
 
 
 # ---- numpy conveniences (host buffers through the stock entry points) --------------------------
@@ -520,6 +547,56 @@ class RowWhere:
 
     def chunk_matches(self):
         return list(self.matches)[:self.nchunks]
+
+    def chunk_rows(self):
+        return list(self.rows)[:self.nchunks]
+
+    def unread(self):
+        return int(self.nunread.value)
+
+
+class RowAggregate:
+    """Helper for include/blosc_gpu_aggregate.h: count, sum, min and max of a Field (see field()) of the rows of row_bytes bytes of many chunks,
+    of the rows a Predicate lets through (filter None: of every row).
+
+    batch(): chunk i at src_ptrs[i].  packed(): the chunks in a container with its offset table [n + 1].  Both return the call's answer.
+    total() is the call's Aggregate, chunks() every chunk's, chunk_status() 0 or the negative answer of the decoder per chunk, chunk_rows()
+    every chunk's row count (or its negative census code), unread() the rows of the chunks that did not decode.
+    The library handle may be given (an emulator build in the CPU tests); default: the product."""
+
+    def __init__(self, row_bytes, lib=None):
+        self.row_bytes = row_bytes
+        self.lib = lib if lib is not None else load()
+        self._outputs(0)
+
+    def _outputs(self, nchunks):
+        self.nchunks = nchunks
+        self.result = Aggregate()
+        self.per_chunk = (Aggregate * max(nchunks, 1))()
+        self.status = (C.c_int * max(nchunks, 1))()
+        self.rows = (C.c_int * max(nchunks, 1))()
+        self.nunread = C.c_size_t(0)
+
+    def batch(self, src_ptrs, fld, filter=None, stream=None):
+        self._outputs(len(src_ptrs))
+        return self.lib.blosc_gpu_aggregate_batch(self.nchunks, (C.c_void_p * max(self.nchunks, 1))(*src_ptrs), self.row_bytes, C.byref(fld),
+                                                  C.byref(filter) if filter is not None else None, C.byref(self.result), self.per_chunk, self.status,
+                                                  self.rows, C.byref(self.nunread), stream)
+
+    def packed(self, container, containersize, offsets, fld, filter=None, stream=None):
+        self._outputs(len(offsets) - 1)
+        return self.lib.blosc_gpu_aggregate_packed(self.nchunks, container, containersize, (C.c_size_t * (self.nchunks + 1))(*offsets), self.row_bytes,
+                                                   C.byref(fld), C.byref(filter) if filter is not None else None, C.byref(self.result), self.per_chunk,
+                                                   self.status, self.rows, C.byref(self.nunread), stream)
+
+    def total(self):
+        return self.result
+
+    def chunks(self):
+        return list(self.per_chunk)[:self.nchunks]
+
+    def chunk_status(self):
+        return list(self.status)[:self.nchunks]
 
     def chunk_rows(self):
         return list(self.rows)[:self.nchunks]

@@ -1,5 +1,5 @@
 // blosc_api.hip — the exported C ABI (include/blosc.h, include/blosc_gpu.h, include/blosc_gpu_packed.h, include/blosc_gpu_params.h,
-// include/blosc_gpu_getitem.h, include/blosc_gpu_take.h, include/blosc_gpu_put.h, include/blosc_gpu_checksum.h).
+// include/blosc_gpu_getitem.h, include/blosc_gpu_take.h, include/blosc_gpu_put.h, include/blosc_gpu_where.h, include/blosc_gpu_aggregate.h, include/blosc_gpu_checksum.h).
 //
 // Host-side mirror of the reference's public layer (blosc/blosc.c:1282-1703, :1951-2317):
 // process globals, the per-call environment overrides, name/code tables and cbuffer introspection
@@ -23,6 +23,7 @@
 #include "../../include/blosc_gpu_take.h"
 #include "../../include/blosc_gpu_put.h"
 #include "../../include/blosc_gpu_where.h"
+#include "../../include/blosc_gpu_aggregate.h"
 #include "../../include/blosc_gpu_checksum.h"
 #include "blosc_format.h"
 #include "dev_types.h"
@@ -59,6 +60,9 @@ static bool codec_built(int code) { return code == BLOSC_BLOSCLZ || code == BLOS
 //   where_*                                 where_opening(): a negative nchunks, row_bytes outside 1 ... 65536, no predicate or one outside the header's table, a field
 //                                           that ends behind the row, a capacity without `index_out` are unusable; then as take_*, and index_out against the
 //                                           container; no chunks answer 0 with a total of 0.
+//   aggregate_*                             aggregate_opening(): a negative nchunks, row_bytes outside 1 ... 65536, no field, a field with pad_ set, outside the
+//                                           header's table (field_of_table(), which where_opening() reads too) or ending behind the row; then a filter that
+//                                           where_opening() refuses; then as take_*; no chunks answer 0 with the total of nothing.
 //   checksum_*                              checksum_opening(): `kind` first, then nruns <= 0 answers 0; then the arrays (`length` may be NULL,
 //                                           the container where every run is empty).
 //   cbuffer_sizes_batch                     n < 0 is unusable, n == 0 answers 0, then `src`; every output may be NULL.
@@ -673,25 +677,35 @@ int blosc_gpu_put_packed(int nchunks, const void* container, size_t containersiz
 
 // ---- rows by a field predicate (include/blosc_gpu_where.h) -----------------------------------------
 // where_opening(): the whole-call checks, and the predicate as the kernels evaluate it (dev_types.h: WherePred)
+// The header's kind / bytes table, the one copy of it: false for a pair outside it, else the field as the kernels read it (dev_types.h:
+// AggField - the kind of where_key, the pattern of +infinity and the mantissa bits of a floating-point format).  The field must end inside the row.
+static bool field_of_table(int32_t kind, uint32_t b, uint32_t offset, size_t row_bytes, AggField* f) {
+  uint64_t inf = 0;
+  uint32_t mant = 0;
+  switch (kind) {
+    case BLOSC_GPU_FIELD_UINT: case BLOSC_GPU_FIELD_INT: if (b != 1 && b != 2 && b != 4 && b != 8) return false; break;
+    case BLOSC_GPU_FIELD_FLOAT:
+      if (b != 2 && b != 4 && b != 8) return false;
+      inf = b == 2 ? 0x7c00ull : (b == 4 ? 0x7f800000ull : 0x7ff0000000000000ull); mant = b == 2 ? 10 : (b == 4 ? 23 : 52);
+      break;
+    case BLOSC_GPU_FIELD_BFLOAT16: if (b != 2) return false; inf = 0x7f80ull; mant = 7; break;
+    default: return false;
+  }
+  if ((size_t)offset + b > row_bytes) return false;
+  *f = AggField{offset, b, kind == BLOSC_GPU_FIELD_UINT ? 0 : (kind == BLOSC_GPU_FIELD_INT ? 1 : 2), mant, inf};
+  return true;
+}
 static int where_opening(int nchunks, size_t row_bytes, const blosc_gpu_predicate* pred, const int64_t* index_out, size_t capacity, WherePred* q) {
   if (nchunks < 0 || row_bytes < 1 || row_bytes > 65536 || !pred) return -1;
   if (pred->op < BLOSC_GPU_WHERE_EQ || pred->op > BLOSC_GPU_WHERE_GE) return -1;
-  const uint32_t b = pred->bytes;
-  uint64_t inf = 0;
-  switch (pred->kind) {
-    case BLOSC_GPU_FIELD_UINT: case BLOSC_GPU_FIELD_INT: if (b != 1 && b != 2 && b != 4 && b != 8) return -1; break;
-    case BLOSC_GPU_FIELD_FLOAT: if (b != 2 && b != 4 && b != 8) return -1; inf = b == 2 ? 0x7c00ull : (b == 4 ? 0x7f800000ull : 0x7ff0000000000000ull); break;
-    case BLOSC_GPU_FIELD_BFLOAT16: if (b != 2) return -1; inf = 0x7f80ull; break;
-    default: return -1;
-  }
-  if ((size_t)pred->offset + b > row_bytes) return -1;
+  AggField f;
+  if (!field_of_table(pred->kind, pred->bytes, pred->offset, row_bytes, &f)) return -1;
   if (capacity && (!index_out || capacity > SIZE_MAX / sizeof(int64_t))) return -1;
   uint64_t v = 0;
-  for (uint32_t i = 0; i < b; i++) v |= (uint64_t)pred->value[i] << (8 * i);
-  const int32_t kind = pred->kind == BLOSC_GPU_FIELD_UINT ? 0 : (pred->kind == BLOSC_GPU_FIELD_INT ? 1 : 2);
+  for (uint32_t i = 0; i < f.bytes; i++) v |= (uint64_t)pred->value[i] << (8 * i);
   bool nan = false;
-  const int64_t key = where_key(v, kind, b, inf, &nan);
-  *q = WherePred{pred->offset, b, kind, pred->op, key, inf, nan ? 1 : 0, 0};
+  const int64_t key = where_key(v, f.kind, f.bytes, f.inf, &nan);
+  *q = WherePred{pred->offset, f.bytes, f.kind, pred->op, key, f.inf, nan ? 1 : 0, 0};
   return kGo;
 }
 static int where_call(int nchunks, const Table<Job>& jobs, size_t row_bytes, const WherePred& q, int64_t* index_out, size_t capacity, size_t* total_out,
@@ -720,6 +734,47 @@ int blosc_gpu_where_packed(int nchunks, const void* container, size_t containers
   if (nchunks > 0 && capacity && containersize && s0 < d1 && d0 < s1) return -1;
   return where_call(nchunks, jobs_from_spans(nchunks, container, containersize, offsets, nullptr, BLOSC_MIN_HEADER_LENGTH), row_bytes, q, index_out, capacity,
                     total_out, chunk_matches_out, chunk_rows_out, unread_out, stream);
+}
+
+// ---- count, sum, min, max of a row field (include/blosc_gpu_aggregate.h) ----------------------------
+static_assert(sizeof(blosc_gpu_aggregate) == sizeof(AggResult) && sizeof(blosc_gpu_aggregate) == 64 && sizeof(blosc_gpu_field) == 16,
+              "blosc_gpu_aggregate is the engine's AggResult");
+// aggregate_opening(): the whole-call checks, and field and filter as the kernels evaluate them (dev_types.h: AggField, WherePred)
+static int aggregate_opening(int nchunks, size_t row_bytes, const blosc_gpu_field* field, const blosc_gpu_predicate* filter, AggField* f, WherePred* q) {
+  if (nchunks < 0 || row_bytes < 1 || row_bytes > 65536 || !field || field->pad_ != 0) return -1;
+  if (!field_of_table(field->kind, field->bytes, field->offset, row_bytes, f)) return -1;
+  return filter ? where_opening(nchunks, row_bytes, filter, nullptr, 0, q) : kGo;
+}
+static int aggregate_call(int nchunks, const Table<Job>& jobs, size_t row_bytes, const AggField& f, const WherePred* q, blosc_gpu_aggregate* total_out,
+                          blosc_gpu_aggregate* chunk_out, int* chunk_status_out, int* chunk_rows_out, size_t* unread_out, void* stream) {
+  if (!jobs) return -1;
+  if (nchunks == 0) {      // no chunk to read: the total of nothing
+    if (total_out) { memset(total_out, 0, sizeof *total_out); total_out->min_row = total_out->max_row = -1; }
+    if (unread_out) *unread_out = 0;
+    return 0;
+  }
+  return engine_aggregate(nchunks, jobs.get(), row_bytes, f, q, (AggResult*)total_out, (AggResult*)chunk_out, chunk_status_out, chunk_rows_out, unread_out,
+                          (hipStream_t)stream);
+}
+int blosc_gpu_aggregate_batch(int nchunks, const void* const* src, size_t row_bytes, const blosc_gpu_field* field, const blosc_gpu_predicate* filter,
+                              blosc_gpu_aggregate* total_out, blosc_gpu_aggregate* chunk_out, int* chunk_status_out, int* chunk_rows_out, size_t* unread_out,
+                              void* stream) {
+  AggField f; WherePred q;
+  const int c = aggregate_opening(nchunks, row_bytes, field, filter, &f, &q);
+  if (c != kGo) return c;
+  if (nchunks > 0 && !src) return -1;
+  return aggregate_call(nchunks, jobs_from_arrays(nchunks, src, nullptr, nullptr, nullptr), row_bytes, f, filter ? &q : nullptr, total_out, chunk_out,
+                        chunk_status_out, chunk_rows_out, unread_out, stream);
+}
+int blosc_gpu_aggregate_packed(int nchunks, const void* container, size_t containersize, const size_t* offsets, size_t row_bytes, const blosc_gpu_field* field,
+                               const blosc_gpu_predicate* filter, blosc_gpu_aggregate* total_out, blosc_gpu_aggregate* chunk_out, int* chunk_status_out,
+                               int* chunk_rows_out, size_t* unread_out, void* stream) {
+  AggField f; WherePred q;
+  const int c = aggregate_opening(nchunks, row_bytes, field, filter, &f, &q);
+  if (c != kGo) return c;
+  if (nchunks > 0 && (!container || !offsets)) return -1;
+  return aggregate_call(nchunks, jobs_from_spans(nchunks, container, containersize, offsets, nullptr, BLOSC_MIN_HEADER_LENGTH), row_bytes, f,
+                        filter ? &q : nullptr, total_out, chunk_out, chunk_status_out, chunk_rows_out, unread_out, stream);
 }
 
 // ---- adler32 / crc32 of many runs (include/blosc_gpu_checksum.h) ---------------------------------------

@@ -171,6 +171,49 @@ inline int64_t where_key(uint64_t v, int32_t kind, uint32_t bytes, uint64_t inf,
   return (v & sign) ? -(int64_t)mag : (int64_t)mag;
 }
 
+// The binary64 pattern of a floating-point field: v as where_key takes it, `mant` the mantissa bits of its format (binary16 10, bfloat16 7,
+// binary32 23, binary64 52).  Every value of the narrow formats is a binary64, so widening is exact; the pattern is put together from
+// integers - a subnormal is normalised by its leading bit - so that the floating-point mode of the wave (denormals flushed or kept) plays
+// no part.  Infinities stay infinities, a NaN stays a NaN.
+#if defined(__HIPCC__) || defined(__HIP__)
+__host__ __device__
+#endif
+inline uint64_t widen_to_f64(uint64_t v, uint32_t bytes, uint32_t mant) {
+  if (bytes == 8u) return v;
+  const uint32_t bits = 8u * bytes, ebits = bits - 1u - mant;
+  const uint64_t sign = (v >> (bits - 1u)) << 63, m = v & ((1ull << mant) - 1ull);
+  const uint32_t e = (uint32_t)(v >> mant) & ((1u << ebits) - 1u), bias = (1u << (ebits - 1u)) - 1u;
+  if (e == (1u << ebits) - 1u) return sign | (0x7ffull << 52) | (m << (52u - mant));
+  if (e) return sign | ((uint64_t)(e + 1023u - bias) << 52) | (m << (52u - mant));
+  if (!m) return sign;
+  const uint32_t p = 63u - (uint32_t)__builtin_clzll(m);      // m * 2^(1 - bias - mant) = 1.xxx * 2^(p + 1 - bias - mant)
+  return sign | ((uint64_t)(p + 1u + 1023u - bias - mant) << 52) | ((m ^ (1ull << p)) << (52u - p));
+}
+
+// The tables of k_aggregate_tiles / k_aggregate_chunks (k_aggregate.hip; include/blosc_gpu_aggregate.h), next to where's WhereChunk and tile prefix.
+// AggField: the aggregated field.  kind as in WherePred; inf and mant: its floating-point format (0 for the integers).
+struct AggField {
+  uint32_t offset, bytes;
+  int32_t kind;          // 0 UINT, 1 INT, 2 the floating-point formats
+  uint32_t mant;
+  uint64_t inf;
+};
+// AggPartial, one per tile: what its rows that pass the filter add up to.  The extremes are (key, row in chunk) pairs, the lower row winning
+// among equal keys; row AGG_NO_ROW: no value.  sum: a 64-bit integer, or the pattern of a binary64.
+constexpr uint32_t AGG_NO_ROW = 0xffffffffu;
+struct AggPartial {
+  int64_t min_key, max_key;
+  uint64_t sum;
+  uint32_t min_row, max_row;
+  uint32_t count, nans;
+};
+// AggResult, one per chunk: blosc_gpu_aggregate as the device writes it (min and max: the field's bytes, little endian, zero-extended)
+struct AggResult {
+  uint64_t rows, count, nans;
+  int64_t min_row, max_row;
+  uint64_t min, max, sum;
+};
+
 // Negative per-chunk status codes written by kernels (host maps them to the reference's
 // return values, blosc/blosc.c:762-782): -1 bad csize chain / bounds, -2 codec produced wrong size.
 enum : int32_t { ST_OK = 0, ST_BADCHAIN = -1, ST_BADCODEC = -2 };

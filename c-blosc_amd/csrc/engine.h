@@ -94,6 +94,16 @@ int engine_put(int nchunks, const Job* chunks, size_t row_bytes, size_t nidx, co
 struct WherePred;
 int engine_where(int nchunks, const Job* chunks, size_t row_bytes, const WherePred& pred, int64_t* index_out, size_t capacity, size_t* total_out,
                  int* chunk_matches_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream);
+// Count, sum, min and max of a row field (include/blosc_gpu_aggregate.h), over the array of rows engine_take reads, of the rows whose filter
+// field passes (filter nullptr: of every row).  field, filter: the caller's as the kernels evaluate them (dev_types.h: AggField, WherePred).
+// chunk_out [nchunks]: every chunk's result in blosc_gpu_aggregate's layout (dev_types.h: AggResult), the row numbers the call's; total_out: their
+// left fold in chunk order; chunk_status_out [nchunks]: 0, or the negative answer of the decoder for a chunk that does not decode, whose rows are
+// counted in unread_out; chunk_rows_out as in engine_take (all host, may be nullptr).  With a census failure the call answers -1 and writes
+// nothing but chunk_rows_out.
+struct AggField;
+struct AggResult;
+int engine_aggregate(int nchunks, const Job* chunks, size_t row_bytes, const AggField& field, const WherePred* filter, AggResult* total_out,
+                     AggResult* chunk_out, int* chunk_status_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream);
 
 // zlib's adler32 (kind 1) / crc32 (kind 2) of n runs in device memory (include/blosc_gpu_checksum.h): runs[i].src and runs[i].srcsize;
 // an empty run's pointer is never read.  digests[] is written only when the call answers 0.

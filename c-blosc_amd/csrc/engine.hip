@@ -28,6 +28,7 @@
 #include "k_take.hip"
 #include "k_put.hip"
 #include "k_where.hip"
+#include "k_aggregate.hip"
 
 namespace bamd {
 
@@ -2084,68 +2085,73 @@ int engine_put(int nchunks, const Job* chunks, size_t row_bytes, size_t nidx, co
 // Synchronisations: 2 + 2 per pass that holds a row, whatever the rows and the matches.
 // Memory.  As in engine_put the workspace lives in st.io and the tables' host images in st.put_pin, which the decode calls inside leave alone:
 // the plaintext of the largest pass, and per tile of WH_TILE rows of it WH_WORDS mask words, a count and a base (140 bytes per 1024 rows).
-int engine_where(int nchunks, const Job* chunks, size_t row_bytes, const WherePred& pred, int64_t* index_out, size_t capacity, size_t* total_out,
-                 int* chunk_matches_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream) {
-  CtxGuard ctx; EngineState& st = *ctx.st;
-  if (ensure_device(st)) return -1;
-  const size_t n = (size_t)(nchunks > 0 ? nchunks : 0);
+//
+// RowScan is that front half, which engine_aggregate shares (steps 1, 2 and the decode of step 3): census() fetches the headers and counts the
+// rows, deal() deals the chunks to passes and sizes the workspace - the plaintext of the largest pass, tile_bytes per tile of it, back_bytes
+// at D + o_back and their host image at P + o_back for what the call brings down at its end - and decode_pass() decodes the next pass into
+// its slots and uploads its chunk table and tile prefix.  What the caller launches behind it finds its tiles' words from D + at on.
+struct RowScan {
+  size_t n = 0, npass = 0, unread = 0;
   std::vector<Header> hdrs;
-  if (n && fetch_headers(st, (int)n, chunks, true, stream, hdrs)) return -1;
-  // ---- the census: take's; then index_out against every source - a call that fails the second writes nothing at all ----
-  std::vector<Job> jobs(chunks, chunks + n);
-  std::vector<RangeChunk> uc(n);
+  std::vector<Job> jobs;
   std::vector<TakeChunk> table;
-  std::vector<int> rows_of(n ? n : 1, 0);
-  const bool usable = rows_census(jobs, hdrs, row_bytes, /*whole_chunks*/ true, uc, table, rows_of.data());
-  if (!usable) {
+  std::vector<int> rows_of, pass_of, code;      // code, negative: what the decoder answered for the chunk
+  std::vector<uint32_t> tiles_of;
+  std::vector<size_t> ws_of;                    // per pass: plaintext slots + the tiles' words
+  size_t o_chunks = 0, o_tiles = 0, o_back = 0, o_ws = 0;
+  uint8_t *D = nullptr, *P = nullptr;
+  // the pass decode_pass() has just decoded: chunks [c0, c1), ntiles tiles, the workspace free from `at` on
+  size_t pass = 0, c0 = 0, c1 = 0, at = 0;
+  uint32_t ntiles = 0;
+  std::vector<Job> djobs; std::vector<int> dres; std::vector<size_t> live;
+
+  // one header fetch and take's census; *usable false: rows_of holds every chunk's rows or its negative code, and the call is to answer -1
+  int census(EngineState& st, int nchunks, const Job* chunks, size_t row_bytes, hipStream_t stream, bool* usable) {
+    n = (size_t)(nchunks > 0 ? nchunks : 0);
+    if (n && fetch_headers(st, (int)n, chunks, true, stream, hdrs)) return -1;
+    jobs.assign(chunks, chunks + n);
+    std::vector<RangeChunk> uc(n);
+    rows_of.assign(n ? n : 1, 0);
+    *usable = rows_census(jobs, hdrs, row_bytes, /*whole_chunks*/ true, uc, table, rows_of.data());
+    return 0;
+  }
+  void rows_to(int* chunk_rows_out) const {
     if (chunk_rows_out) std::copy(rows_of.begin(), rows_of.begin() + (ptrdiff_t)n, chunk_rows_out);
-    return -1;
   }
-  const uintptr_t d0 = (uintptr_t)index_out, d1 = d0 + capacity * sizeof(int64_t);
-  for (size_t k = 0; k < n && capacity; k++) {
-    const uintptr_t s0 = (uintptr_t)jobs[k].src, s1 = s0 + (jobs[k].srcsize ? jobs[k].srcsize : (size_t)hdrs[k].cbytes);
-    if (s0 < d1 && d0 < s1) return -1;
-  }
-  if (chunk_rows_out) std::copy(rows_of.begin(), rows_of.begin() + (ptrdiff_t)n, chunk_rows_out);
-  // ---- chunks dealt to passes in chunk order; the workspace of the largest pass ----
-  const size_t bound = std::min(g_getitem_pass_bytes.load(), (size_t)1 << 30);
-  const size_t tile_bytes = sizeof(uint64_t) * WH_WORDS + sizeof(uint32_t) + sizeof(uint64_t);
-  std::vector<int> pass_of(n, 0);
-  std::vector<uint32_t> tiles_of(n, 0);
-  std::vector<size_t> ws_of(1, 0);      // per pass: plaintext slots + the tiles' words
-  {
-    size_t in_pass = 0; int pass = 0;
+  // chunks dealt to passes in chunk order; the workspace of the largest pass
+  int deal(EngineState& st, size_t tile_bytes, size_t back_bytes) {
+    const size_t bound = std::min(g_getitem_pass_bytes.load(), (size_t)1 << 30);
+    pass_of.assign(n, 0); tiles_of.assign(n, 0); ws_of.assign(1, 0); code.assign(n, 0);
+    size_t in_pass = 0; int pass_at = 0;
     for (size_t k = 0; k < n; k++) {
       const size_t bytes = rows_of[k] ? align_up((size_t)hdrs[k].nbytes, 256) : 0;
-      if (in_pass && bytes && in_pass + bytes > bound) { pass++; in_pass = 0; ws_of.push_back(0); }
-      pass_of[k] = pass; in_pass += bytes;
+      if (in_pass && bytes && in_pass + bytes > bound) { pass_at++; in_pass = 0; ws_of.push_back(0); }
+      pass_of[k] = pass_at; in_pass += bytes;
       tiles_of[k] = (uint32_t)(((size_t)rows_of[k] + WH_TILE - 1) / WH_TILE);
-      ws_of[(size_t)pass] += bytes + tile_bytes * tiles_of[k];
+      ws_of[(size_t)pass_at] += bytes + tile_bytes * tiles_of[k];
     }
+    npass = ws_of.size();
+    Carver cv;
+    o_chunks = cv.take(sizeof(WhereChunk) * (n ? n : 1));
+    o_tiles = cv.take(sizeof(uint32_t) * (n + npass));      // pass p over chunks [c0, c1): entries [c0 + p, c1 + p]
+    o_back = cv.take(back_bytes);
+    const size_t table_bytes = cv.take(0);
+    o_ws = cv.take(*std::max_element(ws_of.begin(), ws_of.end()) + 4 * 256);
+    if (st.io.ensure(cv.off) || st.put_pin.ensure(table_bytes)) return -1;
+    D = st.io.base; P = st.put_pin.base;
+    return 0;
   }
-  const size_t npass = ws_of.size();
-  Carver cv;
-  const size_t o_chunks = cv.take(sizeof(WhereChunk) * (n ? n : 1));
-  const size_t o_tiles = cv.take(sizeof(uint32_t) * (n + npass));      // pass p over chunks [c0, c1): entries [c0 + p, c1 + p]
-  const size_t o_back = cv.take(sizeof(uint64_t) + sizeof(uint32_t) * (n ? n : 1));      // the running total, then the chunks' counters
-  const size_t table_bytes = cv.take(0);
-  const size_t o_ws = cv.take(*std::max_element(ws_of.begin(), ws_of.end()) + 4 * 256);
-  if (st.io.ensure(cv.off) || st.put_pin.ensure(table_bytes)) return -1;
-  uint8_t *D = st.io.base, *P = st.put_pin.base;
-  WhereChunk* h_chunks = (WhereChunk*)(P + o_chunks);
-  uint32_t* h_tiles = (uint32_t*)(P + o_tiles);
-  uint64_t* d_running = (uint64_t*)(D + o_back);
-  uint32_t* d_count = (uint32_t*)(D + o_back + sizeof(uint64_t));
-  HIP_TRY(hipMemsetAsync(D + o_back, 0, sizeof(uint64_t) + sizeof(uint32_t) * (n ? n : 1), stream));
-  std::vector<int> code(n, 0);      // negative: what the decoder answered for the chunk
-  size_t unread = 0;
-  std::vector<Job> djobs; std::vector<int> dres; std::vector<size_t> live;
-  for (size_t p = 0, c0 = 0; p < npass; p++) {
-    size_t c1 = c0;
-    while (c1 < n && pass_of[c1] == (int)p) c1++;
-    // ---- the pass's chunks decode into their slots ----
-    size_t at = o_ws;
-    uint32_t* tiles = h_tiles + c0 + p;
+  const WhereChunk* d_chunks() const { return (const WhereChunk*)(D + o_chunks) + c0; }
+  const uint32_t* d_tiles() const { return (const uint32_t*)(D + o_tiles) + c0 + pass; }
+  // Pass p = 0, 1, ... npass - 1, in this order: its chunks decode into their slots, the verdicts enter the chunk table, table and tile prefix go up.
+  // *holds_rows false: no chunk of the pass holds a row, nothing was launched and nothing is to be
+  int decode_pass(EngineState& st, size_t p, hipStream_t stream, bool* holds_rows) {
+    pass = p;
+    c0 = p ? c1 : 0; c1 = c0;
+    while (c1 < n && pass_of[c1] == (int)pass) c1++;
+    WhereChunk* h_chunks = (WhereChunk*)(P + o_chunks);
+    uint32_t* tiles = (uint32_t*)(P + o_tiles) + c0 + pass;
+    at = o_ws;
     tiles[0] = 0;
     djobs.clear(); live.clear();
     for (size_t k = c0; k < c1; k++) {
@@ -2157,24 +2163,59 @@ int engine_where(int nchunks, const Job* chunks, size_t row_bytes, const WherePr
       live.push_back(k);
       at += align_up((size_t)hdrs[k].nbytes, 256);
     }
-    const uint32_t ntiles = tiles[c1 - c0];
-    if (!live.empty()) {
-      dres.assign(live.size(), -1);
-      if (decompress_batch_in(st, (int)live.size(), djobs.data(), dres.data(), true, stream, nullptr)) return -1;
-      for (size_t i = 0; i < live.size(); i++) {
-        const size_t k = live[i];
-        if (dres[i] == hdrs[k].nbytes) { h_chunks[k].status = 0; continue; }
-        code[k] = dres[i] < 0 ? dres[i] : -1;      // blosc.c:1511-1514: the chunk holds no row anybody can read
-        unread += (size_t)rows_of[k];
-      }
-      Carver wv; wv.off = at;
+    ntiles = tiles[c1 - c0];
+    *holds_rows = !live.empty();
+    if (live.empty()) return 0;
+    dres.assign(live.size(), -1);
+    if (decompress_batch_in(st, (int)live.size(), djobs.data(), dres.data(), true, stream, nullptr)) return -1;
+    for (size_t i = 0; i < live.size(); i++) {
+      const size_t k = live[i];
+      if (dres[i] == hdrs[k].nbytes) { h_chunks[k].status = 0; continue; }
+      code[k] = dres[i] < 0 ? dres[i] : -1;      // blosc.c:1511-1514: the chunk holds no row anybody can read
+      unread += (size_t)rows_of[k];
+    }
+    HIP_TRY(hipMemcpyAsync(D + o_chunks + sizeof(WhereChunk) * c0, h_chunks + c0, sizeof(WhereChunk) * (c1 - c0), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(D + o_tiles + sizeof(uint32_t) * (c0 + pass), tiles, sizeof(uint32_t) * (c1 - c0 + 1), hipMemcpyHostToDevice, stream));
+    return 0;
+  }
+};
+
+int engine_where(int nchunks, const Job* chunks, size_t row_bytes, const WherePred& pred, int64_t* index_out, size_t capacity, size_t* total_out,
+                 int* chunk_matches_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream) {
+  CtxGuard ctx; EngineState& st = *ctx.st;
+  if (ensure_device(st)) return -1;
+  // ---- the census: take's; then index_out against every source - a call that fails the second writes nothing at all ----
+  RowScan rs;
+  bool usable = false;
+  if (rs.census(st, nchunks, chunks, row_bytes, stream, &usable)) return -1;
+  const size_t n = rs.n;
+  if (!usable) { rs.rows_to(chunk_rows_out); return -1; }
+  const uintptr_t d0 = (uintptr_t)index_out, d1 = d0 + capacity * sizeof(int64_t);
+  for (size_t k = 0; k < n && capacity; k++) {
+    const uintptr_t s0 = (uintptr_t)rs.jobs[k].src, s1 = s0 + (rs.jobs[k].srcsize ? rs.jobs[k].srcsize : (size_t)rs.hdrs[k].cbytes);
+    if (s0 < d1 && d0 < s1) return -1;
+  }
+  rs.rows_to(chunk_rows_out);
+  // ---- the passes: per tile its mask words, a count and a base; the running total and the chunks' counters come down at the end ----
+  const size_t back_bytes = sizeof(uint64_t) + sizeof(uint32_t) * (n ? n : 1);
+  if (rs.deal(st, sizeof(uint64_t) * WH_WORDS + sizeof(uint32_t) + sizeof(uint64_t), back_bytes)) return -1;
+  uint8_t *D = rs.D, *P = rs.P;
+  const size_t o_back = rs.o_back;
+  uint64_t* d_running = (uint64_t*)(D + o_back);
+  uint32_t* d_count = (uint32_t*)(D + o_back + sizeof(uint64_t));
+  HIP_TRY(hipMemsetAsync(D + o_back, 0, back_bytes, stream));
+  for (size_t p = 0; p < rs.npass; p++) {
+    bool holds_rows = false;
+    if (rs.decode_pass(st, p, stream, &holds_rows)) return -1;
+    if (holds_rows) {
+      const size_t c0 = rs.c0, c1 = rs.c1;
+      const uint32_t ntiles = rs.ntiles;
+      Carver wv; wv.off = rs.at;
       uint64_t* d_masks = (uint64_t*)(D + wv.take(sizeof(uint64_t) * WH_WORDS * ntiles));
       uint32_t* d_tile_count = (uint32_t*)(D + wv.take(sizeof(uint32_t) * ntiles));
       uint64_t* d_tile_base = (uint64_t*)(D + wv.take(sizeof(uint64_t) * ntiles));
-      const WhereChunk* d_chunks = (const WhereChunk*)(D + o_chunks) + c0;
-      const uint32_t* d_tiles = (const uint32_t*)(D + o_tiles) + c0 + p;
-      HIP_TRY(hipMemcpyAsync(D + o_chunks + sizeof(WhereChunk) * c0, h_chunks + c0, sizeof(WhereChunk) * (c1 - c0), hipMemcpyHostToDevice, stream));
-      HIP_TRY(hipMemcpyAsync(D + o_tiles + sizeof(uint32_t) * (c0 + p), tiles, sizeof(uint32_t) * (c1 - c0 + 1), hipMemcpyHostToDevice, stream));
+      const WhereChunk* d_chunks = rs.d_chunks();
+      const uint32_t* d_tiles = rs.d_tiles();
       const dim3 grid(persistent_grid(st, ntiles, WH_WAVES_PER_CU / WH_WAVES));
       {
         ProfScope ps(st, stream, "k_where_mark");
@@ -2194,7 +2235,6 @@ int engine_where(int nchunks, const Job* chunks, size_t row_bytes, const WherePr
         HIP_TRY(hipGetLastError());
       }
     }
-    c0 = c1;
   }
   // ---- collect ----
   const uint32_t* h_count = (const uint32_t*)(P + o_back + sizeof(uint64_t));
@@ -2203,11 +2243,90 @@ int engine_where(int nchunks, const Job* chunks, size_t row_bytes, const WherePr
   prof_collect(st);
   size_t total = 0;
   for (size_t k = 0; k < n; k++) {
-    if (code[k] >= 0) total += (size_t)h_count[k];
-    if (chunk_matches_out) chunk_matches_out[k] = code[k] < 0 ? code[k] : (int)h_count[k];
+    if (rs.code[k] >= 0) total += (size_t)h_count[k];
+    if (chunk_matches_out) chunk_matches_out[k] = rs.code[k] < 0 ? rs.code[k] : (int)h_count[k];
   }
   if (total_out) *total_out = total;
-  if (unread_out) *unread_out = unread;
+  if (unread_out) *unread_out = rs.unread;
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// aggregate (include/blosc_gpu_aggregate.h): count, sum, min and max of a row field, per chunk and for the call
+// ---------------------------------------------------------------------------------------------
+// engine_where's front half (RowScan) around the two kernels of k_aggregate.hip: per pass k_aggregate_tiles writes one AggPartial per tile,
+// k_aggregate_chunks folds them into the chunks' entries of a device table of nchunks AggResult, which comes down with the last
+// synchronisation.  Synchronisations: 2 + 2 per pass that holds a row.  Memory: the plaintext of the largest pass, 40 bytes per tile of
+// WH_TILE rows of it, 64 bytes per chunk.
+// The call's total is folded here, on the host, from the chunks' results in chunk order: what a chunk answers does not depend on its neighbours.
+static void aggregate_none(AggResult* r) { *r = AggResult{0, 0, 0, -1, -1, 0, 0, 0}; }
+static void aggregate_fold(AggResult* total, const AggResult& c, const AggField& f) {
+  bool nan;
+  total->rows += c.rows; total->count += c.count; total->nans += c.nans;
+  if (f.kind == 2) {
+    double a, b;
+    memcpy(&a, &total->sum, 8); memcpy(&b, &c.sum, 8);
+    a += b;
+    memcpy(&total->sum, &a, 8);
+  } else total->sum += c.sum;
+  // the smaller min and the larger max win, the earlier chunk among equals
+  if (c.min_row >= 0 && (total->min_row < 0 || where_key(c.min, f.kind, f.bytes, f.inf, &nan) < where_key(total->min, f.kind, f.bytes, f.inf, &nan))) {
+    total->min_row = c.min_row; total->min = c.min;
+  }
+  if (c.max_row >= 0 && (total->max_row < 0 || where_key(c.max, f.kind, f.bytes, f.inf, &nan) > where_key(total->max, f.kind, f.bytes, f.inf, &nan))) {
+    total->max_row = c.max_row; total->max = c.max;
+  }
+}
+int engine_aggregate(int nchunks, const Job* chunks, size_t row_bytes, const AggField& field, const WherePred* filter, AggResult* total_out,
+                     AggResult* chunk_out, int* chunk_status_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream) {
+  CtxGuard ctx; EngineState& st = *ctx.st;
+  if (ensure_device(st)) return -1;
+  RowScan rs;
+  bool usable = false;
+  if (rs.census(st, nchunks, chunks, row_bytes, stream, &usable)) return -1;
+  const size_t n = rs.n;
+  rs.rows_to(chunk_rows_out);
+  if (!usable) return -1;
+  const size_t back_bytes = sizeof(AggResult) * (n ? n : 1);
+  if (rs.deal(st, sizeof(AggPartial), back_bytes)) return -1;
+  uint8_t *D = rs.D, *P = rs.P;
+  AggResult* d_results = (AggResult*)(D + rs.o_back);
+  const WherePred q = filter ? *filter : WherePred{};
+  for (size_t p = 0; p < rs.npass; p++) {
+    bool holds_rows = false;
+    if (rs.decode_pass(st, p, stream, &holds_rows)) return -1;
+    if (!holds_rows) continue;
+    const int in_pass = (int)(rs.c1 - rs.c0);
+    Carver wv; wv.off = rs.at;
+    AggPartial* d_partials = (AggPartial*)(D + wv.take(sizeof(AggPartial) * rs.ntiles));
+    {
+      ProfScope ps(st, stream, "k_aggregate_tiles");
+      hipLaunchKernelGGL(k_aggregate_tiles, dim3(persistent_grid(st, rs.ntiles, WH_WAVES_PER_CU / WH_WAVES)), dim3(WH_THREADS), 0, stream, rs.d_chunks(),
+                         rs.d_tiles(), in_pass, (uint32_t)row_bytes, field, q, filter ? 1 : 0, d_partials);
+      HIP_TRY(hipGetLastError());
+    }
+    ProfScope ps(st, stream, "k_aggregate_chunks");
+    hipLaunchKernelGGL(k_aggregate_chunks, dim3(persistent_grid(st, (size_t)in_pass, WH_WAVES_PER_CU / WH_WAVES)), dim3(WH_THREADS), 0, stream, rs.d_chunks(),
+                       rs.d_tiles(), in_pass, (uint32_t)row_bytes, field, (const AggPartial*)d_partials, d_results + rs.c0);
+    HIP_TRY(hipGetLastError());
+  }
+  // ---- collect: the chunks' entries; a chunk without rows, or one that did not decode, was in no launch or counts nothing ----
+  const AggResult* h_results = (const AggResult*)(P + rs.o_back);
+  if (n) HIP_TRY(hipMemcpyAsync(P + rs.o_back, d_results, sizeof(AggResult) * n, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  prof_collect(st);
+  AggResult total;
+  aggregate_none(&total);
+  for (size_t k = 0; k < n; k++) {
+    AggResult r;
+    aggregate_none(&r);
+    if (rs.rows_of[k] && rs.code[k] >= 0) r = h_results[k];
+    aggregate_fold(&total, r, field);
+    if (chunk_out) chunk_out[k] = r;
+    if (chunk_status_out) chunk_status_out[k] = rs.code[k];
+  }
+  if (total_out) *total_out = total;
+  if (unread_out) *unread_out = rs.unread;
   return 0;
 }
 

@@ -11,10 +11,13 @@ back by a device index tensor: index_select on the compressed table, one blosc_g
 (include/blosc_gpu_put.h): only the chunks a row lands in are decoded and compressed again.
 `where_rows` makes the index tensor both read - the rows whose column satisfies a comparison with a scalar, torch.nonzero on the compressed
 table - by blosc_gpu_where_packed (include/blosc_gpu_where.h), holding one pass of plaintext at a time.
+`aggregate_rows` reduces a column over such rows - count, sum, min, max and the rows of the extremes, per chunk and for the table - by
+blosc_gpu_aggregate_packed (include/blosc_gpu_aggregate.h), without an index table.
 
 Like blpk.py's device functions this module only drives the library: `lib` is the ctypes handle (load() of the package), memory comes
 from a `mem` with blpk.TorchMem's alloc().  There is no CPU implementation: without the library and a GPU the calls fail.
 """
+import collections
 import ctypes as C
 import importlib.util
 import os
@@ -177,6 +180,40 @@ def take_rows(lib, container, offsets, meta, index, mem=None, stream=None):
 _WHERE_OPS = {"eq": 0, "ne": 1, "lt": 2, "le": 3, "gt": 4, "ge": 5, "==": 0, "!=": 1, "<": 2, "<=": 3, ">": 4, ">=": 5}
 
 
+def _table_fields(pkg, meta, call, *columns):
+    """What where_rows and aggregate_rows read from `meta`: (the table's dtype, its field kind, its element size, the bytes of a row);
+    ValueError for chunks that are not slices of one table, a dtype without a field kind, rows `call` does not take, a column outside the row"""
+    import torch
+    dtype, row_shape = meta[0][0], tuple(meta[0][1][1:])
+    if any(dt != dtype or tuple(shape[1:]) != row_shape for dt, shape in meta):
+        raise ValueError("the container's chunks are not slices of one table")
+    kinds = {torch.uint8: pkg.FIELD_UINT, torch.bool: pkg.FIELD_UINT, torch.int8: pkg.FIELD_INT, torch.int16: pkg.FIELD_INT, torch.int32: pkg.FIELD_INT,
+             torch.int64: pkg.FIELD_INT, torch.float16: pkg.FIELD_FLOAT, torch.float32: pkg.FIELD_FLOAT, torch.float64: pkg.FIELD_FLOAT,
+             torch.bfloat16: pkg.FIELD_BFLOAT16}
+    if dtype not in kinds:
+        raise ValueError(f"no predicate for a table of {dtype}")
+    element = int(torch.empty(0, dtype=dtype).element_size())
+    per_row = int(torch.Size(row_shape).numel())
+    row_bytes = element * per_row
+    if not 1 <= row_bytes <= 65536:
+        raise ValueError(f"rows of {row_bytes} bytes: {call} takes 1 ... 65536")
+    for column in columns:
+        if not 0 <= column < per_row:
+            raise ValueError(f"column {column} of rows of {per_row} elements")
+    return dtype, kinds[dtype], element, row_bytes
+
+
+def _where_predicate(pkg, dtype, kind, element, op, value, column):
+    """column `op` value as a Predicate; ValueError for an op nobody knows"""
+    import torch
+    name = getattr(op, "__name__", op)
+    if name not in _WHERE_OPS:
+        raise ValueError(f"op {op!r}: one of {sorted(_WHERE_OPS)}")
+    # the constant in the table's own representation: torch rounds it as it would round the scalar of the comparison
+    raw = bytes(torch.tensor([value], dtype=dtype).view(torch.uint8).tolist())
+    return pkg.predicate(kind, element, _WHERE_OPS[name], raw, offset=column * element)
+
+
 def where_rows(lib, container, offsets, meta, op, value, column=0, max_matches=None, mem=None, stream=None):
     """torch.nonzero(op(table.reshape(nrows, -1)[:, column], value)).flatten() for the table pack_rows packed, without its plaintext:
     blosc_gpu_where_packed (include/blosc_gpu_where.h) decodes pass by pass and keeps the row numbers alone.  op: "eq" / "ne" / "lt" / "le" /
@@ -191,27 +228,8 @@ def where_rows(lib, container, offsets, meta, op, value, column=0, max_matches=N
     pkg = _sibling("", "__init__.py")
     mem = mem if mem is not None else _sibling("blpk", "blpk.py").TorchMem()
     pkg.declare_where(lib)
-    dtype, row_shape = meta[0][0], tuple(meta[0][1][1:])
-    if any(dt != dtype or tuple(shape[1:]) != row_shape for dt, shape in meta):
-        raise ValueError("the container's chunks are not slices of one table")
-    kinds = {torch.uint8: pkg.FIELD_UINT, torch.bool: pkg.FIELD_UINT, torch.int8: pkg.FIELD_INT, torch.int16: pkg.FIELD_INT, torch.int32: pkg.FIELD_INT,
-             torch.int64: pkg.FIELD_INT, torch.float16: pkg.FIELD_FLOAT, torch.float32: pkg.FIELD_FLOAT, torch.float64: pkg.FIELD_FLOAT,
-             torch.bfloat16: pkg.FIELD_BFLOAT16}
-    if dtype not in kinds:
-        raise ValueError(f"no predicate for a table of {dtype}")
-    element = int(torch.empty(0, dtype=dtype).element_size())
-    per_row = int(torch.Size(row_shape).numel())
-    row_bytes = element * per_row
-    if not 1 <= row_bytes <= 65536:
-        raise ValueError(f"rows of {row_bytes} bytes: blosc_gpu_where_packed takes 1 ... 65536")
-    if not 0 <= column < per_row:
-        raise ValueError(f"column {column} of rows of {per_row} elements")
-    name = getattr(op, "__name__", op)
-    if name not in _WHERE_OPS:
-        raise ValueError(f"op {op!r}: one of {sorted(_WHERE_OPS)}")
-    # the constant in the table's own representation: torch rounds it as it would round the scalar of the comparison
-    raw = bytes(torch.tensor([value], dtype=dtype).view(torch.uint8).tolist())
-    pred = pkg.predicate(kinds[dtype], element, _WHERE_OPS[name], raw, offset=column * element)
+    dtype, kind, element, row_bytes = _table_fields(pkg, meta, "blosc_gpu_where_packed", column)
+    pred = _where_predicate(pkg, dtype, kind, element, op, value, column)
     where = pkg.RowWhere(row_bytes, lib=lib)
 
     def call(ptr, capacity):
@@ -233,6 +251,46 @@ def where_rows(lib, container, offsets, meta, op, value, column=0, max_matches=N
     elif total is None:
         total = call(None, 0)
     return keep[:min(total, capacity) * 8].view(torch.int64), total
+
+
+class Aggregated(collections.namedtuple("Aggregated", "count nans sum min max argmin argmax chunks")):
+    """What aggregate_rows answers: the rows counted, the NaNs among them (left out of the rest), the sum (an int, modulo 2^64 as the dtype's
+    signedness reads it; a float for the floating-point dtypes), min and max as scalars of the table's dtype with the lowest row that holds
+    each (None: no value), and `chunks`: the same per chunk (their own `chunks` is None)"""
+    __slots__ = ()
+
+
+def aggregate_rows(lib, container, offsets, meta, column=0, where=None, mem=None, stream=None):
+    """count / sum / min / max / argmin / argmax of table.reshape(nrows, -1)[:, column] for the table pack_rows packed, without its plaintext and
+    without an index table: ONE blosc_gpu_aggregate_packed (include/blosc_gpu_aggregate.h), which decodes pass by pass and keeps 64 bytes per
+    chunk.  where=(op, value, column): only the rows whose `column` (any column of the row) satisfies the comparison, with where_rows' op names
+    and value; None: every row.  The field's type is the table's dtype, as in where_rows.  NaNs are counted in `nans` and left out of sum, min
+    and max; the floating-point sum is added in float64, in an order the chunk's row count fixes (the header has the rules).
+    Returns an Aggregated; its `chunks` are the per-chunk results - their min and max are a zone map of the container.
+    Raises, like where_rows, if the container does not hold this table or if any row was unread (a chunk that does not decode)."""
+    import torch
+    pkg = _sibling("", "__init__.py")
+    pkg.declare_aggregate(lib)
+    columns = (column,) if where is None else (column, where[2] if len(where) > 2 else 0)
+    dtype, kind, element, row_bytes = _table_fields(pkg, meta, "blosc_gpu_aggregate_packed", *columns)
+    pred = None if where is None else _where_predicate(pkg, dtype, kind, element, where[0], where[1], columns[1])
+    agg = pkg.RowAggregate(row_bytes, lib=lib)
+    if agg.packed(container.data_ptr(), int(container.numel()), list(offsets), pkg.field(kind, element, offset=column * element), pred, stream) != 0:
+        raise RuntimeError(f"blosc_gpu_aggregate_packed failed; rows per chunk (negative: the chunk's code): {agg.chunk_rows()}")
+    if agg.chunk_rows() != [int(shape[0]) for _, shape in meta]:
+        raise RuntimeError(f"the container does not hold this table: rows per chunk {agg.chunk_rows()}")
+    if agg.unread():
+        raise RuntimeError(f"{agg.unread()} of {sum(agg.chunk_rows())} rows were not read (chunks that do not decode: {agg.chunk_status()})")
+
+    def scalar(raw):
+        return torch.tensor(list(raw[:element]), dtype=torch.uint8).view(dtype)[0].item()
+
+    def result(a, chunks):
+        total = a.sum.f if dtype.is_floating_point else (a.sum.i if kind == pkg.FIELD_INT else a.sum.u)
+        return Aggregated(int(a.count), int(a.nans), total, scalar(a.min) if a.min_row >= 0 else None, scalar(a.max) if a.max_row >= 0 else None,
+                          int(a.min_row) if a.min_row >= 0 else None, int(a.max_row) if a.max_row >= 0 else None, chunks)
+
+    return result(agg.total(), [result(c, None) for c in agg.chunks()])
 
 
 def put_rows(lib, container, offsets, meta, index, rows, mem=None, stream=None, align=256, **settings):

@@ -204,12 +204,23 @@ def _table_fields(pkg, meta, call, *columns):
 
 
 def _where_predicate(pkg, dtype, kind, element, op, value, column):
-    """column `op` value as a Predicate; ValueError for an op nobody knows"""
+    """column `op` value as a Predicate; ValueError for an op nobody knows, and for a value that an integer (or bool) dtype does not hold"""
     import torch
     name = getattr(op, "__name__", op)
     if name not in _WHERE_OPS:
         raise ValueError(f"op {op!r}: one of {sorted(_WHERE_OPS)}")
-    # the constant in the table's own representation: torch rounds it as it would round the scalar of the comparison
+    if not dtype.is_floating_point:
+        # an integer column is compared with the value itself: 1.5, a NaN or 300 on uint8 is no constant of the dtype, and rounding or
+        # wrapping it would answer another question than torch's op(column, value)
+        low, high = (0, 1) if dtype == torch.bool else (torch.iinfo(dtype).min, torch.iinfo(dtype).max)
+        try:
+            whole = int(value)
+        except (TypeError, ValueError, OverflowError):      # a NaN, an infinity, no number at all
+            whole = None
+        if whole is None or whole != value or not low <= whole <= high:
+            raise ValueError(f"the value {value!r} is none that {dtype} holds: a table of integers is compared with an integer of {low} ... {high}")
+        value = whole
+    # the constant in the table's own representation: torch rounds a floating-point one as it would round the scalar of the comparison
     raw = bytes(torch.tensor([value], dtype=dtype).view(torch.uint8).tolist())
     return pkg.predicate(kind, element, _WHERE_OPS[name], raw, offset=column * element)
 
@@ -220,6 +231,10 @@ def where_rows(lib, container, offsets, meta, op, value, column=0, max_matches=N
     "gt" / "ge" (or "==", "!=", ...; the functions of `operator` and the torch comparisons are taken by their name), value: a scalar of the
     table's dtype, column: the flat element number inside a row.  The predicate's type is the table's dtype: torch.uint8 and bool are
     unsigned bytes, int8 ... int64, float16 / float32 / float64, bfloat16; any other raises ValueError.
+    The value of a floating-point table is rounded to the dtype, as torch rounds the scalar of its own comparison (0.1 on float16 is the
+    float16 next to 0.1, 1e6 on float16 is inf).  The value of an integer or bool table must be one the dtype holds - an int, a bool or an
+    integral float such as 2.0 inside its range: 1.5, a NaN, an infinity, 300 on uint8 or 2**63 on int64 raise ValueError and are never
+    rounded or wrapped into another constant.
     Returns (index, total): an int64 device tensor - what take_rows and put_rows read - and the number of matches.  With max_matches the
     table has min(total, max_matches) entries, the first ones, and one call is made.  With max_matches=None TWO calls are made: one with
     capacity 0 that counts, one that fills a table of exactly `total` (none if nothing matches).
@@ -264,7 +279,8 @@ def aggregate_rows(lib, container, offsets, meta, column=0, where=None, mem=None
     """count / sum / min / max / argmin / argmax of table.reshape(nrows, -1)[:, column] for the table pack_rows packed, without its plaintext and
     without an index table: ONE blosc_gpu_aggregate_packed (include/blosc_gpu_aggregate.h), which decodes pass by pass and keeps 64 bytes per
     chunk.  where=(op, value, column): only the rows whose `column` (any column of the row) satisfies the comparison, with where_rows' op names
-    and value; None: every row.  The field's type is the table's dtype, as in where_rows.  NaNs are counted in `nans` and left out of sum, min
+    and value - rounded to a floating-point dtype as torch rounds it, ValueError if an integer or bool dtype does not hold it (1.5, a NaN,
+    300 on uint8); None: every row.  The field's type is the table's dtype, as in where_rows.  NaNs are counted in `nans` and left out of sum, min
     and max; the floating-point sum is added in float64, in an order the chunk's row count fixes (the header has the rules).
     Returns an Aggregated; its `chunks` are the per-chunk results - their min and max are a zone map of the container.
     Raises, like where_rows, if the container does not hold this table or if any row was unread (a chunk that does not decode)."""

@@ -4,7 +4,9 @@ is the oracle's orc_decompress (take_checks.plaintext), the field view is where_
 where_checks.expected, count and nans are numpy's, min and max numpy's over the selected values that are no NaN with the first index that
 attains them, integer sums numpy's with dtype uint64 / int64 (which wraps as the contract does), and a floating-point sum is math.fsum: equal
 where every partial sum is exact, else within the bound of n - 1 binary64 additions in any order, n u A / (1 - n u) with u = 2^-53 and
-A = fsum(|x|), computed in fractions.Fraction.  The tables are where_checks' (make_table, drawn, value_set, where_chunks, table_call)."""
+A = fsum(|x|), computed in fractions.Fraction.  The tables are where_checks' (make_table, drawn, value_set, where_chunks, table_call, table16,
+neighbour_set); the exact-sum windows (WINDOWS) put every finite value of binary16 and bfloat16, and binary32 over all its exponent fields,
+through the widening and the additions, with the precondition of an exact sum asserted in integers before each call (assert_exact_window)."""
 import ctypes as C
 import math
 import struct
@@ -16,8 +18,9 @@ from getitem_ranges_checks import plain
 from helpers import header, orc_compress
 from take_checks import N, TakeSource, chunk_rows, pack_container, plaintext
 from test_emu_take import SETTINGS  # noqa: F401  (re-exported to the test files)
-from where_checks import (BFLOAT16, FLOAT, INT, INT_SENTINEL, KINDS, LAYOUTS, OPS, SIZE_SENTINEL, UINT, Env, both_sources, comparable,  # noqa: F401
-                          decoder_code, drawn, field_of, kind_name, make_table, predicate, table_call, total_rows, value_set, where_chunks)
+from where_checks import (BFLOAT16, FLOAT, INT, INT_SENTINEL, KINDS, KINDS16, LAYOUTS, LAYOUTS16, MANTISSA, NEIGHBOUR_KINDS, OPS, SIZE_SENTINEL,  # noqa: F401
+                          UINT, Env, both_sources, comparable, constants16, decoder_code, drawn, field_of, kind_name, make_table, neighbour_set,
+                          predicate, regime, table16, table_call, thin_constants16, thin_neighbour_picks, total_rows, value_set, where_chunks)
 
 SENTINEL = 0xA5
 EQ, NE, LT, LE, GT, GE = range(6)
@@ -220,6 +223,65 @@ def case_kind(env, kind, nbytes, setting, turn=0, thin=False):
             assert total[7] == true % 2 ** 64
 
 
+def case_neighbours(env, kind, nbytes, setting, turn=0, thin=False):
+    """case 1 on where's neighbour set of the kind: unfiltered, and under LT c and GT c for every constant c of the set (thin: under two of
+    where's thin_neighbour_picks)"""
+    values = neighbour_set(kind, nbytes)
+    patterns = drawn(values, total_rows(17, setting[3]), seed=6)
+    if (kind, nbytes) == (FLOAT, 8):
+        # binary64's largest finite value added to itself overflows, and an infinity made on the way meets the table's other one as a NaN:
+        # float_sum's answer (an infinity among the values is the sum) holds for additions that do not overflow.  One row of each sign, then
+        big, sign = regime(FLOAT, 8)["max_finite"], 1 << 63
+        patterns = drawn([v for v in values if v & (sign - 1) != big], patterns.size, seed=6)
+        patterns[5], patterns[700] = big, sign | big
+    # (binary64: every row of the MEMCPYED chunk has its field set as well - random patterns reach 2^1023)
+    chunks, rows_plain = table_call(env, setting, (17, 3, kind, nbytes), patterns, turn, memcpyed_step=1 if (kind, nbytes) == (FLOAT, 8) else 4)
+    if kind in (FLOAT, BFLOAT16):
+        with np.errstate(invalid="ignore"):      # (a signalling NaN on its way to binary64)
+            x = field_of(rows_plain, 17, 3, kind, nbytes).astype(np.float64)
+        for one_sign in (x[np.isfinite(x) & (x > 0)], -x[np.isfinite(x) & (x < 0)]):
+            assert sum(map(Fraction, one_sign.tolist())) < 2 ** 1024 - 2 ** 970, "the finite values of one sign overflow binary64 on the way"
+    src = TakeSource(env.mem, chunks=chunks)
+    picks = [None] + (thin_neighbour_picks(kind, nbytes)[:2] if thin else [(op, c) for c in values for op in (LT, GT)])
+    for pick in picks:
+        flt = None if pick is None else (3, kind, nbytes, pick[0], pick[1])
+        check_aggregate(env, src, chunks, rows_plain, 17, (3, kind, nbytes), flt, what=("neighbours", setting))
+
+
+def neighbour16(kind, constant, op, row_of):
+    """(row, pattern) of the maximum under LT constant / the minimum under GT constant in the table of every 16-bit pattern, from the format's
+    order alone: the integer next to it; the floating-point key - the magnitude, negated under the sign - next to the constant's, key 0 being
+    whichever zero has the lower row.  None: no row (the end of the range, a NaN constant).  row_of[pattern]: the pattern's row"""
+    step = -1 if op == LT else 1
+    if kind in (UINT, INT):
+        v = (constant - 0x10000 if kind == INT and constant >= 0x8000 else constant) + step
+        low, high = (0, 0xffff) if kind == UINT else (-0x8000, 0x7fff)
+        if not low <= v <= high: return None
+        return int(row_of[v % 0x10000]), v % 0x10000
+    inf, mag = regime(kind, 2)["inf"], constant & 0x7fff
+    key = (-mag if constant & 0x8000 else mag) + step
+    if mag > inf or abs(key) > inf: return None
+    p = min((0, 0x8000), key=lambda q: row_of[q]) if key == 0 else key if key > 0 else 0x8000 | -key
+    return int(row_of[p]), p
+
+
+def case_patterns16(env, kind, row_layout, constants, turn=0):
+    """where's table of every 16-bit pattern: the field under LT c and under GT c for each constant c.  The maximum under LT c and the minimum
+    under GT c are c's neighbours in the format's order - asserted against numpy by check_aggregate and against neighbour16"""
+    row_bytes, offset = row_layout
+    chunks, rows_plain = table16(env, row_layout, turn)
+    src = TakeSource(env.mem, chunks=chunks)
+    row_of = np.empty(1 << 16, np.int64)
+    row_of[field_of(rows_plain, row_bytes, offset, UINT, 2)] = np.arange(1 << 16)
+    for constant in constants:
+        for op in (LT, GT):
+            what = ("every pattern", kind_name(kind, 2), OPS[op].__name__, hex(constant))
+            total, _ = check_aggregate(env, src, chunks, rows_plain, row_bytes, (offset, kind, 2), (offset, kind, 2, op, constant), what=what)
+            want = neighbour16(kind, constant, op, row_of)
+            got = (total[4], total[6]) if op == LT else (total[3], total[5])
+            assert got == ((-1, bytes(8)) if want is None else (want[0], want[1].to_bytes(2, "little") + bytes(6))), (what, got, want)
+
+
 def case_layout(env, layout, setting, turn=0, stream=None):
     """case 2, where's LAYOUTS: the layout's field aggregated, unfiltered and filtered on itself, through both entry points"""
     row_bytes, offset, kind, nbytes = layout
@@ -383,6 +445,89 @@ def case_sum_subnormals(env, kind, nbytes, nrows, turn=0):
     chunks, rows_plain = sum_call(env, np.ones(nrows, np.uint64), nbytes, turn)
     total, _ = check_aggregate(env, TakeSource(env.mem, chunks=chunks), chunks, rows_plain, 12, (3, kind, nbytes), exact=True, what="subnormals")
     assert total[1] == nrows and as_f64(total[7]) == math.ldexp(nrows, SMALLEST[(kind, nbytes)]) > 0
+
+
+# ---- exact-sum windows: every value of a format widened and added ----
+def assert_exact_window(patterns, kind, nbytes):
+    """The precondition of an exact sum, in integers and fractions, for all the rows of a call: every value is finite and a multiple of
+    2^q, and n max|x| < 2^(q + 53).  Then every sum of any of the values, in any order, is a multiple of 2^q below 2^(q + 53) - a binary64 -
+    so the kernel's tree, the host's fold and math.fsum agree bit for bit.  Returns q"""
+    x = comparable(patterns, kind, nbytes).astype(np.float64)
+    assert np.all(np.isfinite(x)), "a window holds finite values"
+    values = [Fraction(v) for v in x.tolist() if v]
+    assert values, "a window of zeros"
+    # the 2-adic valuation of a dyadic rational num / 2^k: the trailing zeros of num, less k
+    q = min((f.numerator & -f.numerator).bit_length() - f.denominator.bit_length() for f in values)
+    unit = Fraction(2) ** q
+    assert all((f / unit).denominator == 1 for f in values)
+    assert int(x.size) * max(abs(f) for f in values) < unit * 2 ** 53, ("the window's sums may round", int(x.size), q)
+    return q
+
+
+def windows_f16():
+    """all 63 488 finite binary16 patterns in a seeded permutation, as 8 windows of 7 936 rows (q = -24, max 65 504: n < 2^13 suffices)"""
+    p = np.arange(1 << 16, dtype=np.uint64)
+    p = np.random.default_rng(51).permutation(p[(p & 0x7c00) != 0x7c00])
+    assert p.size == 63488
+    return [p[7936 * w:7936 * (w + 1)] for w in range(8)]
+
+
+def windows_bf16():
+    """all finite bfloat16 patterns in 8 windows by exponent field, e // 32 = 0 ... 7 without e = 255: 8 192 rows each, 7 936 in the last"""
+    p = np.arange(1 << 16, dtype=np.uint64)
+    e = (p >> np.uint64(7)) & np.uint64(0xff)
+    rng = np.random.default_rng(52)
+    out = [rng.permutation(p[(e // np.uint64(32) == w) & (e != 255)]) for w in range(8)]
+    assert [w.size for w in out] == [8192] * 7 + [7936]
+    return out
+
+
+def window_f32(w, nrows=8000):
+    """window w = 0 ... 14 of binary32: the 17 exponent fields 17 w ... 17 w + 16, both signs.  n 2^(e_min + 17) < 2^(e_min - 23 + 53) gives
+    n < 2^13.  For every exponent field and sign the mantissas 0, all ones and every single bit; the rest random.  In window 0 half of the
+    rows have exponent field 0: for every leading-bit position p of a subnormal 1 << p, (1 << (p + 1)) - 1 and a random pattern with that
+    leading bit, then random ones with a random leading bit"""
+    rng = np.random.default_rng(530 + w)
+    e_min = 17 * w
+    mants = [0, (1 << 23) - 1] + [1 << k for k in range(23)]
+    rows = [(s << 31) | (e << 23) | m for e in range(e_min, e_min + 17) for s in (0, 1) for m in mants]
+    if w == 0:
+        def below(p):      # a random pattern whose leading bit is bit p
+            return (1 << p) | int(rng.integers(0, 1 << p))
+        rows += [(s << 31) | m for p in range(23) for s in (0, 1) for m in (1 << p, (1 << (p + 1)) - 1, below(p))]
+        have = sum(1 for r in rows if not (r >> 23) & 0xff)
+        rows += [(int(rng.integers(0, 2)) << 31) | below(int(rng.integers(0, 23))) for _ in range(nrows // 2 - have)]
+    n = nrows - len(rows)
+    e = rng.integers(max(e_min, 1) if w == 0 else e_min, e_min + 17, n).astype(np.uint64)
+    rows = np.concatenate([np.array(rows, dtype=np.uint64), (rng.integers(0, 2, n).astype(np.uint64) << np.uint64(31)) | (e << np.uint64(23))
+                           | rng.integers(0, 1 << 23, n).astype(np.uint64)])
+    assert rows.size == nrows and (w != 0 or int(((rows >> np.uint64(23)) & np.uint64(0xff) == 0).sum()) == nrows // 2)
+    return rng.permutation(rows)
+
+
+def window_f64(nrows=8000):
+    """binary64 subnormals below 2^39 units, both signs: widening is the identity, the window is about the device's additions of subnormals"""
+    rng = np.random.default_rng(54)
+    return rng.integers(1, 1 << 39, nrows).astype(np.uint64) | (rng.integers(0, 2, nrows).astype(np.uint64) << np.uint64(63))
+
+
+F32_WINDOWS = 15
+WINDOWS = {(FLOAT, 2): lambda: windows_f16(), (BFLOAT16, 2): lambda: windows_bf16(), (FLOAT, 4): lambda: [window_f32(w) for w in range(F32_WINDOWS)],
+           (FLOAT, 8): lambda: [window_f64()]}
+THREE_WAYS = (None, GT, LT)      # unfiltered, the positive values alone, the negative values alone: no two wrong values cancel in all three
+
+
+def case_sum_window(env, kind, nbytes, patterns, ways=THREE_WAYS, turn=0, what=""):
+    """one window through sum_call: the precondition asserted for the whole call before it is made, then every chunk's sum and the call's
+    compared with == against math.fsum - unfiltered, under GT +0 and under LT +0"""
+    assert_exact_window(patterns, kind, nbytes)
+    chunks, rows_plain = sum_call(env, patterns, nbytes, turn)
+    assert np.array_equal(field_of(rows_plain, 12, 3, UINT, nbytes).astype(np.uint64), patterns)
+    src = TakeSource(env.mem, chunks=chunks)
+    for op in ways:
+        flt = None if op is None else (3, kind, nbytes, op, 0)
+        total, _ = check_aggregate(env, src, chunks, rows_plain, 12, (3, kind, nbytes), flt, exact=True, what=("window", what))
+        assert total[2] == 0 and total[1] > 0 and (op is None) == (total[1] == patterns.size)
 
 
 def rounding_values(nbytes, nrows):

@@ -79,6 +79,35 @@ def test_float_sum_exact_and_subnormals(env, kind, nbytes):
     A.case_sum_subnormals(env, kind, nbytes, 2500, turn=at + 1)
 
 
+@pytest.mark.parametrize("kind,nbytes", A.FLOATS[:2], ids=[A.kind_name(*k) for k in A.FLOATS[:2]])
+def test_exact_sum_windows_of_every_16_bit_value(env, kind, nbytes):
+    """every finite binary16 / bfloat16 pattern widened and added, unfiltered (the device runs each window under GT +0 and LT +0 as well)"""
+    for w, patterns in enumerate(A.WINDOWS[(kind, nbytes)]()):
+        A.case_sum_window(env, kind, nbytes, patterns, ways=(None,), turn=w, what=w)
+
+
+@pytest.mark.parametrize("w", [0, 9])
+def test_exact_sum_windows_of_binary32(env, w):
+    """the window that holds the subnormals, every leading bit among them, and one of normals - of the device's 15"""
+    A.case_sum_window(env, A.FLOAT, 4, A.window_f32(w), turn=w, what=w)
+
+
+def test_exact_sum_window_of_binary64_subnormals(env):
+    A.case_sum_window(env, A.FLOAT, 8, A.window_f64(), ways=(None,), what="binary64")
+
+
+@pytest.mark.parametrize("kind,nbytes", A.KINDS16, ids=[A.kind_name(*k) for k in A.KINDS16])
+def test_every_16_bit_pattern_below_and_above_each_constant(env, kind, nbytes):
+    """rows of 2 bytes, the four constants of the kind that sit on a change of regime (the device: both layouts, every constant)"""
+    A.case_patterns16(env, kind, A.LAYOUTS16[0], A.thin_constants16(kind), turn=A.KINDS16.index((kind, nbytes)))
+
+
+@pytest.mark.parametrize("kind,nbytes", A.NEIGHBOUR_KINDS, ids=[A.kind_name(*k) for k in A.NEIGHBOUR_KINDS])
+def test_neighbours_of_the_wide_kinds(env, kind, nbytes):
+    at = A.NEIGHBOUR_KINDS.index((kind, nbytes))
+    A.case_neighbours(env, kind, nbytes, SETTINGS[at % 3], turn=at, thin=True)
+
+
 @pytest.mark.parametrize("nbytes", [4, 8])
 def test_float_sum_rounding_and_bit_identity(env, nbytes):
     A.case_sum_rounding(env, nbytes, 4000, turn=nbytes)

@@ -52,6 +52,19 @@ def test_every_kind_width_and_op(env, kind, nbytes):
     W.case_kind(env, kind, nbytes, SETTINGS[at % 3], W.thin_picks, turn=at)
 
 
+@pytest.mark.parametrize("kind,nbytes", W.KINDS16, ids=[W.kind_name(*k) for k in W.KINDS16])
+def test_every_16_bit_pattern_against_each_constant(env, kind, nbytes):
+    """rows of 2 bytes, EQ / LT / GE against the four constants of the kind that sit on a change of regime (the device: both layouts, every
+    constant, every op)"""
+    W.case_patterns16(env, kind, W.LAYOUTS16[0], W.thin_constants16(kind), ops=(0, 2, 5), packed_ops=(), turn=W.KINDS16.index((kind, nbytes)))
+
+
+@pytest.mark.parametrize("kind,nbytes", W.NEIGHBOUR_KINDS, ids=[W.kind_name(*k) for k in W.NEIGHBOUR_KINDS])
+def test_neighbours_of_the_wide_kinds(env, kind, nbytes):
+    at = W.NEIGHBOUR_KINDS.index((kind, nbytes))
+    W.case_neighbours(env, kind, nbytes, SETTINGS[at % 3], W.thin_neighbour_picks(kind, nbytes), turn=at)
+
+
 @pytest.mark.parametrize("layout", W.LAYOUTS, ids=[f"{l[0]}-at-{l[1]}" for l in W.LAYOUTS])
 def test_row_layouts_and_both_entry_points(env, layout):
     at = W.LAYOUTS.index(layout)

@@ -80,6 +80,28 @@ def test_float_sum_exact_and_subnormals(env, kind, nbytes):
     A.case_sum_subnormals(env, kind, nbytes, 30000, turn=at + 1)
 
 
+@pytest.mark.parametrize("kind,nbytes", A.FLOATS, ids=[A.kind_name(*k) for k in A.FLOATS])
+def test_exact_sum_windows(env, kind, nbytes):
+    """every finite binary16 and bfloat16 pattern, binary32 over all its exponent fields with every leading bit of a subnormal, binary64
+    subnormals: windows whose sums are exact in any order, each unfiltered, under GT +0 and under LT +0, equal to math.fsum"""
+    for w, patterns in enumerate(A.WINDOWS[(kind, nbytes)]()):
+        A.case_sum_window(env, kind, nbytes, patterns, turn=w, what=w)
+
+
+@pytest.mark.parametrize("row_layout", A.LAYOUTS16, ids=[f"{l[0]}-at-{l[1]}" for l in A.LAYOUTS16])
+@pytest.mark.parametrize("kind,nbytes", A.KINDS16, ids=[A.kind_name(*k) for k in A.KINDS16])
+def test_every_16_bit_pattern_below_and_above_each_constant(env, kind, nbytes, row_layout):
+    """the 65 536 patterns as rows: max under LT c and min under GT c are c's neighbours, across both zeros and every change of regime"""
+    A.case_patterns16(env, kind, row_layout, A.constants16(kind), turn=A.KINDS16.index((kind, nbytes)))
+
+
+@pytest.mark.parametrize("kind,nbytes", A.NEIGHBOUR_KINDS, ids=[A.kind_name(*k) for k in A.NEIGHBOUR_KINDS])
+def test_neighbours_of_the_wide_kinds(env, kind, nbytes):
+    """the neighbours of 2^31, 2^32 and 2^63, the regime changes of binary32 and binary64, halves of 8-byte values: under LT c and GT c"""
+    at = A.NEIGHBOUR_KINDS.index((kind, nbytes))
+    A.case_neighbours(env, kind, nbytes, SETTINGS[at % len(SETTINGS)], turn=at)
+
+
 @pytest.mark.parametrize("nbytes", [4, 8])
 def test_float_sum_rounding_and_bit_identity(env, nbytes):
     import torch
@@ -167,6 +189,7 @@ def test_aggregate_rows_of_every_dtype(lib, tensors, dtype):
     if dt.is_floating_point:
         table = table * 0.5
         table[::37, 4] = float("nan"); table[5::41, 4] = float("inf"); table[3::43, 4] = -0.0
+        table[::29, 1] = 0.1; table[1::31, 1] = 0.125; table[2::31, 1] = 0.0625      # column 1: the dtype's 0.1 between its neighbours
     cont, off, meta = tensors.pack_rows(lib, table, rows_per_chunk=1000, cname=b"lz4", shuffle=1)
     col = table[:, 4]
     everything = torch.ones(5000, dtype=torch.bool, device=dev)
@@ -174,6 +197,12 @@ def test_aggregate_rows_of_every_dtype(lib, tensors, dtype):
     runs = [(None, everything), (("lt", one, 4), col < one), (("ge", one, 2), table[:, 2] >= one), (("ne", one, 4), col != one)]
     if dt.is_floating_point:
         runs += [(("lt", float("inf"), 4), col < float("inf")), (("eq", float("nan"), 4), ~everything), (("ne", float("nan"), 4), everything)]
+        # 0.1 is no value of the dtype: rounded to it, as torch rounds the scalar of its comparison
+        runs += [(("eq", 0.1, 1), table[:, 1] == 0.1), (("gt", 0.1, 1), table[:, 1] > 0.1)]
+        assert 0 < int((table[:, 1] == 0.1).sum()) < 5000
+    else:      # 1.5 is no value of an integer column: refused, not answered for the constant 1
+        with pytest.raises(ValueError, match="1.5"):
+            tensors.aggregate_rows(lib, cont, off, meta, column=4, where=("lt", 1.5, 4))
     for where, mask in runs:
         got = tensors.aggregate_rows(lib, cont, off, meta, column=4, where=where)
         same(got, torch_answer(torch, col, mask))

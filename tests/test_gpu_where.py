@@ -53,6 +53,22 @@ def test_every_kind_width_and_op(env, kind, nbytes):
     W.case_kind(env, kind, nbytes, SETTINGS[at % len(SETTINGS)], W.all_picks, turn=at)
 
 
+@pytest.mark.parametrize("row_layout", W.LAYOUTS16, ids=[f"{l[0]}-at-{l[1]}" for l in W.LAYOUTS16])
+@pytest.mark.parametrize("kind,nbytes", W.KINDS16, ids=[W.kind_name(*k) for k in W.KINDS16])
+def test_every_16_bit_pattern_against_each_constant(env, kind, nbytes, row_layout):
+    """the 65 536 patterns as rows, every op against the byte carries and the sign change (integers), against both zeros and every change of
+    regime up to the first NaN (binary16, bfloat16); three of the ops through the packed entry point as well"""
+    W.case_patterns16(env, kind, row_layout, W.constants16(kind), turn=W.KINDS16.index((kind, nbytes)))
+
+
+@pytest.mark.parametrize("kind,nbytes", W.NEIGHBOUR_KINDS, ids=[W.kind_name(*k) for k in W.NEIGHBOUR_KINDS])
+def test_neighbours_of_the_wide_kinds(env, kind, nbytes):
+    """every op against every constant of the kind's neighbour set: around 2^31, 2^32 and 2^63, the regime changes of binary32 and binary64,
+    8-byte values that differ in one half only"""
+    at = W.NEIGHBOUR_KINDS.index((kind, nbytes))
+    W.case_neighbours(env, kind, nbytes, SETTINGS[(at + 1) % len(SETTINGS)], turn=at)
+
+
 @pytest.mark.parametrize("layout", W.LAYOUTS, ids=[f"{l[0]}-at-{l[1]}" for l in W.LAYOUTS])
 def test_row_layouts_and_both_entry_points(env, layout):
     """every op on every row layout under two settings, one of them a Zstd or zlib one; one layout on a caller's side stream"""
@@ -139,12 +155,20 @@ def test_where_rows_of_every_dtype(lib, tensors, dtype):
     if dt.is_floating_point:
         table = table * 0.5
         table[::37, 4] = float("nan"); table[5::41, 4] = float("inf"); table[3::43, 4] = -0.0
+        table[::29, 1] = 0.1; table[1::31, 1] = 0.125; table[2::31, 1] = 0.0625      # column 1: the dtype's 0.1 between its neighbours
     cont, off, meta = tensors.pack_rows(lib, table, rows_per_chunk=1000, cname=b"lz4", shuffle=1)
     for name, fn in (("eq", operator.eq), ("ne", operator.ne), ("lt", operator.lt), ("le", operator.le), ("gt", operator.gt), ("ge", operator.ge)):
         for value in ((True,) if dt == torch.bool else (1, 0) + ((float("nan"), -0.5) if dt.is_floating_point else ())):
             index, total = tensors.where_rows(lib, cont, off, meta, name if value != 0 else fn, value, column=4)
             want = torch.nonzero(fn(table[:, 4], value)).flatten()
             assert index.dtype == torch.int64 and index.is_cuda and total == want.numel() and torch.equal(index, want), (dtype, name, value)
+        if dt.is_floating_point:      # 0.1 is no value of the dtype: rounded to it, as torch rounds the scalar of its comparison
+            index, total = tensors.where_rows(lib, cont, off, meta, name, 0.1, column=1)
+            want = torch.nonzero(fn(table[:, 1], 0.1)).flatten()
+            assert 0 < want.numel() < 5000 and total == want.numel() and torch.equal(index, want), (dtype, name, 0.1)
+        else:                         # 1.5 is no value of an integer column: refused, not answered for the constant 1
+            with pytest.raises(ValueError, match="1.5"):
+                tensors.where_rows(lib, cont, off, meta, name, 1.5, column=4)
     want = torch.nonzero(table[:, 4] >= 1).flatten()
     index, total = tensors.where_rows(lib, cont, off, meta, "ge", 1, column=4, max_matches=want.numel() // 2)
     assert total == want.numel() > 2 and torch.equal(index, want[:want.numel() // 2])

@@ -5,7 +5,9 @@ the oracle's orc_decompress, the expected table is numpy.nonzero of the numpy co
 TorchMem: how a test reaches "device" memory.
 
 The tables are made here: bytes every codec compresses, the field of every row overwritten with a pattern from a small value set, so that
-every constant of the set has matches and the densities are known."""
+every constant of the set has matches and the densities are known.  Two kinds of table go through whole value spaces instead: table16 holds
+every 16-bit pattern once, asked about the constants at which a format changes regime (constants16), and the 4- and 8-byte kinds are drawn
+from neighbour_set - the patterns around 2^31, 2^32 and 2^63, the regime changes of binary32 and binary64, halves of 8-byte values."""
 import ctypes as C
 import operator
 
@@ -45,6 +47,65 @@ def value_set(kind, nbytes):
                        (FLOAT, 8): (0x7ff0 << 48, 0x7ff8 << 48, 0x3ff8 << 48)}[(kind, nbytes)]
     sign = 1 << (bits - 1)
     return [quiet, sign | exp | 1, 0, sign, exp, sign | exp, 1, sig, sign | sig]
+
+
+MANTISSA = {(FLOAT, 2): 10, (BFLOAT16, 2): 7, (FLOAT, 4): 23, (FLOAT, 8): 52}      # the mantissa bits of the floating-point formats
+
+
+def regime(kind, nbytes):
+    """the magnitudes at which a floating-point format changes regime, by name: zero, the smallest and the largest subnormal, the smallest
+    normal, 1.0, the largest finite value, infinity, the first pattern above it (a NaN) and a quiet NaN"""
+    mant, bits = MANTISSA[(kind, nbytes)], 8 * nbytes
+    inf = ((1 << (bits - 1 - mant)) - 1) << mant
+    return {"zero": 0, "min_sub": 1, "max_sub": (1 << mant) - 1, "min_normal": 1 << mant, "one": ((1 << (bits - 2 - mant)) - 1) << mant,
+            "max_finite": inf - 1, "inf": inf, "first_nan": inf + 1, "quiet_nan": inf | (1 << (mant - 1))}
+
+
+def regime_set(kind, nbytes):
+    """every magnitude of regime() with both signs, and one quiet NaN: 17 patterns"""
+    r, sign = regime(kind, nbytes), 1 << (8 * nbytes - 1)
+    mags = [r[k] for k in ("zero", "min_sub", "max_sub", "min_normal", "one", "max_finite", "inf", "first_nan")]
+    return [s | m for m in mags for s in (0, sign)] + [r["quiet_nan"]]
+
+
+CARRIES16 = [0, 1, 0x00ff, 0x0100, 0x7fff, 0x8000, 0x8001, 0xfffe, 0xffff]      # the byte carry of a two-byte load, and the sign change
+KINDS16 = [(UINT, 2), (INT, 2), (FLOAT, 2), (BFLOAT16, 2)]
+NEIGHBOUR_KINDS = [(UINT, 4), (UINT, 8), (INT, 4), (INT, 8), (FLOAT, 4), (FLOAT, 8)]
+# binary64: two patterns that differ only in the low word - in the order a signed low word would reverse - and two that differ only in the high word
+LOW_PAIR = [(0x400921fb << 32) | 0x00000001, (0x400921fb << 32) | 0xfffffffe]
+HIGH_PAIR = [(0x3ff00000 << 32) | 0x80000000, (0x3ff00001 << 32) | 0x80000000]
+
+
+def constants16(kind):
+    """the constants the table of every 16-bit pattern is asked about"""
+    return CARRIES16 if kind in (UINT, INT) else regime_set(kind, 2)
+
+
+def thin_constants16(kind):
+    """the emulator's four, each on a regime change"""
+    if kind in (UINT, INT): return [0x00ff, 0x0100, 0x7fff, 0x8000]
+    r = regime(kind, 2)
+    return [r["max_sub"], 0x8000 | r["min_normal"], r["inf"], 0x8000 | r["first_nan"]]
+
+
+def neighbour_set(kind, nbytes):
+    """the patterns of the 4- and 8-byte kinds next to which an order can go wrong.  Integers: 0, 1 and the neighbours of 2^31, 2^32 and 2^63 -
+    where a sign bit, a half of a composed load or the key's bit 63 changes; floating point: regime_set, and for binary64 LOW_PAIR and HIGH_PAIR"""
+    if kind in (UINT, INT):
+        small = [0, 1, 2 ** 31 - 1, 2 ** 31, 2 ** 31 + 1, 2 ** 32 - 1]
+        return small if nbytes == 4 else small + [2 ** 32, 2 ** 32 + 1, 2 ** 63 - 1, 2 ** 63, 2 ** 63 + 1, 2 ** 64 - 1]
+    return regime_set(kind, nbytes) + (LOW_PAIR + HIGH_PAIR if nbytes == 8 else [])
+
+
+def thin_neighbour_picks(kind, nbytes):
+    """the emulator's (op, constant) pairs on a neighbour set, as many as thin_picks has: the integers across 2^31 (and 2^32, 2^63), the
+    floating-point formats across subnormal / normal and finite / infinity / NaN (binary64: inside the two pairs)"""
+    if kind in (UINT, INT):
+        return [(2, 2 ** 31), (5, 2 ** 32 - 1)] + ([(4, 2 ** 63 - 1), (3, 2 ** 32)] if nbytes == 8 else [])
+    r, sign = regime(kind, nbytes), 1 << (8 * nbytes - 1)
+    if nbytes == 8:
+        return [(2, LOW_PAIR[1]), (4, HIGH_PAIR[0]), (5, sign | r["max_sub"]), (3, r["max_finite"])]
+    return [(2, r["min_normal"]), (5, sign | r["max_sub"]), (4, r["max_finite"]), (1, r["first_nan"])]
 
 
 def comparable(patterns, kind, nbytes):
@@ -266,6 +327,51 @@ def case_kind(env, kind, nbytes, setting, picks, turn=0):
         want = check_where(env.lib, env.mem, src, chunks, rows_plain, 17, (3, kind, nbytes, op, constant), env.pkg, what=setting)
         if kind in (FLOAT, BFLOAT16) and constant in values[:2]:      # a NaN constant: nothing, or with NE every row
             assert want.size == (rows_plain.size // 17 if op == 1 else 0)
+
+
+def case_neighbours(env, kind, nbytes, setting, picks=None, turn=0):
+    """case 1 on the kind's neighbour set: the table drawn from it, every op against every constant of it (picks: the (op, constant) pairs
+    of a thinner run)"""
+    values = neighbour_set(kind, nbytes)
+    chunks, rows_plain = table_call(env, setting, (17, 3, kind, nbytes), drawn(values, total_rows(17, setting[3]), seed=6), turn)
+    src = TakeSource(env.mem, chunks=chunks)
+    for op, constant in (all_picks(values) if picks is None else picks):
+        assert constant in values
+        check_where(env.lib, env.mem, src, chunks, rows_plain, 17, (3, kind, nbytes, op, constant), env.pkg, what=("neighbours", setting))
+
+
+ROWS16 = [30001, 20003, 15532]      # the 65 536 rows of table16 in three chunks, none a multiple of a tile's 1 024 rows
+LAYOUTS16 = [(2, 0), (5, 3)]        # (row_bytes, offset): the field is the row; the field at an odd address in every row
+
+
+def table16(env, row_layout, turn=0):
+    """(chunks, their plaintext) of a table whose two-byte field takes each of the 65 536 patterns exactly once, in a seeded permutation"""
+    row_bytes, offset = row_layout
+    patterns = np.random.default_rng(16).permutation(1 << 16).astype(np.uint64)
+    write = env.writer("lz4" if row_bytes == 2 else "blosclz", row_bytes, 1, turn)
+    assert sum(ROWS16) == 1 << 16 and all(r % 1024 for r in ROWS16)
+    chunks = [write(k, make_table(rows, row_bytes, offset, 2, patterns[sum(ROWS16[:k]):sum(ROWS16[:k + 1])], seed=90 + k)) for k, rows in enumerate(ROWS16)]
+    rows_plain = plaintext(env.oracle, chunks)
+    assert np.array_equal(np.sort(field_of(rows_plain, row_bytes, offset, UINT, 2)), np.arange(1 << 16)), "not every pattern once"
+    return chunks, rows_plain
+
+
+def case_patterns16(env, kind, row_layout, constants, ops=range(6), packed_ops=(0, 2, 4), turn=0):
+    """every 16-bit pattern as a row against each constant: the ops through blosc_gpu_where_batch, packed_ops through _packed as well"""
+    row_bytes, offset = row_layout
+    chunks, rows_plain = table16(env, row_layout, turn)
+    batch, packed = both_sources(env, chunks)
+    for constant in constants:
+        for op in ops:
+            args = (offset, kind, 2, op, constant)
+            a = check_where(env.lib, env.mem, batch, chunks, rows_plain, row_bytes, args, env.pkg, what="every pattern, batch")
+            if op == 0:      # EQ: the pattern itself - both zeros of a floating-point format, no row for a NaN
+                is_float = kind in (FLOAT, BFLOAT16)
+                mag = constant & 0x7fff
+                assert a.size == (1 if not is_float else 0 if mag > regime(kind, 2)["inf"] else 2 if mag == 0 else 1), (kind_name(kind, 2), hex(constant), a.size)
+            if op in packed_ops:
+                b = check_where(env.lib, env.mem, packed, chunks, rows_plain, row_bytes, args, env.pkg, what="every pattern, packed")
+                assert np.array_equal(a, b)
 
 
 def all_picks(values):

@@ -638,6 +638,16 @@ struct EncodeBatch {
   explicit EncodeBatch(int n) : chunks((size_t)n), live((size_t)n, 0), variant((size_t)n, (uint8_t)kEncModes) {}
 };
 
+// The parameter checks of a chunk of nbytes into destsize, in the compress call's order (blosc.c:1062-1145, :1197-1207; Snappy: not built).
+// false: it cannot be written, *result is what the compress call answers for it: 0 (too large, or no room for a header), -10, -5.
+static bool check_cparams(const CompressParams& p, size_t nbytes, size_t destsize, int* result) {
+  *result = 0;
+  if (nbytes > (size_t)kMaxBufferSize || destsize < (size_t)kMaxOverhead) return false;
+  if (p.clevel < 0 || p.clevel > 9 || (p.doshuffle != 0 && p.doshuffle != 1 && p.doshuffle != 2) || p.typesize == 0) *result = -10;
+  else if (p.codec != kBloscLZ && p.codec != kLZ4 && p.codec != kLZ4HC && p.codec != kZlib && p.codec != kZstd) *result = -5;
+  return *result == 0;
+}
+
 // Parameter checks and geometry of chunk i of n (blosc.c:1062-1145, :1148-1247).  false: nothing runs for it, *result is its outcome.
 static bool add_encode_chunk(const CompressParams& p, const Job& job, int i, int n, bool may_fuse, EncodeBatch& B, int* result) {
   ChunkDesc& c = B.chunks[(size_t)i];
@@ -646,12 +656,9 @@ static bool add_encode_chunk(const CompressParams& p, const Job& job, int i, int
   c.mode = CH_SKIP;
   size_t nbytes = job.srcsize, destsize = job.dstsize, typesize = p.typesize;
   const int codec = p.codec;
-  *result = 0;
-  if (nbytes > (size_t)kMaxBufferSize || destsize < (size_t)kMaxOverhead) return false;
+  if (!check_cparams(p, nbytes, destsize, result)) return false;
   if (destsize - kMaxOverhead > nbytes) destsize = nbytes + kMaxOverhead;
-  if (p.clevel < 0 || p.clevel > 9 || (p.doshuffle != 0 && p.doshuffle != 1 && p.doshuffle != 2) || typesize == 0) { *result = -10; return false; }
   if (typesize > (size_t)kMaxTypeSize) typesize = 1;
-  if (codec != kBloscLZ && codec != kLZ4 && codec != kLZ4HC && codec != kZlib && codec != kZstd) { *result = -5; return false; }  // blosc.c:1197-1207 (Snappy: not built)
   const int32_t T = (int32_t)typesize, nb = (int32_t)nbytes;
   const int32_t bs = compute_blocksize(p.clevel, T, nb, p.forced_blocksize, codec, p.splitmode);
   const int32_t leftover = nb % bs, nblocks = nb / bs + (leftover > 0 ? 1 : 0);
@@ -1465,6 +1472,27 @@ static size_t merge_runs(std::vector<BlockRun>& runs, size_t bs) {      // retur
   return bytes;
 }
 
+// Chunks dealt to passes in their order, for getitem and every row call: a pass holds at most `bound` of their bytes, a single chunk beyond
+// the bound is a pass of its own.  Returns the pass of each chunk.  A chunk without bytes stays in the pass of the chunk before it;
+// empty_opens (getitem_ranges alone): behind a chunk beyond the bound it opens the next pass, as a chunk with bytes does.
+static std::vector<int> deal_to_passes(const std::vector<size_t>& bytes, size_t bound, bool empty_opens = false) {
+  std::vector<int> pass_of(bytes.size(), 0);
+  size_t in_pass = 0; int pass = 0;
+  for (size_t k = 0; k < bytes.size(); k++) {
+    if (in_pass && (bytes[k] || empty_opens) && in_pass + bytes[k] > bound) { pass++; in_pass = 0; }
+    pass_of[k] = pass; in_pass += bytes[k];
+  }
+  return pass_of;
+}
+// ... for the two calls that decode block runs (getitem_ranges, engine_take): the runs merged, their slots' bytes dealt.  Returns the passes.
+static int deal_runs_to_passes(std::vector<RangeChunk>& uc, const std::vector<Header>& hdrs, bool empty_opens) {
+  std::vector<size_t> bytes(uc.size());
+  for (size_t k = 0; k < uc.size(); k++) bytes[k] = merge_runs(uc[k].runs, (size_t)(hdrs[k].blocksize > 0 ? hdrs[k].blocksize : 1));
+  const std::vector<int> pass_of = deal_to_passes(bytes, g_getitem_pass_bytes.load(), empty_opens);
+  for (size_t k = 0; k < uc.size(); k++) uc[k].pass = pass_of[k];
+  return uc.empty() ? 1 : pass_of.back() + 1;
+}
+
 // "Decode the runs of one pass", shared by getitem_pass and take_pass (which differ in their gather tables and gather kernel alone):
 // lay_out_runs, then decode_runs up to launch_decode, then - behind the caller's read_back_decode and gather launch - finish_pass.
 struct PassRuns {
@@ -1684,14 +1712,8 @@ static int getitem_ranges(EngineState& st, int nchunks, const Job* chunks, const
   }
   if (packed) { packed->offsets[nranges] = off; if (!packed->base) return 0; }
   // ---- runs per chunk, chunks dealt to passes ----
-  const size_t bound = g_getitem_pass_bytes.load();
-  size_t in_pass = 0; int pass = 0;
-  for (size_t k = 0; k < uc.size(); k++) {
-    const size_t bytes = merge_runs(uc[k].runs, (size_t)(hdrs[k].blocksize > 0 ? hdrs[k].blocksize : 1));
-    if (in_pass && in_pass + bytes > bound) { pass++; in_pass = 0; }
-    uc[k].pass = pass; in_pass += bytes;
-  }
-  for (int p = 0; p <= pass; p++)
+  const int npass = deal_runs_to_passes(uc, hdrs, /*empty_opens*/ true);
+  for (int p = 0; p < npass; p++)
     if (getitem_pass(st, p, uc, hdrs, jobs, nranges, pr, results, stream)) return -1;
   return 0;
 }
@@ -1706,27 +1728,13 @@ int engine_getitem_batch(int nchunks, const Job* chunks, int nranges, const Item
 }
 
 // ---------------------------------------------------------------------------------------------
-// take (include/blosc_gpu_take.h): rows of the chunks by an index table that lies on the device
+// the row calls - take, put, where, aggregate: their shared front end
 // ---------------------------------------------------------------------------------------------
-// The getitem pipeline with another front end and another gather.  The indices are never brought to the host:
-//   1. one header fetch for all chunks, the census on the host (classify_for_getitem's checks, the packed form's slot checks, nbytes a
-//      multiple of row_bytes) and the chunk table (dev_types.h: TakeChunk) - a call with an unusable chunk ends here;
-//   2. k_take_mark sets a byte per block some row lies in; the flags come down, one synchronisation;
-//   3. the maximal intervals of touched blocks are the chunks' runs - merge_runs, the dealing to passes and decode_runs as in getitem_ranges;
-//   4. per pass k_take_gather over ALL indices, with a table over the blocks of the call (dev_types.h: TakeBlock) that says where a block lies
-//      in this pass's slots; rows of other passes' chunks are skipped, indices outside the rows are answered by the first pass;
-//   5. the rows that failed are counted in one more status word behind the blocks', which comes down with them: one synchronisation per pass.
-// Synchronisations: 2 + the passes, whatever nidx.
-namespace {
-struct TakeCall {
-  std::vector<TakeChunk> chunks;      // [nchunks + 1]
-  uint32_t row_bytes; int lanes_log2;
-  size_t nidx; const int64_t* index; uint8_t* dest; int32_t* status;
-  size_t failed = 0;
-};
-}  // namespace
+// Every row call begins with one header fetch (first synchronisation) and rows_census on the host; a call with an unusable chunk ends there.
+// Behind it: mark_touched and row_lanes_log2 (take, put), overlaps_a_source (put, where), deal_to_passes (above: getitem's too), and RowScan,
+// the whole-chunk pipeline of put, where and aggregate.  The indices and the rows never come to the host.
 
-// The census of the row calls (take, and put below), before anything is decoded: which chunks are usable - classify_for_getitem's checks, the
+// The census, before anything is decoded: which chunks are usable - classify_for_getitem's checks, the
 // packed form's slot checks, nbytes a multiple of row_bytes -, and the rows and table entries in front of each (table: [n + 1]).
 // chunk_rows_out[k] (may be nullptr): the chunk's rows or its negative code.  whole_chunks (put): every chunk is ONE block of nbytes, so
 // k_take_mark's flags are per chunk - a MEMCPYED chunk too, which take gives blocksize 0 because it decodes nothing of it.
@@ -1766,6 +1774,182 @@ static unsigned take_grid(const EngineState& st, size_t nidx, int lanes_log2) {
   const size_t per_group = (size_t)(TK_THREADS >> lanes_log2);
   return persistent_grid(st, (nidx + per_group - 1) / per_group, TK_WAVES_PER_CU / (TK_THREADS / 64));
 }
+
+// The blocks (take) or chunks (put: one block per chunk) some valid index names: k_take_mark over the census' table, in st.dev / st.pin.
+// *flags: nflags bytes in st.pin, read behind the one synchronisation - theirs until the next decode or encode call of the context carves st.pin.
+static int mark_touched(EngineState& st, const std::vector<TakeChunk>& table, size_t nflags, const int64_t* index, size_t nidx, size_t row_bytes,
+                        hipStream_t stream, const uint8_t** flags) {
+  const size_t table_bytes = sizeof(TakeChunk) * table.size();
+  Carver cv;
+  const size_t o_chunks = cv.take(table_bytes), o_touched = cv.take(nflags);
+  if (st.dev.ensure(cv.off) || st.pin.ensure(cv.off)) return -1;
+  uint8_t *D = st.dev.base, *P = st.pin.base;
+  memcpy(P + o_chunks, table.data(), table_bytes);
+  HIP_TRY(hipMemcpyAsync(D + o_chunks, P + o_chunks, table_bytes, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemsetAsync(D + o_touched, 0, nflags, stream));
+  {
+    ProfScope ps(st, stream, "k_take_mark");
+    hipLaunchKernelGGL(k_take_mark, dim3(take_grid(st, nidx, 0)), dim3(TK_THREADS), 0, stream, (const TakeChunk*)(D + o_chunks), (int)table.size() - 1, index,
+                       nidx, (uint32_t)row_bytes, D + o_touched);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipMemcpyAsync(P + o_touched, D + o_touched, nflags, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  prof_collect(st);
+  *flags = P + o_touched;
+  return 0;
+}
+
+// Lanes per row, as a power of two: one up to 16 bytes; above, one per 16-byte piece (at most the wave), and at least 16 where rows have head
+// and tail bytes - misaligned: row_bytes, or an address the rows are laid out from, is no multiple of 16.
+static int row_lanes_log2(size_t row_bytes, bool misaligned) {
+  int lanes_log2 = 0;
+  if (row_bytes > 16) {
+    while (((size_t)16 << lanes_log2) < row_bytes && lanes_log2 < 6) lanes_log2++;
+    if (misaligned && lanes_log2 < 4) lanes_log2 = 4;
+  }
+  return lanes_log2;
+}
+
+// An output [lo, hi) of the call that lies over a chunk it reads
+static bool overlaps_a_source(const std::vector<Job>& jobs, const std::vector<Header>& hdrs, uintptr_t lo, uintptr_t hi) {
+  for (size_t k = 0; k < jobs.size(); k++) {
+    const uintptr_t s0 = (uintptr_t)jobs[k].src, s1 = s0 + (jobs[k].srcsize ? jobs[k].srcsize : (size_t)hdrs[k].cbytes);
+    if (s0 < hi && lo < s1) return true;
+  }
+  return false;
+}
+
+// RowScan.  census() fetches the headers and counts the rows; the caller then says which chunks are live - decoded, because they hold rows
+// (where, aggregate) or an index names them (put); deal() deals the live chunks' plaintext to passes and sizes the workspace; decode_pass()
+// decodes the next pass (the decompress call's two synchronisations, headers and verdicts - the verdicts are on the host, so what the caller
+// launches behind it needs no status words of the device).  A chunk that does not decode (blosc.c:1511-1514) keeps its slot and has code[k] < 0.
+// Memory.  st.io holds a table of entry_bytes per chunk for the caller (WhereChunk, PutChunk), a prefix of n + npass tile counts (pass p over
+// chunks [c0, c1): entries [c0 + p, c1 + p]), back_bytes at o_back for whatever else the call uploads or brings down, and the workspace of
+// the largest pass: the slots, and extra_of[k] more per live chunk, free from `at` on.  st.put_pin holds the host images of all but the
+// workspace, at the same offsets.  The decode and encode calls inside carve st.dev / st.pin anew and leave these two alone.
+struct RowScan {
+  size_t n = 0, npass = 0, unread = 0;          // unread: the rows of the chunks that did not decode
+  std::vector<Header> hdrs; std::vector<Job> jobs; std::vector<TakeChunk> table;
+  std::vector<int> rows_of, pass_of, code;      // rows_of: the chunk's rows or its negative code; code, negative: what the decoder answered
+  std::vector<uint8_t> live;                    // [n], the caller's, between census() and deal()
+  std::vector<uint8_t*> slot_of;                // the plaintext of a live chunk once its pass is decoded
+  std::vector<uint32_t> tiles_of;
+  size_t o_chunks = 0, o_tiles = 0, o_back = 0, o_ws = 0;
+  uint8_t *D = nullptr, *P = nullptr;
+  // the pass decode_pass() has just decoded: chunks [c0, c1), the workspace free from `at` on
+  size_t pass = 0, c0 = 0, c1 = 0, at = 0;
+  uint32_t ntiles = 0;
+  std::vector<Job> djobs; std::vector<int> dres;
+
+  // one header fetch and the census; *usable false: rows_of holds every chunk's rows or its negative code, and the call is to answer -1
+  int census(EngineState& st, int nchunks, const Job* chunks, size_t row_bytes, hipStream_t stream, bool* usable) {
+    n = (size_t)(nchunks > 0 ? nchunks : 0);
+    if (n && fetch_headers(st, (int)n, chunks, true, stream, hdrs)) return -1;
+    jobs.assign(chunks, chunks + n);
+    std::vector<RangeChunk> uc(n);
+    rows_of.assign(n ? n : 1, 0);
+    *usable = rows_census(jobs, hdrs, row_bytes, /*whole_chunks*/ true, uc, table, rows_of.data());
+    return 0;
+  }
+  void rows_to(int* chunk_rows_out) const {
+    if (chunk_rows_out) std::copy(rows_of.begin(), rows_of.begin() + (ptrdiff_t)n, chunk_rows_out);
+  }
+  // live chunks dealt to passes in chunk order; the workspace of the largest pass
+  int deal(EngineState& st, const std::vector<size_t>& extra_of, size_t bound, size_t entry_bytes, size_t back_bytes) {
+    std::vector<size_t> bytes(n, 0);
+    for (size_t k = 0; k < n; k++) if (live[k]) bytes[k] = align_up((size_t)hdrs[k].nbytes, 256);
+    pass_of = deal_to_passes(bytes, bound);
+    npass = n ? (size_t)pass_of[n - 1] + 1 : 1;
+    std::vector<size_t> ws_of(npass, 0);
+    for (size_t k = 0; k < n; k++) if (live[k]) ws_of[(size_t)pass_of[k]] += bytes[k] + extra_of[k];
+    code.assign(n, 0); slot_of.assign(n, nullptr);
+    Carver cv;
+    o_chunks = cv.take(entry_bytes * (n ? n : 1));
+    o_tiles = cv.take(sizeof(uint32_t) * (n + npass));
+    o_back = cv.take(back_bytes);
+    const size_t table_bytes = cv.take(0);
+    o_ws = cv.take(*std::max_element(ws_of.begin(), ws_of.end()) + 4 * 256);
+    if (st.io.ensure(cv.off) || st.put_pin.ensure(table_bytes)) return -1;
+    D = st.io.base; P = st.put_pin.base;
+    return 0;
+  }
+  // Pass p = 0, 1, ... npass - 1, in this order.  *any_live false: the pass has no live chunk, nothing was launched
+  int decode_pass(EngineState& st, size_t p, hipStream_t stream, bool* any_live) {
+    pass = p;
+    c0 = p ? c1 : 0; c1 = c0;
+    while (c1 < n && pass_of[c1] == (int)pass) c1++;
+    at = o_ws;
+    djobs.clear();
+    for (size_t k = c0; k < c1; k++) {
+      if (!live[k]) continue;
+      slot_of[k] = D + at;
+      djobs.push_back(Job{jobs[k].src, D + at, jobs[k].srcsize, (size_t)hdrs[k].nbytes});
+      at += align_up((size_t)hdrs[k].nbytes, 256);
+    }
+    *any_live = !djobs.empty();
+    if (djobs.empty()) return 0;
+    dres.assign(djobs.size(), -1);
+    if (decompress_batch_in(st, (int)djobs.size(), djobs.data(), dres.data(), true, stream, nullptr)) return -1;
+    for (size_t k = c0, i = 0; k < c1; k++) {
+      if (!live[k]) continue;
+      const int r = dres[i++];
+      if (r != hdrs[k].nbytes) { code[k] = r < 0 ? r : -1; unread += (size_t)rows_of[k]; }
+    }
+    return 0;
+  }
+
+  // ---- where and aggregate: the chunks that hold rows are live, tile_bytes of workspace per tile of WH_TILE rows, the tables k_where.hip reads ----
+  // The bound is at most 1 GiB, so that the counts of a pass stay in 32 bits.
+  int deal_tiles(EngineState& st, size_t tile_bytes, size_t back_bytes) {
+    std::vector<size_t> extra_of(n);
+    live.assign(n, 0); tiles_of.assign(n, 0);
+    for (size_t k = 0; k < n; k++) {
+      live[k] = rows_of[k] != 0;
+      tiles_of[k] = (uint32_t)(((size_t)rows_of[k] + WH_TILE - 1) / WH_TILE);
+      extra_of[k] = tile_bytes * tiles_of[k];
+    }
+    return deal(st, extra_of, std::min(g_getitem_pass_bytes.load(), (size_t)1 << 30), sizeof(WhereChunk), back_bytes);
+  }
+  const WhereChunk* d_chunks() const { return (const WhereChunk*)(D + o_chunks) + c0; }
+  const uint32_t* d_tiles() const { return (const uint32_t*)(D + o_tiles) + c0 + pass; }
+  // decode_pass(), then the pass's WhereChunk table - a chunk that did not decode has a negative status, its tiles count nothing - and tile
+  // prefix go up.  What the caller launches behind it finds its ntiles tiles' words from D + at on.
+  int decode_tiles(EngineState& st, size_t p, hipStream_t stream, bool* holds_rows) {
+    if (decode_pass(st, p, stream, holds_rows)) return -1;
+    if (!*holds_rows) return 0;
+    WhereChunk* h_chunks = (WhereChunk*)(P + o_chunks);
+    uint32_t* tiles = (uint32_t*)(P + o_tiles) + c0 + pass;
+    tiles[0] = 0;
+    for (size_t k = c0; k < c1; k++) {
+      h_chunks[k] = WhereChunk{slot_of[k], table[k].row_first, (uint32_t)rows_of[k], live[k] && code[k] >= 0 ? 0 : -1};
+      tiles[k - c0 + 1] = tiles[k - c0] + tiles_of[k];
+    }
+    ntiles = tiles[c1 - c0];
+    HIP_TRY(hipMemcpyAsync(D + o_chunks + sizeof(WhereChunk) * c0, h_chunks + c0, sizeof(WhereChunk) * (c1 - c0), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(D + o_tiles + sizeof(uint32_t) * (c0 + pass), tiles, sizeof(uint32_t) * (c1 - c0 + 1), hipMemcpyHostToDevice, stream));
+    return 0;
+  }
+};
+
+// ---------------------------------------------------------------------------------------------
+// take (include/blosc_gpu_take.h): rows of the chunks by an index table that lies on the device
+// ---------------------------------------------------------------------------------------------
+// The shared front end (census over the chunks' blocks, mark_touched, row_lanes_log2) in front of getitem's block-run pipeline:
+//   1. the maximal intervals of touched blocks are the chunks' runs - merged and dealt to passes as getitem_ranges does, but a chunk that
+//      decodes nothing never opens a pass: a pass is a gather over all indices;
+//   2. per pass decode_runs, then k_take_gather over ALL indices, with a table over the blocks of the call (dev_types.h: TakeBlock) that says
+//      where a block lies in this pass's slots; rows of other passes' chunks are skipped, indices outside the rows are answered by the first pass;
+//   3. the rows that failed are counted in one more status word behind the blocks', which comes down with them: one synchronisation per pass.
+// Synchronisations: 2 + the passes, whatever nidx.
+namespace {
+struct TakeCall {
+  std::vector<TakeChunk> chunks;      // [nchunks + 1]
+  uint32_t row_bytes; int lanes_log2;
+  size_t nidx; const int64_t* index; uint8_t* dest; int32_t* status;
+  size_t failed = 0;
+};
+}  // namespace
 
 static int take_pass(EngineState& st, int pass, std::vector<RangeChunk>& uc, const std::vector<Header>& hdrs, const std::vector<Job>& jobs,
                      TakeCall& tc, hipStream_t stream) {
@@ -1817,36 +2001,15 @@ int engine_take(int nchunks, const Job* chunks, size_t row_bytes, size_t nidx, c
   if (failed_out) *failed_out = 0;
   if (!nidx) return 0;
   tc.row_bytes = (uint32_t)row_bytes; tc.nidx = nidx; tc.index = index; tc.dest = (uint8_t*)dest; tc.status = status;
-  // lanes per row: one up to 16 bytes; above, one per 16-byte piece (a power of two, at most the wave), and at least 16 where rows have
-  // head and tail bytes - where dest or row_bytes is no multiple of 16
-  tc.lanes_log2 = 0;
-  if (row_bytes > 16) {
-    while (((size_t)16 << tc.lanes_log2) < row_bytes && tc.lanes_log2 < 6) tc.lanes_log2++;
-    if ((((uintptr_t)dest | row_bytes) & 15) && tc.lanes_log2 < 4) tc.lanes_log2 = 4;
-  }
+  tc.lanes_log2 = row_lanes_log2(row_bytes, (((uintptr_t)dest | row_bytes) & 15) != 0);      // dest: the rows lie back to back from it
   // ---- the blocks the rows touch ----
   if (blocks) {
-    Carver cv;
-    const size_t o_chunks = cv.take(sizeof(TakeChunk) * (n + 1));
-    const size_t o_touched = cv.take((size_t)blocks);
-    if (st.dev.ensure(cv.off) || st.pin.ensure(cv.off)) return -1;
-    uint8_t *D = st.dev.base, *P = st.pin.base;
-    memcpy(P + o_chunks, tc.chunks.data(), sizeof(TakeChunk) * (n + 1));
-    HIP_TRY(hipMemcpyAsync(D + o_chunks, P + o_chunks, sizeof(TakeChunk) * (n + 1), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemsetAsync(D + o_touched, 0, (size_t)blocks, stream));
-    {
-      ProfScope ps(st, stream, "k_take_mark");
-      hipLaunchKernelGGL(k_take_mark, dim3(take_grid(st, nidx, 0)), dim3(TK_THREADS), 0, stream, (const TakeChunk*)(D + o_chunks), (int)n, index, nidx,
-                         tc.row_bytes, D + o_touched);
-      HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipMemcpyAsync(P + o_touched, D + o_touched, (size_t)blocks, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    prof_collect(st);
+    const uint8_t* touched;
+    if (mark_touched(st, tc.chunks, (size_t)blocks, index, nidx, row_bytes, stream, &touched)) return -1;
     // ---- runs: the maximal intervals of touched blocks of every chunk (a row's blocks are all marked, so they lie in one run) ----
     for (size_t k = 0; k < n; k++) {
       if (uc[k].memcpyed || !tc.chunks[k].blocksize) continue;
-      const uint8_t* t = P + o_touched + tc.chunks[k].block_first;
+      const uint8_t* t = touched + tc.chunks[k].block_first;
       const int32_t nblk = tc.chunks[k + 1].block_first - tc.chunks[k].block_first;
       for (int32_t j = 0; j < nblk; j++) {
         if (!t[j]) continue;
@@ -1857,15 +2020,8 @@ int engine_take(int nchunks, const Job* chunks, size_t row_bytes, size_t nidx, c
       }
     }
   }
-  // ---- chunks dealt to passes, as getitem_ranges deals them (a chunk that decodes nothing never opens a pass: a pass is a gather over all indices) ----
-  const size_t bound = g_getitem_pass_bytes.load();
-  size_t in_pass = 0; int pass = 0;
-  for (size_t k = 0; k < n; k++) {
-    const size_t bytes = merge_runs(uc[k].runs, (size_t)(hdrs[k].blocksize > 0 ? hdrs[k].blocksize : 1));
-    if (in_pass && bytes && in_pass + bytes > bound) { pass++; in_pass = 0; }
-    uc[k].pass = pass; in_pass += bytes;
-  }
-  for (int p = 0; p <= pass; p++)
+  const int npass = deal_runs_to_passes(uc, hdrs, /*empty_opens*/ false);
+  for (int p = 0; p < npass; p++)
     if (take_pass(st, p, uc, hdrs, jobs, tc, stream)) return -1;
   if (failed_out) *failed_out = tc.failed;
   return 0;
@@ -1874,106 +2030,60 @@ int engine_take(int nchunks, const Job* chunks, size_t row_bytes, size_t nidx, c
 // ---------------------------------------------------------------------------------------------
 // put (include/blosc_gpu_put.h): rows written into the chunks by an index table that lies on the device; the result is a new container
 // ---------------------------------------------------------------------------------------------
-// Take's front end around the two whole-chunk pipelines the engine has, in ONE context (decompress_batch_in, compress_entries_in):
-//   1. one header fetch, rows_census with every chunk as one block, every chunk's parameters, dest against the sources;
-//   2. k_take_mark, UNCHANGED, over that table: a flag per chunk some valid index names.  The flags come down, second synchronisation;
-//   3. the chunks are dealt to passes in chunk order, under engine_take's bound counted over the plaintext of the touched chunks - so a pass
-//      is a range [c0, c1) of chunks, and every chunk's place in dest is known once the sizes of its pass are;
-//   4. per pass with a touched chunk: the touched chunks decode into plaintext slots (the decompress call's two synchronisations, headers
-//      and verdicts - the verdicts are on the host, so the scatter needs no status words of the device and no synchronisation of its own),
-//      k_put_claim and k_put_scatter over all indices, the chunks that decoded are compressed into slots of nbytes + 16 (the compress call's
-//      synchronisation); per pass, touched chunk or not: the host sets the offsets, k_put_assemble writes the pass's piece of dest;
-//   5. the count of failed rows comes down, last synchronisation; the caller's host tables are written.
+// RowScan with the chunks an index names as the live ones, and the engine's whole-chunk encoder behind it, in ONE context:
+//   1. the census, then every chunk's parameters (check_cparams) and dest against the sources; mark_touched over one block per chunk, before
+//      anything else has carved st.dev / st.pin: second synchronisation;
+//   2. the touched chunks dealt under engine_take's bound, unclipped - a pass is a range [c0, c1) of chunks, and every chunk's place in dest
+//      is known once the sizes of its pass are.  A live chunk's extra workspace: one owner word per row and nbytes + 16 for the encoder's output;
+//   3. per pass with a touched chunk: decode_pass, k_put_claim and k_put_scatter over all indices, the chunks that decoded are compressed
+//      (compress_entries_in's synchronisation), the others carried over as they are; per pass, touched chunk or not: the host sets the
+//      offsets, k_put_assemble writes the pass's piece of dest (RowScan's tile prefix counts the PA_TILE pieces of the copies here);
+//   4. the count of failed rows comes down, last synchronisation; the caller's host tables are written.
 // Synchronisations: 3 + 3 per pass that has a touched chunk, whatever nidx.
-// Memory.  The slots, the owner words and the put tables live in st.io, which a device-pointer call leaves alone - the decode and the encode
-// carve st.dev anew and may move it -, sized once for the largest pass: its plaintext (up to the bound, or one chunk), one owner word per
-// row of it, and nbytes + 16 per chunk for the encoder's output.  The tables' host images live in st.put_pin for the same reason.
 int engine_put(int nchunks, const Job* chunks, size_t row_bytes, size_t nidx, const int64_t* index, const void* rows, const CompressParams* params,
                const PackedBuffer* out, int* cbytes_out, int* rewritten_out, int* status, int* chunk_rows_out, size_t* failed_out, hipStream_t stream) {
   CtxGuard ctx; EngineState& st = *ctx.st;
   if (ensure_device(st)) return -1;
-  const size_t n = (size_t)(nchunks > 0 ? nchunks : 0);
-  std::vector<Header> hdrs;
-  if (n && fetch_headers(st, (int)n, chunks, true, stream, hdrs)) return -1;
-  // ---- the census: take's, then every chunk's parameters (add_encode_chunk's checks in its order), then dest against every source ----
-  std::vector<Job> jobs(chunks, chunks + n);
-  std::vector<RangeChunk> uc(n);
-  std::vector<TakeChunk> table;
-  bool usable = rows_census(jobs, hdrs, row_bytes, /*whole_chunks*/ true, uc, table, chunk_rows_out);
+  // ---- the census; then every chunk's parameters, its cbytes as the room: -1 for no chunk the compress call would write, or none to copy ----
+  RowScan rs;
+  bool usable = false;
+  if (rs.census(st, nchunks, chunks, row_bytes, stream, &usable)) return -1;
+  const size_t n = rs.n;
+  const std::vector<Header>& hdrs = rs.hdrs;
   for (size_t k = 0; k < n; k++) {
-    if (!uc[k].usable) continue;
-    const CompressParams& p = params[k];
-    int code = 0;
-    if (hdrs[k].nbytes > kMaxBufferSize || hdrs[k].cbytes < kMaxOverhead) code = -1;      // (no chunk the compress call would write; no chunk to copy)
-    else if (p.clevel < 0 || p.clevel > 9 || (p.doshuffle != 0 && p.doshuffle != 1 && p.doshuffle != 2) || p.typesize == 0) code = -10;
-    else if (p.codec != kBloscLZ && p.codec != kLZ4 && p.codec != kLZ4HC && p.codec != kZlib && p.codec != kZstd) code = -5;
-    if (!code) continue;
-    if (chunk_rows_out) chunk_rows_out[k] = code;
+    if (rs.rows_of[k] < 0) continue;      // unusable
+    int code;
+    if (check_cparams(params[k], (size_t)hdrs[k].nbytes, (size_t)std::max(hdrs[k].cbytes, 0), &code)) continue;
+    rs.rows_of[k] = code ? code : -1;
     usable = false;
   }
+  rs.rows_to(chunk_rows_out);
   if (!usable) return -1;
-  const uintptr_t d0 = (uintptr_t)out->base, d1 = d0 + out->size;
-  for (size_t k = 0; k < n && out->base && out->size; k++) {
-    const uintptr_t s0 = (uintptr_t)jobs[k].src, s1 = s0 + (jobs[k].srcsize ? jobs[k].srcsize : (size_t)hdrs[k].cbytes);
-    if (s0 < d1 && d0 < s1) return -1;
-  }
+  if (out->base && out->size && overlaps_a_source(rs.jobs, hdrs, (uintptr_t)out->base, (uintptr_t)out->base + out->size)) return -1;
   // ---- the chunks some valid index names: k_take_mark over one block per chunk ----
-  std::vector<uint8_t> touched(n, 0);
-  if (nidx && n) {
-    Carver cv;
-    const size_t o_chunks = cv.take(sizeof(TakeChunk) * (n + 1));
-    const size_t o_touched = cv.take(n);
-    if (st.dev.ensure(cv.off) || st.pin.ensure(cv.off)) return -1;
-    uint8_t *D = st.dev.base, *P = st.pin.base;
-    memcpy(P + o_chunks, table.data(), sizeof(TakeChunk) * (n + 1));
-    HIP_TRY(hipMemcpyAsync(D + o_chunks, P + o_chunks, sizeof(TakeChunk) * (n + 1), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemsetAsync(D + o_touched, 0, n, stream));
-    {
-      ProfScope ps(st, stream, "k_take_mark");
-      hipLaunchKernelGGL(k_take_mark, dim3(take_grid(st, nidx, 0)), dim3(TK_THREADS), 0, stream, (const TakeChunk*)(D + o_chunks), (int)n, index, nidx,
-                         (uint32_t)row_bytes, D + o_touched);
-      HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipMemcpyAsync(P + o_touched, D + o_touched, n, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    prof_collect(st);
-    memcpy(touched.data(), P + o_touched, n);
-  }
-  // ---- chunks dealt to passes in chunk order; the workspace of the largest pass ----
-  const size_t bound = g_getitem_pass_bytes.load();
-  std::vector<int> pass_of(n, 0);
-  std::vector<size_t> ws_of(1, 0);      // per pass: plaintext slots + owner words + encoder slots
+  rs.live.assign(n, 0);
   bool any_touched = false;
-  {
-    size_t in_pass = 0; int pass = 0;
-    for (size_t k = 0; k < n; k++) {
-      const size_t nb = (size_t)hdrs[k].nbytes, bytes = touched[k] ? align_up(nb, 256) : 0;
-      if (in_pass && bytes && in_pass + bytes > bound) { pass++; in_pass = 0; ws_of.push_back(0); }
-      pass_of[k] = pass; in_pass += bytes;
-      if (touched[k]) { any_touched = true; ws_of[(size_t)pass] += bytes + align_up(sizeof(uint32_t) * (nb / row_bytes), 256) + align_up(nb + kMaxOverhead, 256); }
-    }
+  if (nidx && n) {
+    const uint8_t* touched;
+    if (mark_touched(st, rs.table, n, index, nidx, row_bytes, stream, &touched)) return -1;
+    rs.live.assign(touched, touched + n);
+    any_touched = std::count(touched, touched + n, 0) != (ptrdiff_t)n;
   }
-  const size_t npass = ws_of.size();
-  Carver cv;
-  const size_t o_table = cv.take(sizeof(TakeChunk) * (n + 1));
-  const size_t o_put = cv.take(sizeof(PutChunk) * (n ? n : 1));
-  const size_t o_copy = cv.take(sizeof(PutCopy) * (n ? n : 1));
-  const size_t o_tiles = cv.take(sizeof(uint32_t) * (n + npass));      // pass p over chunks [c0, c1): entries [c0 + p, c1 + p]
-  const size_t o_failed = cv.take(sizeof(uint32_t));
-  const size_t table_bytes = cv.take(0);
-  const size_t o_ws = cv.take(*std::max_element(ws_of.begin(), ws_of.end()) + 256);
-  if (st.io.ensure(cv.off) || st.put_pin.ensure(table_bytes)) return -1;
-  uint8_t *D = st.io.base, *P = st.put_pin.base;
-  memcpy(P + o_table, table.data(), sizeof(TakeChunk) * (n + 1));
+  // ---- the passes; behind RowScan's tables the call's TakeChunk table, the chunks' PutCopy and the count of failed rows ----
+  std::vector<size_t> extra_of(n);
+  for (size_t k = 0; k < n; k++) {
+    const size_t nb = (size_t)hdrs[k].nbytes;
+    extra_of[k] = align_up(sizeof(uint32_t) * (nb / row_bytes), 256) + align_up(nb + kMaxOverhead, 256);
+  }
+  Carver back;
+  const size_t b_table = back.take(sizeof(TakeChunk) * (n + 1)), b_copy = back.take(sizeof(PutCopy) * (n ? n : 1)), b_failed = back.take(sizeof(uint32_t));
+  if (rs.deal(st, extra_of, g_getitem_pass_bytes.load(), sizeof(PutChunk), back.off)) return -1;
+  const size_t o_put = rs.o_chunks, o_tiles = rs.o_tiles, o_table = rs.o_back + b_table, o_copy = rs.o_back + b_copy, o_failed = rs.o_back + b_failed;
+  uint8_t *D = rs.D, *P = rs.P;
+  memcpy(P + o_table, rs.table.data(), sizeof(TakeChunk) * (n + 1));
   HIP_TRY(hipMemcpyAsync(D + o_table, P + o_table, sizeof(TakeChunk) * (n + 1), hipMemcpyHostToDevice, stream));
   HIP_TRY(hipMemsetAsync(D + o_failed, 0, sizeof(uint32_t), stream));
-  // lanes per index: one up to 16 bytes; above, one per 16-byte piece (a power of two, at most the wave), and at least 16 where rows have
-  // head and tail bytes - where row_bytes is no multiple of 16 (the slots are aligned)
-  int lanes_log2 = 0;
-  if (row_bytes > 16) {
-    while (((size_t)16 << lanes_log2) < row_bytes && lanes_log2 < 6) lanes_log2++;
-    if ((row_bytes & 15) && lanes_log2 < 4) lanes_log2 = 4;
-  }
+  const int lanes_log2 = row_lanes_log2(row_bytes, (row_bytes & 15) != 0);      // (the slots are aligned)
   const TakeChunk* d_table = (const TakeChunk*)(D + o_table);
   uint32_t* d_failed = (uint32_t*)(D + o_failed);
   PutChunk* h_put = (PutChunk*)(P + o_put); PutCopy* h_copy = (PutCopy*)(P + o_copy); uint32_t* h_tiles = (uint32_t*)(P + o_tiles);
@@ -1984,36 +2094,28 @@ int engine_put(int nchunks, const Job* chunks, size_t row_bytes, size_t nidx, co
   };
   std::vector<size_t> offsets(n + 1, 0);
   std::vector<int> cbytes(n, 0), rewritten(n, 0);
-  std::vector<Job> djobs, cjobs; std::vector<int> dres, cres; std::vector<CompressParams> cpar; std::vector<size_t> live;
+  std::vector<Job> cjobs; std::vector<int> cres; std::vector<CompressParams> cpar;
   bool answered = false;      // the indices outside the rows have their -1
-  for (size_t p = 0, c0 = 0; p < npass; p++) {
-    size_t c1 = c0;
-    while (c1 < n && pass_of[c1] == (int)p) c1++;
+  for (size_t p = 0; p < rs.npass; p++) {
     // ---- the touched chunks of the pass: decode, claim, scatter, encode ----
-    size_t at = o_ws, nrows = 0;
-    djobs.clear(); live.clear();
-    for (size_t k = c0; k < c1; k++) {
-      h_put[k] = PutChunk{nullptr, 0, 0, 0};
-      if (!touched[k]) continue;
-      h_put[k].slot = D + at; h_put[k].owner_first = nrows;
-      djobs.push_back(Job{jobs[k].src, D + at, jobs[k].srcsize, (size_t)hdrs[k].nbytes});
-      live.push_back(k);
-      at += align_up((size_t)hdrs[k].nbytes, 256); nrows += (size_t)hdrs[k].nbytes / row_bytes;
-    }
-    if (!live.empty()) {
-      dres.assign(live.size(), -1);
-      if (decompress_batch_in(st, (int)live.size(), djobs.data(), dres.data(), true, stream, nullptr)) return -1;
-      uint32_t* owner = (uint32_t*)(D + at);
-      at += align_up(sizeof(uint32_t) * nrows, 256);
+    bool touched = false;
+    if (rs.decode_pass(st, p, stream, &touched)) return -1;
+    const size_t c0 = rs.c0, c1 = rs.c1;
+    if (touched) {
+      size_t at = rs.at, nrows = 0;      // behind the slots: the encoder's slots, then the owner words
       cjobs.clear(); cpar.clear();
-      for (size_t i = 0; i < live.size(); i++) {
-        const size_t k = live[i], nb = (size_t)hdrs[k].nbytes;
-        if (dres[i] != hdrs[k].nbytes) { h_put[k].status = -1; rewritten[k] = -1; continue; }      // blosc.c:1511-1514: carried over as it is
-        rewritten[k] = 1;
-        cjobs.push_back(Job{h_put[k].slot, D + at, nb, nb + kMaxOverhead});
+      for (size_t k = c0; k < c1; k++) {      // an untouched chunk: no slot, all zero
+        h_put[k] = PutChunk{rs.slot_of[k], rs.live[k] ? nrows : 0, rs.code[k] < 0 ? -1 : 0, 0};
+        if (!rs.live[k]) continue;
+        const size_t nb = (size_t)hdrs[k].nbytes;
+        nrows += nb / row_bytes;
+        rewritten[k] = rs.code[k] < 0 ? -1 : 1;      // -1: carried over as it is
+        if (rewritten[k] != 1) continue;
+        cjobs.push_back(Job{rs.slot_of[k], D + at, nb, nb + kMaxOverhead});
         cpar.push_back(params[k]);
         at += align_up(nb + kMaxOverhead, 256);
       }
+      uint32_t* owner = (uint32_t*)(D + at);
       HIP_TRY(hipMemcpyAsync(D + o_put + sizeof(PutChunk) * c0, h_put + c0, sizeof(PutChunk) * (c1 - c0), hipMemcpyHostToDevice, stream));
       HIP_TRY(hipMemsetAsync(owner, 0xff, sizeof(uint32_t) * nrows, stream));
       {
@@ -2026,8 +2128,7 @@ int engine_put(int nchunks, const Job* chunks, size_t row_bytes, size_t nidx, co
       HIP_TRY(hipGetLastError());
       cres.assign(cjobs.size(), 0);
       if (compress_entries_in(st, cpar.data(), true, (int)cjobs.size(), cjobs.data(), cres.data(), true, stream, nullptr, nullptr)) return -1;
-      for (size_t i = 0, j = 0; i < live.size(); i++) {
-        const size_t k = live[i];
+      for (size_t k = c0, j = 0; k < c1; k++) {
         if (rewritten[k] != 1) continue;
         if (cres[j] <= 0) return -1;      // (with destsize nbytes + 16 and checked parameters the call has no such answer)
         cbytes[k] = cres[j]; h_copy[k].src = (const uint8_t*)cjobs[j].dst; j++;
@@ -2041,7 +2142,7 @@ int engine_put(int nchunks, const Job* chunks, size_t row_bytes, size_t nidx, co
     uint32_t* tiles = h_tiles + c0 + p;
     tiles[0] = 0;
     for (size_t k = c0; k < c1; k++) {
-      if (rewritten[k] != 1) { cbytes[k] = hdrs[k].cbytes; h_copy[k].src = (const uint8_t*)jobs[k].src; }
+      if (rewritten[k] != 1) { cbytes[k] = hdrs[k].cbytes; h_copy[k].src = (const uint8_t*)rs.jobs[k].src; }
       const size_t end = offsets[k] + (size_t)cbytes[k];
       offsets[k + 1] = align_up(end, out->align);
       h_copy[k].dst = (uint8_t*)out->base + offsets[k]; h_copy[k].nbytes = 0; h_copy[k].pad = 0;
@@ -2058,7 +2159,6 @@ int engine_put(int nchunks, const Job* chunks, size_t row_bytes, size_t nidx, co
                          (const uint32_t*)(D + o_tiles) + c0 + p, (int)(c1 - c0));
       HIP_TRY(hipGetLastError());
     }
-    c0 = c1;
   }
   // ---- collect ----
   uint32_t* h_failed = (uint32_t*)(P + o_failed);
@@ -2074,131 +2174,28 @@ int engine_put(int nchunks, const Job* chunks, size_t row_bytes, size_t nidx, co
 // ---------------------------------------------------------------------------------------------
 // where (include/blosc_gpu_where.h): the rows whose field satisfies a predicate, as the index table take and put read
 // ---------------------------------------------------------------------------------------------
-// Put's front end and its whole-chunk decode, in ONE context, around the three kernels of k_where.hip:
-//   1. one header fetch, rows_census with every chunk as one block, index_out against every source;
-//   2. the chunks that hold rows are dealt to passes in chunk order under engine_take's bound (at most 1 GiB, so that the counts of a pass stay
-//      in 32 bits; a single chunk beyond the bound is a pass of its own), and the workspace is sized once for the largest pass;
-//   3. per pass: the chunks decode into plaintext slots (the decompress call's two synchronisations, headers and verdicts - the verdicts are on
-//      the host, so a chunk that did not decode enters the table with a negative status and its tiles count nothing), then k_where_mark,
-//      and - where the caller gave a table - k_where_scan and k_where_write.  The running total stays on the device: no pass waits for a count;
-//   4. the chunks' counters come down, last synchronisation; the caller's host tables are written.
+// RowScan with the chunks that hold rows as the live ones (deal_tiles, decode_tiles), in ONE context, around the three kernels of k_where.hip:
+//   1. the census, index_out against every source;
+//   2. per pass that holds a row: decode_tiles, then k_where_mark, and - where the caller gave a table - k_where_scan and k_where_write.  The
+//      running total stays on the device: no pass waits for a count;
+//   3. the chunks' counters come down, last synchronisation; the caller's host tables are written.
 // Synchronisations: 2 + 2 per pass that holds a row, whatever the rows and the matches.
-// Memory.  As in engine_put the workspace lives in st.io and the tables' host images in st.put_pin, which the decode calls inside leave alone:
-// the plaintext of the largest pass, and per tile of WH_TILE rows of it WH_WORDS mask words, a count and a base (140 bytes per 1024 rows).
-//
-// RowScan is that front half, which engine_aggregate shares (steps 1, 2 and the decode of step 3): census() fetches the headers and counts the
-// rows, deal() deals the chunks to passes and sizes the workspace - the plaintext of the largest pass, tile_bytes per tile of it, back_bytes
-// at D + o_back and their host image at P + o_back for what the call brings down at its end - and decode_pass() decodes the next pass into
-// its slots and uploads its chunk table and tile prefix.  What the caller launches behind it finds its tiles' words from D + at on.
-struct RowScan {
-  size_t n = 0, npass = 0, unread = 0;
-  std::vector<Header> hdrs;
-  std::vector<Job> jobs;
-  std::vector<TakeChunk> table;
-  std::vector<int> rows_of, pass_of, code;      // code, negative: what the decoder answered for the chunk
-  std::vector<uint32_t> tiles_of;
-  std::vector<size_t> ws_of;                    // per pass: plaintext slots + the tiles' words
-  size_t o_chunks = 0, o_tiles = 0, o_back = 0, o_ws = 0;
-  uint8_t *D = nullptr, *P = nullptr;
-  // the pass decode_pass() has just decoded: chunks [c0, c1), ntiles tiles, the workspace free from `at` on
-  size_t pass = 0, c0 = 0, c1 = 0, at = 0;
-  uint32_t ntiles = 0;
-  std::vector<Job> djobs; std::vector<int> dres; std::vector<size_t> live;
-
-  // one header fetch and take's census; *usable false: rows_of holds every chunk's rows or its negative code, and the call is to answer -1
-  int census(EngineState& st, int nchunks, const Job* chunks, size_t row_bytes, hipStream_t stream, bool* usable) {
-    n = (size_t)(nchunks > 0 ? nchunks : 0);
-    if (n && fetch_headers(st, (int)n, chunks, true, stream, hdrs)) return -1;
-    jobs.assign(chunks, chunks + n);
-    std::vector<RangeChunk> uc(n);
-    rows_of.assign(n ? n : 1, 0);
-    *usable = rows_census(jobs, hdrs, row_bytes, /*whole_chunks*/ true, uc, table, rows_of.data());
-    return 0;
-  }
-  void rows_to(int* chunk_rows_out) const {
-    if (chunk_rows_out) std::copy(rows_of.begin(), rows_of.begin() + (ptrdiff_t)n, chunk_rows_out);
-  }
-  // chunks dealt to passes in chunk order; the workspace of the largest pass
-  int deal(EngineState& st, size_t tile_bytes, size_t back_bytes) {
-    const size_t bound = std::min(g_getitem_pass_bytes.load(), (size_t)1 << 30);
-    pass_of.assign(n, 0); tiles_of.assign(n, 0); ws_of.assign(1, 0); code.assign(n, 0);
-    size_t in_pass = 0; int pass_at = 0;
-    for (size_t k = 0; k < n; k++) {
-      const size_t bytes = rows_of[k] ? align_up((size_t)hdrs[k].nbytes, 256) : 0;
-      if (in_pass && bytes && in_pass + bytes > bound) { pass_at++; in_pass = 0; ws_of.push_back(0); }
-      pass_of[k] = pass_at; in_pass += bytes;
-      tiles_of[k] = (uint32_t)(((size_t)rows_of[k] + WH_TILE - 1) / WH_TILE);
-      ws_of[(size_t)pass_at] += bytes + tile_bytes * tiles_of[k];
-    }
-    npass = ws_of.size();
-    Carver cv;
-    o_chunks = cv.take(sizeof(WhereChunk) * (n ? n : 1));
-    o_tiles = cv.take(sizeof(uint32_t) * (n + npass));      // pass p over chunks [c0, c1): entries [c0 + p, c1 + p]
-    o_back = cv.take(back_bytes);
-    const size_t table_bytes = cv.take(0);
-    o_ws = cv.take(*std::max_element(ws_of.begin(), ws_of.end()) + 4 * 256);
-    if (st.io.ensure(cv.off) || st.put_pin.ensure(table_bytes)) return -1;
-    D = st.io.base; P = st.put_pin.base;
-    return 0;
-  }
-  const WhereChunk* d_chunks() const { return (const WhereChunk*)(D + o_chunks) + c0; }
-  const uint32_t* d_tiles() const { return (const uint32_t*)(D + o_tiles) + c0 + pass; }
-  // Pass p = 0, 1, ... npass - 1, in this order: its chunks decode into their slots, the verdicts enter the chunk table, table and tile prefix go up.
-  // *holds_rows false: no chunk of the pass holds a row, nothing was launched and nothing is to be
-  int decode_pass(EngineState& st, size_t p, hipStream_t stream, bool* holds_rows) {
-    pass = p;
-    c0 = p ? c1 : 0; c1 = c0;
-    while (c1 < n && pass_of[c1] == (int)pass) c1++;
-    WhereChunk* h_chunks = (WhereChunk*)(P + o_chunks);
-    uint32_t* tiles = (uint32_t*)(P + o_tiles) + c0 + pass;
-    at = o_ws;
-    tiles[0] = 0;
-    djobs.clear(); live.clear();
-    for (size_t k = c0; k < c1; k++) {
-      h_chunks[k] = WhereChunk{nullptr, table[k].row_first, (uint32_t)rows_of[k], -1};
-      tiles[k - c0 + 1] = tiles[k - c0] + tiles_of[k];
-      if (!rows_of[k]) continue;
-      h_chunks[k].slot = D + at;
-      djobs.push_back(Job{jobs[k].src, D + at, jobs[k].srcsize, (size_t)hdrs[k].nbytes});
-      live.push_back(k);
-      at += align_up((size_t)hdrs[k].nbytes, 256);
-    }
-    ntiles = tiles[c1 - c0];
-    *holds_rows = !live.empty();
-    if (live.empty()) return 0;
-    dres.assign(live.size(), -1);
-    if (decompress_batch_in(st, (int)live.size(), djobs.data(), dres.data(), true, stream, nullptr)) return -1;
-    for (size_t i = 0; i < live.size(); i++) {
-      const size_t k = live[i];
-      if (dres[i] == hdrs[k].nbytes) { h_chunks[k].status = 0; continue; }
-      code[k] = dres[i] < 0 ? dres[i] : -1;      // blosc.c:1511-1514: the chunk holds no row anybody can read
-      unread += (size_t)rows_of[k];
-    }
-    HIP_TRY(hipMemcpyAsync(D + o_chunks + sizeof(WhereChunk) * c0, h_chunks + c0, sizeof(WhereChunk) * (c1 - c0), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(D + o_tiles + sizeof(uint32_t) * (c0 + pass), tiles, sizeof(uint32_t) * (c1 - c0 + 1), hipMemcpyHostToDevice, stream));
-    return 0;
-  }
-};
-
+// Workspace per tile of WH_TILE rows: WH_WORDS mask words, a count and a base (140 bytes per 1024 rows).
 int engine_where(int nchunks, const Job* chunks, size_t row_bytes, const WherePred& pred, int64_t* index_out, size_t capacity, size_t* total_out,
                  int* chunk_matches_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream) {
   CtxGuard ctx; EngineState& st = *ctx.st;
   if (ensure_device(st)) return -1;
-  // ---- the census: take's; then index_out against every source - a call that fails the second writes nothing at all ----
+  // ---- the census; then index_out against every source - a call that fails the second writes nothing at all ----
   RowScan rs;
   bool usable = false;
   if (rs.census(st, nchunks, chunks, row_bytes, stream, &usable)) return -1;
   const size_t n = rs.n;
   if (!usable) { rs.rows_to(chunk_rows_out); return -1; }
-  const uintptr_t d0 = (uintptr_t)index_out, d1 = d0 + capacity * sizeof(int64_t);
-  for (size_t k = 0; k < n && capacity; k++) {
-    const uintptr_t s0 = (uintptr_t)rs.jobs[k].src, s1 = s0 + (rs.jobs[k].srcsize ? rs.jobs[k].srcsize : (size_t)rs.hdrs[k].cbytes);
-    if (s0 < d1 && d0 < s1) return -1;
-  }
+  if (capacity && overlaps_a_source(rs.jobs, rs.hdrs, (uintptr_t)index_out, (uintptr_t)index_out + capacity * sizeof(int64_t))) return -1;
   rs.rows_to(chunk_rows_out);
   // ---- the passes: per tile its mask words, a count and a base; the running total and the chunks' counters come down at the end ----
   const size_t back_bytes = sizeof(uint64_t) + sizeof(uint32_t) * (n ? n : 1);
-  if (rs.deal(st, sizeof(uint64_t) * WH_WORDS + sizeof(uint32_t) + sizeof(uint64_t), back_bytes)) return -1;
+  if (rs.deal_tiles(st, sizeof(uint64_t) * WH_WORDS + sizeof(uint32_t) + sizeof(uint64_t), back_bytes)) return -1;
   uint8_t *D = rs.D, *P = rs.P;
   const size_t o_back = rs.o_back;
   uint64_t* d_running = (uint64_t*)(D + o_back);
@@ -2206,7 +2203,7 @@ int engine_where(int nchunks, const Job* chunks, size_t row_bytes, const WherePr
   HIP_TRY(hipMemsetAsync(D + o_back, 0, back_bytes, stream));
   for (size_t p = 0; p < rs.npass; p++) {
     bool holds_rows = false;
-    if (rs.decode_pass(st, p, stream, &holds_rows)) return -1;
+    if (rs.decode_tiles(st, p, stream, &holds_rows)) return -1;
     if (holds_rows) {
       const size_t c0 = rs.c0, c1 = rs.c1;
       const uint32_t ntiles = rs.ntiles;
@@ -2254,10 +2251,9 @@ int engine_where(int nchunks, const Job* chunks, size_t row_bytes, const WherePr
 // ---------------------------------------------------------------------------------------------
 // aggregate (include/blosc_gpu_aggregate.h): count, sum, min and max of a row field, per chunk and for the call
 // ---------------------------------------------------------------------------------------------
-// engine_where's front half (RowScan) around the two kernels of k_aggregate.hip: per pass k_aggregate_tiles writes one AggPartial per tile,
+// RowScan as engine_where runs it, around the two kernels of k_aggregate.hip: per pass k_aggregate_tiles writes one AggPartial per tile,
 // k_aggregate_chunks folds them into the chunks' entries of a device table of nchunks AggResult, which comes down with the last
-// synchronisation.  Synchronisations: 2 + 2 per pass that holds a row.  Memory: the plaintext of the largest pass, 40 bytes per tile of
-// WH_TILE rows of it, 64 bytes per chunk.
+// synchronisation.  Synchronisations: 2 + 2 per pass that holds a row.  Workspace: 40 bytes per tile of WH_TILE rows, 64 bytes per chunk.
 // The call's total is folded here, on the host, from the chunks' results in chunk order: what a chunk answers does not depend on its neighbours.
 static void aggregate_none(AggResult* r) { *r = AggResult{0, 0, 0, -1, -1, 0, 0, 0}; }
 static void aggregate_fold(AggResult* total, const AggResult& c, const AggField& f) {
@@ -2288,13 +2284,13 @@ int engine_aggregate(int nchunks, const Job* chunks, size_t row_bytes, const Agg
   rs.rows_to(chunk_rows_out);
   if (!usable) return -1;
   const size_t back_bytes = sizeof(AggResult) * (n ? n : 1);
-  if (rs.deal(st, sizeof(AggPartial), back_bytes)) return -1;
+  if (rs.deal_tiles(st, sizeof(AggPartial), back_bytes)) return -1;
   uint8_t *D = rs.D, *P = rs.P;
   AggResult* d_results = (AggResult*)(D + rs.o_back);
   const WherePred q = filter ? *filter : WherePred{};
   for (size_t p = 0; p < rs.npass; p++) {
     bool holds_rows = false;
-    if (rs.decode_pass(st, p, stream, &holds_rows)) return -1;
+    if (rs.decode_tiles(st, p, stream, &holds_rows)) return -1;
     if (!holds_rows) continue;
     const int in_pass = (int)(rs.c1 - rs.c0);
     Carver wv; wv.off = rs.at;

@@ -6,7 +6,9 @@ attains them, integer sums numpy's with dtype uint64 / int64 (which wraps as the
 where every partial sum is exact, else within the bound of n - 1 binary64 additions in any order, n u A / (1 - n u) with u = 2^-53 and
 A = fsum(|x|), computed in fractions.Fraction.  The tables are where_checks' (make_table, drawn, value_set, where_chunks, table_call, table16,
 neighbour_set); the exact-sum windows (WINDOWS) put every finite value of binary16 and bfloat16, and binary32 over all its exponent fields,
-through the widening and the additions, with the precondition of an exact sum asserted in integers before each call (assert_exact_window)."""
+through the widening and the additions, with the precondition of an exact sum asserted in integers before each call (assert_exact_window).
+On top of that every chunk's floating-point sum, in every case, is held bit for bit against tree_sum: a numpy model of the order of additions
+that the header documents, written from its text (check_tree; tests/test_aggregate_tree_model.py is about the model itself)."""
 import ctypes as C
 import math
 import struct
@@ -117,6 +119,62 @@ def expected_of(vals, raw, mask, kind, nbytes, first_row):
     return (int(vals.size), int(mask.sum()), int((mask & isnan).sum()), low[0], high[0], low[1], high[1], total)
 
 
+TILE_ROWS, LANES, WAVE = 1024, 256, 64      # the header's: tiles of 1024 rows, 256 lanes in four waves of 64
+
+
+def tree_fold(acc):
+    """[m, 256] lane accumulators -> [m]: every wave of 64 lanes folded by the butterfly - l with l ^ 32, ^ 16, ... ^ 1, the lower lane's operand
+    in front, which for the lanes that end in lane 0 is v[:d] + v[d:2 d] - then the four waves in their order"""
+    v = acc.reshape(-1, LANES // WAVE, WAVE)
+    d = WAVE // 2
+    while d >= 1:
+        v = v[:, :, :d] + v[:, :, d:2 * d]
+        d //= 2
+    w = v[:, :, 0]
+    return ((w[:, 0] + w[:, 1]) + w[:, 2]) + w[:, 3]
+
+
+def tree_sum(x):
+    """The binary64 sum of one chunk in the order that include/blosc_gpu_aggregate.h documents, written from its text: x holds the binary64
+    values of the chunk's rows in row order, with +0.0 in the place of every row that fails the filter or holds a NaN.  Tiles of 1024 rows;
+    lane l of 256 adds rows l, l + 256, l + 512, l + 768 of its tile; tree_fold; over the tiles lane l adds the partials of tiles l, l + 256,
+    ... ascending; tree_fold again.
+    The rows behind the chunk's last one and the lanes without a tile are +0.0, and that is exact: an accumulator that starts at +0.0 never
+    becomes -0.0 under round-to-nearest (+0 + -0 = +0, x + -x = +0, and no sum of two values that are not both -0 rounds to -0), so
+    acc + 0.0 has acc's bits - leaving an addition out and adding +0.0 are the same."""
+    x = np.asarray(x, np.float64)
+    ntiles = max(-(-x.size // TILE_ROWS), 1)
+    rows = np.zeros(ntiles * TILE_ROWS)
+    rows[:x.size] = x
+    rows = rows.reshape(ntiles, TILE_ROWS // LANES, LANES)
+    with np.errstate(invalid="ignore", over="ignore"):      # (+inf and -inf meet as a NaN, an overflow is an infinity: IEEE, as the header has it)
+        acc = np.zeros((ntiles, LANES))
+        for step in range(TILE_ROWS // LANES):
+            acc = acc + rows[:, step, :]
+        partial = tree_fold(acc)
+        turns = -(-ntiles // LANES)
+        tiles = np.zeros(turns * LANES)
+        tiles[:ntiles] = partial
+        tiles = tiles.reshape(turns, LANES)
+        acc = np.zeros((1, LANES))
+        for turn in range(turns):
+            acc = acc + tiles[turn]
+        return float(tree_fold(acc)[0])
+
+
+def f64_bits(x):
+    return struct.unpack("<Q", struct.pack("<d", x))[0]
+
+
+def check_tree(got_bits, model, what):
+    """a chunk's sum against tree_sum's: a NaN for a NaN (payload and sign differ between hosts and the device), two zeros with ==, every
+    other value bit for bit"""
+    got = as_f64(got_bits)
+    if math.isnan(model): assert math.isnan(got), (what, "sum", got, "the tree gives a NaN")
+    elif model == 0 and got == 0: pass
+    else: assert got_bits == f64_bits(model), (what, "sum: not the documented order of additions", got, model, hex(got_bits), hex(f64_bits(model)))
+
+
 def check_sum(got_bits, want, exact, what):
     if not isinstance(want, tuple):
         assert got_bits == want, (what, "sum", got_bits, want)
@@ -168,6 +226,10 @@ def check_aggregate(env, source, chunks, rows_plain, row_bytes, field_args, filt
             live[lo:hi] = False
             continue
         check_entry(got[k], expected_of(vals[lo:hi], raw[lo:hi], mask[lo:hi], kind, nbytes, lo), exact, (what, "chunk", k))
+        if kind in (FLOAT, BFLOAT16):      # ... and the order of the additions is the header's
+            with np.errstate(invalid="ignore"):      # (a signalling NaN on its way to binary64)
+                x = vals[lo:hi].astype(np.float64)
+            check_tree(got[k][7], tree_sum(np.where(mask[lo:hi] & ~np.isnan(x), x, 0.0)), (what, "chunk", k))
     total = entry(out.total)
     at = np.flatnonzero(live)
     want = expected_of(vals[at], raw[at], mask[at], kind, nbytes, 0)
@@ -567,6 +629,97 @@ def case_sum_rounding(env, nbytes, nrows, side_stream=None, turn=0):
                                        what=("alone", k))
             e = alone[0]
             assert e[:3] + (e[3] + lo, e[4] + lo) + e[5:] == one[1][k], ("a chunk alone and inside the batch differ", k, e, one[1][k])
+
+
+# ---- chunks taller than 256 tiles: a lane of k_aggregate_chunks folds a second and a third tile ----
+TALL_ROWS = [262144, 262145, 0, 524289, 1]      # 256 tiles (no lane folds twice), 257, none, 513 (lane 0 folds three), one row
+
+
+def rounding_pool(size=300, seed=43):
+    """binary64 patterns whose sums round in nearly every addition: full random 52-bit mantissas over seven binades around 1, both signs.
+    A few hundred of them, for drawn(): the chunks still compress"""
+    rng = np.random.default_rng(seed)
+    mant = rng.integers(0, 1 << 52, size).astype(np.uint64)
+    exp = (1023 + rng.integers(-3, 4, size)).astype(np.uint64)
+    return (rng.integers(0, 2, size).astype(np.uint64) << np.uint64(63)) | (exp << np.uint64(52)) | mant
+
+
+TALL_SEEDS = [24, 15, 12, 33, 12]      # drawn()'s seed of each chunk of TALL_ROWS
+
+
+def tall_patterns(rows=None, seeds=None):
+    """The binary64 field of every row of case_tall_chunks.  A chunk's first half is drawn from the pool; its second half is the first half
+    rotated by 333 rows with the signs flipped.  The true sum of a chunk is then zero (or its one odd row), so what a tree of additions
+    returns is the rounding errors it made on the way, in full precision: two different trees hardly ever agree.  Under GT +0 nothing
+    cancels and about one tree in two agrees with another by chance, which is why each chunk has a seed of its own in TALL_SEEDS:
+    tests/test_aggregate_tree_model.py asserts that these inputs separate the documented tree from every rival in both runs."""
+    rows, seeds = TALL_ROWS if rows is None else rows, TALL_SEEDS if seeds is None else seeds
+    pool, out = rounding_pool(), []
+    for n, seed in zip(rows, seeds):
+        half = drawn(pool, (n + 1) // 2, seed=seed) if n else np.zeros(0, np.uint64)
+        out += [half, np.roll(half, -333)[:n // 2] ^ np.uint64(1 << 63)]
+    return np.concatenate(out)
+
+
+def tall_call(env, patterns, rows, turn=0):
+    """rows of 8 bytes that are the field, in chunks of `rows` rows, the writers in turns"""
+    write = env.writer("lz4", 8, 1, turn)
+    chunks, first = [], 0
+    for k, n in enumerate(rows):
+        chunks.append(write(k, np.ascontiguousarray(patterns[first:first + n], dtype="<u8").view(np.uint8)) if n
+                      else orc_compress(env.oracle, plain(0), 4, 5, 1, "lz4")[1])
+        first += n
+    assert chunk_rows(chunks, 8) == list(rows)
+    return chunks, plaintext(env.oracle, chunks)
+
+
+def case_tall_chunks(env, rows=None, seeds=None, turn=0, thin=False):
+    """chunks of 256, 257 and 513 tiles, an empty one and one of a single row: unfiltered and under GT +0, from both sources and once under a
+    pass bound of 16 KiB.  check_aggregate holds every chunk's sum against tree_sum bit for bit - on values that separate the documented
+    tree from its neighbours (tests/test_aggregate_tree_model.py)"""
+    rows = TALL_ROWS if rows is None else rows
+    chunks, rows_plain = tall_call(env, tall_patterns(rows, seeds), rows, turn)
+    batch, packed = both_sources(env, chunks)
+    for flt in (None, (0, FLOAT, 8, GT, 0)):
+        one = check_aggregate(env, batch, chunks, rows_plain, 8, (0, FLOAT, 8), flt, what="tall chunks")
+        assert math.isfinite(as_f64(one[0][7])) and one[0][2] == 0
+        if thin: return      # (the emulator: one call, unfiltered)
+        assert check_aggregate(env, packed, chunks, rows_plain, 8, (0, FLOAT, 8), flt, what="tall chunks, packed") == one, "batch and packed differ"
+    env.lib.blosc_amd_getitem_pass_bytes(16 << 10)
+    try:
+        assert check_aggregate(env, batch, chunks, rows_plain, 8, (0, FLOAT, 8), flt, what="tall chunks, 16 KiB passes") == one, "the pass bound changes the answer"
+    finally:
+        env.lib.blosc_amd_getitem_pass_bytes(0)
+
+
+TALL_PLANTS = (3 * 1024 + 17, 258 * 1024 + 5, 259 * 1024 + 700)      # the minimum: tile 3 (lane 3's first), tile 258 (lane 2's second, folded in front of lane 3), tile 259 (lane 3's second)
+
+
+def case_tall_extremes(env, kind, turn=0):
+    """the chunk of 524 289 rows alone, as binary64 or int64: the minimum in three rows of three tiles that two lanes of the chunk fold meet
+    in another order than the rows' - min_row is the lowest; the maximum in the last row, alone in the partial tile 512"""
+    nrows = TALL_ROWS[3]
+    p = tall_patterns([nrows], [TALL_SEEDS[3]]).copy()
+    if kind == FLOAT: low, high = int(patterns_of([-32.0], FLOAT, 8)[0]), int(patterns_of([32.0], FLOAT, 8)[0])      # the pool stays below 16
+    else: low, high = 1 << 63, (1 << 63) - 1
+    p[list(TALL_PLANTS)], p[nrows - 1] = low, high
+    chunks, rows_plain = tall_call(env, p, [nrows], turn)
+    total, per_chunk = check_aggregate(env, TakeSource(env.mem, chunks=chunks), chunks, rows_plain, 8, (0, kind, 8), what=("tall extremes", kind_name(kind, 8)))
+    assert total == per_chunk[0] and total[3:7] == (TALL_PLANTS[0], nrows - 1, low.to_bytes(8, "little"), high.to_bytes(8, "little")), total[:7]
+    if kind == INT:
+        true = sum(int(v) for v in field_of(rows_plain, 8, 0, INT, 8))
+        assert not -2 ** 63 <= true < 2 ** 63 and total[7] == true % 2 ** 64, "the integer sum wraps on the way"
+
+
+def case_tall_bytes(env):
+    """one chunk of 300 000 rows of one byte (293 tiles) as uint8: count and sum, unfiltered and under GE 1"""
+    pats = drawn(value_set(UINT, 1), 300000, seed=13)
+    chunks = [env.writer("lz4", 4, 1, 0)(0, make_table(300000, 1, 0, 1, pats))]
+    rows_plain = plaintext(env.oracle, chunks)
+    src = TakeSource(env.mem, chunks=chunks)
+    for flt in (None, (0, UINT, 1, GE, 1)):
+        total, _ = check_aggregate(env, src, chunks, rows_plain, 1, (0, UINT, 1), flt, what="tall, one-byte rows")
+        assert 100000 < total[1] <= 300000 and total[7] == int(rows_plain[rows_plain >= (1 if flt else 0)].astype(np.uint64).sum())
 
 
 def case_damage(env, chunk_of, what="", thin=False):

@@ -56,6 +56,22 @@ def alignment_case(seed=12):
     return lay_out([rng.integers(0, 256, 1000 + k, dtype=np.uint8) for k in range(16)], gap=40, shifts=list(range(16)))
 
 
+LONG_COUNTS = (4096, 4097, 5000)      # k_checksum.hip's ck_find_run probes 64 places a round: two rounds reach 64^2 = 4096 runs, more take a third
+
+
+def long_search_case(nruns, seed=18):
+    """runs of 0 ... 200 random bytes at random shifts; the first and the last run empty, runs 100 ... 169 empty - 70 in a row, more than
+    one round's 64 probes - and, with 5000 runs, runs 400 ... 4499 as well: 4100 in a row, more than two rounds' 4096"""
+    rng = np.random.default_rng(seed)
+    sizes = [int(s) for s in rng.integers(0, 201, nruns)]
+    sizes[0] = sizes[-1] = 0
+    sizes[100:170] = [0] * 70
+    if nruns >= 5000:
+        sizes[400:4500] = [0] * 4100
+    assert sizes[99] and sizes[170] and (nruns < 5000 or (sizes[399] and sizes[4500]))
+    return lay_out([rng.integers(0, 256, n, dtype=np.uint8) for n in sizes], shifts=[int(s) for s in rng.integers(0, 16, nruns)])
+
+
 def many_runs_case(seed=13, nruns=300, longest=3000):
     rng = np.random.default_rng(seed)
     sizes = [int(s) for s in rng.integers(0, longest + 1, nruns)]

@@ -38,6 +38,44 @@ def batch_chunks(oracle, write, row_bytes, scale=1):
     return out
 
 
+MANY_SHAPES = [0, 48, 144, 480, 1536]            # nbytes of chunk k of many_chunks: k % 5 picks; multiples of 48, so rows of 4, 12 and 48 bytes divide them
+MANY_EMPTY = (range(100, 103), range(700, 704), range(1022, 1025))      # stretches of chunks without rows; the last one lies across chunk 1024
+MANY_COUNTS = (1024, 1025, 1300)                 # k_take.hip's TK_LDS_CHUNKS = 1024: the last batch that bisects the LDS copy, the first and a later one that bisect global memory
+
+
+def many_chunks(oracle, write, row_bytes, nchunks, made=None):
+    """More chunks than the kernels' LDS table of row_first holds, small ones: chunk k has MANY_SHAPES[k % 5] bytes - none; 48 and 144, which
+    the oracle stores MEMCPYED; 480 in one block, by write(k, data); 1536 in four blocks of 510.  The first chunk, the last two and the
+    stretches of MANY_EMPTY have no rows.  Chunk k is the same in every batch that holds it with rows (made: a dict that keeps them between
+    calls), so the batch of 1025 is the batch of 1024 and one chunk more"""
+    made = {} if made is None else made
+    empty = orc_compress(oracle, plain(0), 4, 5, 1, "lz4")[1]
+    out = []
+    for k in range(nchunks):
+        n = MANY_SHAPES[k % 5]
+        if n == 0 or k >= nchunks - 2 or any(k in s for s in MANY_EMPTY):
+            out.append(empty)
+            continue
+        if k not in made:
+            rng = np.random.default_rng(1000 + k)
+            data = np.resize(rng.integers(0, 256, 96, dtype=np.uint8), n).copy()      # a period of 96 bytes with a little noise: every block compresses
+            data[rng.integers(0, n, n // 97 + 1)] ^= 1
+            if n == 480: c = write(k, data)
+            elif n == 1536: c = orc_compress(oracle, data, 17, 5, 1, "lz4", blocksize=512)[1]      # (typesize 17 is not split: the block size stands)
+            else: c = orc_compress(oracle, data, 4, 5, 1, "lz4")[1]
+            h = header(c)
+            assert h["nbytes"] == n and (n > 144 or h["flags"] & 2), (k, h)
+            assert n != 480 or h["blocksize"] >= n, (k, h)
+            assert n != 1536 or (not h["flags"] & 2 and -(-n // h["blocksize"]) >= 3), (k, h)
+            made[k] = c
+        out.append(made[k])
+    rows = [header(c)["nbytes"] for c in out]
+    assert all(n % row_bytes == 0 for n in rows) and rows[0] == 0 and rows[-1] == 0 and rows[-2] == 0
+    runs = "".join("e" if n == 0 else "." for n in rows).split(".")
+    assert sum(1 for r in runs if len(r) >= 3) >= 2, "two stretches of three or more chunks without rows"
+    return out
+
+
 def plaintext(oracle, chunks):
     """the rows of a call: the oracle's plaintext of every chunk, end to end"""
     parts = []

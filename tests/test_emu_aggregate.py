@@ -72,6 +72,11 @@ def test_many_tiles(env):
     A.case_many_tiles(env, thin=True)
 
 
+def test_a_chunk_taller_than_256_tiles(env):
+    """the device's chunk of 257 tiles, its empty one and its chunk of one row: lane 0 of k_aggregate_chunks folds a second tile"""
+    A.case_tall_chunks(env, rows=A.TALL_ROWS[1:3] + A.TALL_ROWS[4:], seeds=A.TALL_SEEDS[1:3] + A.TALL_SEEDS[4:], thin=True)
+
+
 @pytest.mark.parametrize("kind,nbytes", A.FLOATS, ids=[A.kind_name(*k) for k in A.FLOATS])
 def test_float_sum_exact_and_subnormals(env, kind, nbytes):
     at = A.FLOATS.index((kind, nbytes))

@@ -8,7 +8,8 @@ import os
 import numpy as np
 import pytest
 
-from checksum_checks import (KIND_IDS, KINDS, ZLIB, aligned_copy, alignment_case, check_runs, expected, grid_case, lay_out, many_runs_case)
+from checksum_checks import (KIND_IDS, KINDS, LONG_COUNTS, ZLIB, aligned_copy, alignment_case, check_runs, expected, grid_case, lay_out, long_search_case,
+                             many_runs_case)
 from packed_checks import mixed_batch
 from test_emu_library import emulib  # noqa: F401  (the fixture)
 from test_emu_packed import BLOCKSIZE, EMU_SIZES
@@ -80,6 +81,16 @@ def test_more_runs_than_one_workgroup_is_wide(elib, pkgmod, kind):
     buf, runs = many_runs_case()
     assert len(runs) == 300 and sum(1 for _, n in runs if n == 0) >= 4
     check_runs(pkgmod, elib, kind, buf.ctypes.data, buf, runs, "300 runs")
+
+
+@pytest.mark.parametrize("nruns", LONG_COUNTS)
+@pytest.mark.parametrize("kind", KINDS, ids=KIND_IDS)
+def test_more_runs_than_two_rounds_of_the_search(elib, pkgmod, kind, nruns):
+    """4096 runs are found in two rounds of the 64-way search of a tile's run, 4097 and 5000 take a third; stretches of 70 and 4100 empty runs"""
+    buf, runs = long_search_case(nruns)
+    assert len(runs) == nruns
+    buf = aligned_copy(buf)
+    check_runs(pkgmod, elib, kind, buf.ctypes.data, buf, runs, f"{nruns} runs")
 
 
 @pytest.mark.parametrize("align", [1, 16])

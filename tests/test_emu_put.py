@@ -10,7 +10,7 @@ import pytest
 from getitem_ranges_checks import NumpyMem, pick_damage, plain
 from helpers import header, orc_compress, ptr, ref_compress
 from put_checks import ALIGNS, SENTINEL, bound, check_census_failure, check_put, expected, new_rows, put_index_sets, run_put
-from take_checks import BLOCKSIZE, N, TakeSource, batch_chunks, chunk_rows, offsets_for, pack_container
+from take_checks import BLOCKSIZE, N, TakeSource, batch_chunks, chunk_rows, many_chunks, offsets_for, pack_container
 from test_emu_library import emulib  # noqa: F401  (the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -151,6 +151,23 @@ def test_a_damaged_chunk_is_carried_over(elib, pkgmod, oracle):
         index = np.concatenate([sets["random"][:300], sets["edges"], sets["out of bounds"]])
         _, put, _ = check_put(pkgmod, elib, mem, oracle, TakeSource(mem, chunks=chunks), chunks, row_bytes, index, params, 16, 1, True, what=kind)
         assert put.rewritten() == [-1, 1] and put.failed() > 5
+
+
+def test_more_chunks_than_the_lds_table_holds(elib, pkgmod, oracle, ref):
+    """take_checks.many_chunks, 1025 chunks out of a container: k_put_claim and k_put_scatter bisect row_first in global memory.  The first and
+    last row of every 13th chunk and of the chunks around the stretches without rows, and out-of-bounds values, in rows of 12 bytes; every
+    chunk's rewritten_out, every rewritten chunk read back by the oracle (the emulator encodes 40 KB a second; the device: 1024 and 1300
+    chunks too, rows of 4 and 48 bytes, every index set, both sources)"""
+    mem = NumpyMem()
+    chunks = many_chunks(oracle, writer(elib, oracle, ref, "lz4", 4, 1, 0), 48, 1025)
+    params = [pkgmod.cparams(4, 5, 1, b"lz4", BLOCKSIZE) for _ in chunks]
+    rows = chunk_rows(chunks, 12)
+    first = np.concatenate([[0], np.cumsum(rows)])
+    picked = [k for k in sorted(set(range(1, 1025, 13)) | {98, 99, 103, 104, 698, 699, 704, 1019, 1021}) if rows[k]]
+    sets = put_index_sets(chunks, 12)
+    index = np.concatenate([[int(first[k]), int(first[k + 1]) - 1] for k in picked] + [sets["out of bounds"][1::4]]).astype(np.int64)
+    _, put, _ = check_put(pkgmod, elib, mem, oracle, TakeSource(mem, *(None,) + pack_container(chunks)), chunks, 12, index, params, 1, 5, True, what="many chunks")
+    assert [k for k, w in enumerate(put.rewritten()) if w] == picked and len(picked) > 60
 
 
 def test_census_failures(elib, pkgmod, oracle):

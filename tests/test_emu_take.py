@@ -10,7 +10,7 @@ import pytest
 from getitem_ranges_checks import NumpyMem, pick_damage, plain
 from helpers import header, orc_compress, ptr, ref_compress
 from take_checks import (BLOCKSIZE, N, TakeSource, batch_chunks, check_census_failure, check_take, chunk_rows, damaged_rows, index_sets,
-                         offsets_for, pack_container, plaintext)
+                         many_chunks, offsets_for, pack_container, plaintext)
 from test_emu_library import emulib  # noqa: F401  (the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -136,6 +136,22 @@ def test_a_damaged_block_fails_the_rows_that_touch_it(elib, pkgmod, oracle, cnam
             nbad = int((want == code).sum())
             assert nbad >= 8177 // row_bytes and int((want > 0).sum()) == index.size - nbad, (cname, kind, row_bytes, nbad)
             check_take(pkgmod, elib, mem, TakeSource(mem, chunks=chunks), chunks, rows_plain, row_bytes, index, 0, False, codes, what=(cname, kind))
+
+
+def test_more_chunks_than_the_lds_table_holds(elib, pkgmod, oracle, ref):
+    """take_checks.many_chunks: 1024 chunks out of a container (row_first bisected in LDS), then the same and one more as src[] (bisected in
+    global memory): the first and last row of every chunk, block edges, random rows and out-of-bounds values, in rows of 12 bytes (the
+    device: 1300 chunks too, rows of 4 and 48 bytes, every index set, both sources each)"""
+    mem = NumpyMem()
+    made = {}
+    write = writer(elib, oracle, ref, "lz4", 4, 1, 0)
+    for nchunks in (1024, 1025):
+        chunks = many_chunks(oracle, write, 48, nchunks, made)
+        rows_plain = plaintext(oracle, chunks)
+        src = TakeSource(mem, chunks=chunks) if nchunks == 1025 else TakeSource(mem, *(None,) + pack_container(chunks))
+        sets = index_sets(chunks, 12)
+        index = np.concatenate([sets["edges"], sets["out of bounds"], sets["random"][:600]])
+        check_take(pkgmod, elib, mem, src, chunks, rows_plain, 12, index, 5, nchunks == 1025, what=("many chunks", nchunks))
 
 
 def test_census_failures(elib, pkgmod, oracle):

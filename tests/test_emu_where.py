@@ -9,7 +9,7 @@ import pytest
 
 from getitem_ranges_checks import NumpyMem
 from helpers import orc_compress, ptr, ref_compress
-from take_checks import BLOCKSIZE
+from take_checks import BLOCKSIZE, many_chunks
 from test_emu_library import emulib  # noqa: F401  (the fixture)
 from test_emu_take import SETTINGS
 import where_checks as W
@@ -84,6 +84,17 @@ def test_densities(env, name):
 
 def test_many_tiles(env):
     W.case_many_tiles(env, thin=True)
+
+
+def test_more_tiles_in_a_pass_than_scan_threads(env):
+    """1025 tiles in one pass: threads of k_where_scan with two tiles, one with one, the rest with none (the device: 1024 and 2051 tiles as
+    well, and each with the table cut inside a late tile)"""
+    W.case_wide_pass(env, "1025 tiles", thin=True)
+
+
+def test_more_chunks_than_tiles_a_thread(env):
+    """1300 small chunks, more than 1024 tiles, in one pass under EQ (the device: in dozens of passes of 16 KiB as well, and under NE with the table cut)"""
+    W.case_many_chunks(env, many_chunks(env.oracle, env.writer("lz4", 4, 1, 0), 48, 1300), pass_bytes=(0,), thin=True)
 
 
 def test_capacity(env):

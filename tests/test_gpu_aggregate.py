@@ -72,6 +72,20 @@ def test_many_tiles(env):
     A.case_many_tiles(env)
 
 
+def test_chunks_taller_than_256_tiles(env):
+    """chunks of 256, 257 and 513 tiles: a lane of k_aggregate_chunks folds a second and a third tile, every sum bit for bit the documented tree's"""
+    A.case_tall_chunks(env)
+
+
+@pytest.mark.parametrize("kind", [A.FLOAT, A.INT], ids=["float64", "int64"])
+def test_extremes_across_the_second_turn_of_the_tile_loop(env, kind):
+    A.case_tall_extremes(env, kind, turn=kind)
+
+
+def test_one_byte_rows_of_a_tall_chunk(env):
+    A.case_tall_bytes(env)
+
+
 @pytest.mark.parametrize("kind,nbytes", A.FLOATS, ids=[A.kind_name(*k) for k in A.FLOATS])
 def test_float_sum_exact_and_subnormals(env, kind, nbytes):
     """sums whose every partial sum is exact equal math.fsum; a column of the format's smallest subnormal is count x that value"""

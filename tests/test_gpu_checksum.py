@@ -4,7 +4,7 @@ holds: runs of 64 MiB, and runs on both sides of the 4 GiB offset of one buffer.
 import numpy as np
 import pytest
 
-from checksum_checks import KIND_IDS, KINDS, ZLIB, alignment_case, check_runs, grid_case, lay_out, many_runs_case
+from checksum_checks import KIND_IDS, KINDS, LONG_COUNTS, ZLIB, alignment_case, check_runs, grid_case, lay_out, long_search_case, many_runs_case
 from helpers import DATASETS
 
 pytestmark = pytest.mark.gpu
@@ -35,6 +35,16 @@ def test_alignment_and_many_runs(pkg, lib, kind):
     for what, (buf, runs) in (("alignment", alignment_case()), ("300 runs", many_runs_case()), ("20000 runs", many_runs_case(15, 20000, 40))):
         dev = to_dev(buf)
         check_runs(pkg, lib, kind, dev.data_ptr(), buf, runs, what)
+
+
+@pytest.mark.parametrize("nruns", LONG_COUNTS)
+@pytest.mark.parametrize("kind", KINDS, ids=KIND_IDS)
+def test_more_runs_than_two_rounds_of_the_search(pkg, lib, kind, nruns):
+    """4096 runs are found in two rounds of the 64-way search of a tile's run, 4097 and 5000 take a third; stretches of 70 and 4100 empty runs"""
+    buf, runs = long_search_case(nruns)
+    assert len(runs) == nruns
+    dev = to_dev(buf)
+    check_runs(pkg, lib, kind, dev.data_ptr(), buf, runs, f"{nruns} runs")
 
 
 @pytest.fixture(scope="module")

@@ -10,7 +10,7 @@ import pytest
 from getitem_ranges_checks import TorchMem, pick_damage, plain
 from helpers import header, orc_compress, ref_compress
 from put_checks import ALIGNS, check_census_failure, check_put, put_index_sets
-from take_checks import BLOCKSIZE, N, ROW_SIZES, TakeSource, batch_chunks, offsets_for, pack_container
+from take_checks import BLOCKSIZE, MANY_COUNTS, N, ROW_SIZES, TakeSource, batch_chunks, chunk_rows, many_chunks, offsets_for, pack_container
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -122,6 +122,64 @@ def test_a_damaged_chunk_is_carried_over(pkg, lib, mem, oracle, ref, cname):
             index = np.concatenate([sets["in order"], sets["edges"]])
             _, put, _ = check_put(pkg, lib, mem, oracle, TakeSource(mem, chunks=chunks), chunks, row_bytes, index, params, 16, 1, True, what=(cname, kind))
             assert put.rewritten() == [-1, 1] and put.failed() >= N // row_bytes
+
+
+@pytest.fixture(scope="module")
+def many(pkg, mem, oracle, ref):
+    """nchunks -> (the chunks of take_checks.many_chunks, the batch source, the packed one), made once"""
+    made, batches = {}, {}
+    write = writer(pkg, mem, oracle, ref, "lz4", 4, 1, 0)
+
+    def get(nchunks):
+        if nchunks not in batches:
+            chunks = many_chunks(oracle, write, 48, nchunks, made)
+            batches[nchunks] = (chunks, TakeSource(mem, chunks=chunks), TakeSource(mem, *(None,) + pack_container(chunks)))
+        return batches[nchunks]
+    return get
+
+
+@pytest.mark.parametrize("row_bytes", [4, 12, 48])
+@pytest.mark.parametrize("nchunks", MANY_COUNTS)
+def test_more_chunks_than_the_lds_table_holds(pkg, lib, mem, oracle, many, nchunks, row_bytes):
+    """1024 chunks bisect the LDS copy of row_first in k_put_claim and k_put_scatter, 1025 and 1300 the table in global memory: every index set
+    from both sources at aligns 1 and 256, with and without a status table, `rows` at offsets 0 and 5, and once under a pass bound of 16 KiB;
+    rewritten_out is the expectation for every chunk and the oracle reads every rewritten one (check_put)"""
+    chunks, batch, packed = many(nchunks)
+    params = [pkg.cparams(4, 5, 1, b"lz4", BLOCKSIZE) for _ in chunks]
+    sets = put_index_sets(chunks, row_bytes)
+    holding = sum(1 for r in chunk_rows(chunks, row_bytes) if r)
+    for m, (name, index) in enumerate(sets.items()):
+        src, align, offset = (batch, packed)[m % 2], (1, 256)[(m // 2) % 2], (0, 5)[(m // 4) % 2]
+        _, put, _ = check_put(pkg, lib, mem, oracle, src, chunks, row_bytes, index, params, align, offset, m % 3 != 2, what=(nchunks, name))
+        if name in ("in order", "edges"):
+            assert put.rewritten().count(1) == holding and put.rewritten().count(0) == nchunks - holding
+    mixed = np.concatenate([sets["edges"], sets["out of bounds"], sets["random"], sets["edges"][::-1]])
+    check_put(pkg, lib, mem, oracle, packed, chunks, row_bytes, mixed, params, 1, 5, True, what=(nchunks, "mixed, packed"))
+    one, put1, _ = check_put(pkg, lib, mem, oracle, batch, chunks, row_bytes, mixed, params, 256, 0, False, what=(nchunks, "mixed"))
+    lib.blosc_amd_getitem_pass_bytes(16 << 10)
+    try:
+        many_passes, put2, _ = check_put(pkg, lib, mem, oracle, batch, chunks, row_bytes, mixed, params, 256, 0, False, what=(nchunks, "16 KiB passes"))
+    finally:
+        lib.blosc_amd_getitem_pass_bytes(0)
+    assert put1.offsets() == put2.offsets() and put1.results() == put2.results() and np.array_equal(one, many_passes), "the passes changed the container"
+
+
+def test_carried_over_chunks_around_the_tile_ends_of_assemble(pkg, lib, mem, oracle):
+    """MEMCPYED chunks of 16 383, 16 384, 16 385, 32 768 and 32 769 bytes that no index touches, between chunks that are rewritten, at align 1:
+    the 16 KiB tiles of k_put_assemble end in front of, at and behind a chunk's end, and its head / body / tail split meets every size"""
+    rng = np.random.default_rng(77)
+    sizes = (16383, 16384, 16385, 32768, 32769)
+    carried = [orc_compress(oracle, rng.integers(0, 256, c - 16, dtype=np.uint8), 1, 5, 0, "lz4")[1] for c in sizes]
+    assert [(header(c)["cbytes"], header(c)["flags"] & 2) for c in carried] == [(c, 2) for c in sizes]
+    small = [orc_compress(oracle, plain(n, seed=60 + n), 1, 5, 0, "lz4", blocksize=512)[1] for n in (1001, 3, 2048)]
+    chunks = [small[0], carried[0], carried[1], small[1], carried[2], carried[3], small[2], carried[4]]
+    rows = chunk_rows(chunks, 1)
+    first = np.concatenate([[0], np.cumsum(rows)])
+    index = np.concatenate([np.arange(first[k], first[k + 1])[::3] for k in (0, 3, 6)]).astype(np.int64)
+    params = [pkg.cparams(1, 5, 0, b"lz4", 512) for _ in chunks]
+    for src in (TakeSource(mem, chunks=chunks), TakeSource(mem, *(None,) + pack_container(chunks, align=1))):
+        _, put, _ = check_put(pkg, lib, mem, oracle, src, chunks, 1, index, params, 1, 0, True, what="tile ends")
+        assert put.rewritten() == [1, 0, 0, 1, 0, 0, 1, 0] and put.results()[1:3] + put.results()[4:6] + put.results()[7:] == list(sizes)
 
 
 def test_census_failures(pkg, lib, mem, oracle):

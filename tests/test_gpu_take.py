@@ -9,8 +9,8 @@ import pytest
 
 from getitem_ranges_checks import TorchMem, pick_damage, plain
 from helpers import header, orc_compress, ref_compress
-from take_checks import (BLOCKSIZE, N, ROW_SIZES, TakeSource, batch_chunks, check_census_failure, check_take, chunk_rows, damaged_rows, index_sets,
-                         offsets_for, pack_container, plaintext)
+from take_checks import (BLOCKSIZE, MANY_COUNTS, N, ROW_SIZES, TakeSource, batch_chunks, check_census_failure, check_take, chunk_rows, damaged_rows,
+                         index_sets, many_chunks, offsets_for, pack_container, plaintext)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -107,6 +107,45 @@ def test_a_damaged_block_fails_the_rows_that_touch_it(pkg, lib, mem, oracle, ref
             nbad = int((want == code).sum())
             assert nbad >= max(8177 // row_bytes, 1) and int((want > 0).sum()) == index.size - nbad, (cname, kind, row_bytes, nbad)
             check_take(pkg, lib, mem, TakeSource(mem, chunks=chunks), chunks, rows_plain, row_bytes, index, 0, False, codes, what=(cname, kind))
+
+
+@pytest.fixture(scope="module")
+def many(pkg, mem, oracle, ref):
+    """nchunks -> (the chunks of take_checks.many_chunks, their plaintext, the batch source, the packed one), made once"""
+    made, batches = {}, {}
+    write = writer(pkg, mem, oracle, ref, "lz4", 4, 1, 0)
+
+    def get(nchunks):
+        if nchunks not in batches:
+            chunks = many_chunks(oracle, write, 48, nchunks, made)
+            batches[nchunks] = (chunks, plaintext(oracle, chunks), TakeSource(mem, chunks=chunks), TakeSource(mem, *(None,) + pack_container(chunks)))
+        return batches[nchunks]
+    return get
+
+
+@pytest.mark.parametrize("row_bytes", [4, 12, 48])
+@pytest.mark.parametrize("nchunks", MANY_COUNTS)
+def test_more_chunks_than_the_lds_table_holds(pkg, lib, mem, many, nchunks, row_bytes):
+    """1024 chunks bisect k_take.hip's LDS copy of row_first, 1025 and 1300 the table in global memory: every index set - the first and last row
+    of every chunk among them - from both sources, with and without a status table, dest at offsets 0 and 5, and once under a pass bound of
+    16 KiB.  Rows of 4 bytes move at their natural width, 12 by bytes in one lane, 48 in several lanes"""
+    chunks, rows_plain, batch, packed = many(nchunks)
+    if nchunks == 1025:
+        assert all(np.array_equal(a, b) for a, b in zip(chunks[:1024], many(1024)[0])), "the batch of 1025 is the batch of 1024 and one chunk"
+    sets = index_sets(chunks, row_bytes)
+    assert sets["edges"].size >= 2 * sum(1 for r in chunk_rows(chunks, row_bytes) if r)
+    for name, index in sets.items():
+        for src in (batch, packed):
+            check_take(pkg, lib, mem, src, chunks, rows_plain, row_bytes, index, 0, True, what=(nchunks, name, src.packed))
+            check_take(pkg, lib, mem, src, chunks, rows_plain, row_bytes, index, 5, False, what=(nchunks, name, src.packed))
+    mixed = np.concatenate([sets["edges"], sets["out of bounds"], sets["random"]])
+    check_take(pkg, lib, mem, batch, chunks, rows_plain, row_bytes, mixed, 5, True, what=(nchunks, "mixed"))
+    check_take(pkg, lib, mem, packed, chunks, rows_plain, row_bytes, mixed, 0, False, what=(nchunks, "mixed"))
+    lib.blosc_amd_getitem_pass_bytes(16 << 10)
+    try:
+        check_take(pkg, lib, mem, batch, chunks, rows_plain, row_bytes, mixed, 0, True, what=(nchunks, "16 KiB passes"))
+    finally:
+        lib.blosc_amd_getitem_pass_bytes(0)
 
 
 def test_census_failures(pkg, lib, mem, oracle):

@@ -11,7 +11,7 @@ import pytest
 
 from getitem_ranges_checks import TorchMem
 from helpers import orc_compress, ref_compress
-from take_checks import BLOCKSIZE
+from take_checks import BLOCKSIZE, many_chunks
 from test_emu_take import SETTINGS
 import where_checks as W
 
@@ -90,6 +90,18 @@ def test_densities(env, name):
 
 def test_many_tiles(env):
     W.case_many_tiles(env)
+
+
+@pytest.mark.parametrize("name", list(W.WIDE))
+def test_more_tiles_in_a_pass_than_scan_threads(env, name):
+    """1024, 1025 and 2051 tiles in one pass: every thread of k_where_scan with one tile; threads with two, one and no tiles; three tiles a
+    thread with a chunk boundary inside a thread's stretch"""
+    W.case_wide_pass(env, name)
+
+
+def test_more_chunks_than_tiles_a_thread(env):
+    """1300 small chunks, more than 1024 tiles: in one pass and in dozens of passes of 16 KiB"""
+    W.case_many_chunks(env, many_chunks(env.oracle, env.writer("lz4", 4, 1, 0), 48, 1300))
 
 
 def test_capacity(env):

@@ -434,6 +434,81 @@ def case_many_tiles(env, thin=False):
         check_where(env.lib, env.mem, src, chunks, rows_plain, 1, (0, UINT, 1, 5, 0x35), env.pkg, capacity=100000, what="many tiles, cut")
 
 
+TILE_ROWS, SCAN_THREADS = 1024, 1024      # k_where.hip's WH_TILE and WH_SCAN_THREADS: thread i of k_where_scan owns `per` tiles from i * per
+# rows per chunk, one byte each: 1024 tiles (per = 1, every scan thread busy); 1025 (per = 2: thread 512 owns one tile, 513 ... 1023 none);
+# 1465 + 586 tiles in one pass (per = 3: the chunk boundary lies inside thread 488's stretch)
+WIDE = {"1024 tiles": [1024 * 1024], "1025 tiles": [1024 * 1024 + 1], "two chunks": [1500000, 600001]}
+
+
+def tiles_of_pass(rows):
+    """(the pass's tile number of every row, the number of tiles): tiles of 1024 rows that never straddle a chunk"""
+    per_chunk = [-(-r // TILE_ROWS) for r in rows]
+    first = np.concatenate([[0], np.cumsum(per_chunk)])
+    return np.concatenate([first[k] + np.arange(r) // TILE_ROWS for k, r in enumerate(rows)]), int(first[-1])
+
+
+def wide_patterns(rows, hit, miss):
+    """density_patterns' one row in sixteen, then whole tiles without a match: with per = 3 the middle tile of every scan thread's stretch, so
+    that the tiles either side of every boundary between two threads hold matches; with per <= 2 every tile lies at such a boundary, and one
+    tile in eight is emptied.  The first and the last tile keep their matches, in the first and the last row.  Returns (patterns, the matches
+    of every tile)"""
+    nrows = sum(rows)
+    tile, ntiles = tiles_of_pass(rows)
+    per = -(-ntiles // SCAN_THREADS)
+    p = density_patterns("one in sixteen", nrows, None, hit, miss)
+    none = (tile % 3 == 1) if per == 3 else (tile % 8 == 5)
+    p[none & (tile != 0) & (tile != ntiles - 1)] = miss
+    p[0] = p[nrows - 1] = hit
+    counts = np.bincount(tile, weights=(p == hit), minlength=ntiles).astype(np.int64)
+    assert counts[0] and counts[-1] and (counts == 0).any()
+    if per == 3:
+        assert np.all(counts[np.arange(ntiles) % 3 != 1] > 0), "a tile next to a boundary between two scan threads holds no match"
+    return p, counts
+
+
+def case_wide_pass(env, name, thin=False):
+    """more than 1024 tiles in one pass: a thread of k_where_scan owns two or three tiles, and the threads behind the last tile own none.
+    EQ on one-byte rows; the table with room for every match, and cut inside a tile that a high-numbered thread owns"""
+    rows = WIDE[name]
+    p, counts = wide_patterns(rows, 1, 0)
+    ntiles = counts.size
+    assert -(-ntiles // SCAN_THREADS) == {"1024 tiles": 1, "1025 tiles": 2, "two chunks": 3}[name]
+    write = env.writer("lz4", 4, 1, 0)
+    chunks, first = [], 0
+    for k, n in enumerate(rows):
+        chunks.append(write(k, make_table(n, 1, 0, 1, p[first:first + n])))
+        first += n
+    rows_plain = plaintext(env.oracle, chunks)
+    src = TakeSource(env.mem, chunks=chunks)
+    want = check_where(env.lib, env.mem, src, chunks, rows_plain, 1, (0, UINT, 1, 0, 1), env.pkg, what=("wide pass", name))
+    assert want.size == counts.sum()
+    if thin: return
+    t = max(t for t in range(ntiles - 1) if counts[t] >= 2)      # the last full tile with matches: the highest thread that owns tiles owns it
+    cut = int(counts[:t].sum() + counts[t] // 2)
+    assert t >= ntiles - 4 and counts[:t].sum() < cut < counts[:t + 1].sum()
+    check_where(env.lib, env.mem, src, chunks, rows_plain, 1, (0, UINT, 1, 0, 1), env.pkg, capacity=cut, what=("wide pass, cut", name))
+
+
+def case_many_chunks(env, chunks, pass_bytes=(0, 16 << 10), thin=False):
+    """take_checks.many_chunks as one-byte rows: more than 1024 tiles with another chunk for nearly every tile, under the default pass bound
+    and under 16 KiB - dozens of passes, the running total carried on the device across all of them"""
+    rows = chunk_rows(chunks, 1)
+    assert sum(-(-r // TILE_ROWS) for r in rows) > SCAN_THREADS and len(chunks) > 1024
+    rows_plain = plaintext(env.oracle, chunks)
+    constant = int(np.bincount(rows_plain, minlength=256).argmax())
+    src = TakeSource(env.mem, chunks=chunks)
+    for bound in pass_bytes:
+        env.lib.blosc_amd_getitem_pass_bytes(bound)
+        try:
+            assert rows_plain.size > 30 * bound
+            want = check_where(env.lib, env.mem, src, chunks, rows_plain, 1, (0, UINT, 1, 0, constant), env.pkg, what=("many chunks", bound))
+            if not thin:
+                check_where(env.lib, env.mem, src, chunks, rows_plain, 1, (0, UINT, 1, 1, constant), env.pkg, capacity=rows_plain.size // 2, what=("many chunks, cut", bound))
+        finally:
+            env.lib.blosc_amd_getitem_pass_bytes(0)
+        assert 100 < want.size < rows_plain.size // 2
+
+
 def case_capacity(env, setting, turn=0):
     """case 5: capacity 0 with a NULL table, total - 1, total, total + 7 - the prefix exact, the rest untouched, the counts the same in all four"""
     layout = (12, 5, INT, 4)

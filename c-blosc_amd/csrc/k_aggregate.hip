@@ -1,7 +1,7 @@
 // k_aggregate.hip — count, sum, min and max of a row field of compressed chunks (include/blosc_gpu_aggregate.h; engine.hip: engine_aggregate).
 //
 // The pass is where's (k_where.hip): the chunks decoded whole into plaintext slots (dev_types.h: WhereChunk), tiles of WH_TILE rows that never
-// straddle a chunk, tile_first and where_chunk_of.  Two kernels per pass, and no workgroup ever waits for another one:
+// straddle a chunk, tile_first and tile_owner (row_prims.h).  Two kernels per pass, and no workgroup ever waits for another one:
 //   k_aggregate_tiles    one lane per row: the filter's field against its constant (where_test) and the aggregated field's key (where_key);
 //                        every lane accumulates its WH_STEPS rows in step order, the wave folds its lanes by a butterfly of __shfl_xor, the
 //                        workgroup its waves through LDS in wave order: one AggPartial per tile;
@@ -14,8 +14,9 @@
 // Bytes per row: the field (and the filter's, where it is another one); 40 bytes per tile and 64 per chunk are written.
 #pragma once
 #include "dev_types.h"
-#include "k_where.hip"
 #include "mem_prims.h"
+#include "row_prims.h"
+#include "wave_prims.h"
 
 namespace bamd {
 
@@ -48,19 +49,14 @@ __device__ __forceinline__ AggAcc agg_fold(AggAcc a, const AggAcc& b, bool fp) {
   return a;
 }
 
-// the cross-lane builtins carry 32 bits: a 64-bit value moves as two halves
 __device__ __forceinline__ uint32_t agg_xor32(uint32_t v, int d) { return (uint32_t)__shfl_xor((int)v, d, 64); }
-__device__ __forceinline__ uint64_t agg_xor64(uint64_t v, int d) {
-  const uint32_t lo = agg_xor32((uint32_t)v, d), hi = agg_xor32((uint32_t)(v >> 32), d);
-  return ((uint64_t)hi << 32) | lo;
-}
 // the wave's lanes folded: lane l takes lane l ^ 32, then ^ 16, ... ^ 1.  Every lane runs the same tree over the same values (the lower
 // lane's operand in front), so all 64 hold the result; the caller takes lane 0's.
 __device__ __forceinline__ AggAcc agg_wave(AggAcc a, uint32_t lane, bool fp) {
   for (int d = 32; d >= 1; d >>= 1) {
     AggAcc o;
-    o.min_key = (int64_t)agg_xor64((uint64_t)a.min_key, d); o.max_key = (int64_t)agg_xor64((uint64_t)a.max_key, d);
-    o.sum = agg_xor64(a.sum, d);
+    o.min_key = (int64_t)wave_xor_u64((uint64_t)a.min_key, d); o.max_key = (int64_t)wave_xor_u64((uint64_t)a.max_key, d);
+    o.sum = wave_xor_u64(a.sum, d);
     o.min_row = agg_xor32(a.min_row, d); o.max_row = agg_xor32(a.max_row, d);
     o.count = agg_xor32(a.count, d); o.nans = agg_xor32(a.nans, d);
     a = (lane & (uint32_t)d) ? agg_fold(o, a, fp) : agg_fold(a, o, fp);
@@ -89,7 +85,7 @@ __global__ __launch_bounds__(WH_THREADS) void k_aggregate_tiles(const WhereChunk
   const bool fp = f.kind == 2;
   const bool one_load = filtered && q.offset == f.offset && q.bytes == f.bytes;      // the filter reads the aggregated bytes
   for (uint32_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const uint32_t c = where_chunk_of(tile_first, nchunks, t);
+    const uint32_t c = tile_owner(tile_first, nchunks, t);
     const WhereChunk ch = chunks[c];
     const uint32_t row0 = (t - tile_first[c]) * WH_TILE;
     const gu8* base = as_global(ch.slot);

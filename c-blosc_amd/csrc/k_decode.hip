@@ -15,6 +15,7 @@
 #include <type_traits>
 #include "dev_types.h"
 #include "wave_prims.h"
+#include "row_prims.h"
 
 namespace bamd {
 
@@ -808,11 +809,9 @@ __global__ __launch_bounds__(64 * DEC_WAVES, BAMD_DEC_MINWAVES) void k_decode_st
 // ---------------------------------------------------------------------------------------------
 // A range is cut into tiles of GI_TILE bytes and tile_first[r] is the number of tiles in front of range r (tile_first[nranges]: all of
 // them; a range that failed on the host has none), so a 1-byte range and a 64 MiB range share one grid: every wave takes tiles
-// grid-stride and finds its range by bisection.  It first reads the verdict of the blocks the range depends on - a failed range
-// is not written at all - and then copies: bytes up to the first 16-byte boundary of the DESTINATION, 16-byte loads and stores over
-// the middle, bytes behind it.  The stores of the middle are aligned; the loads are as well where source and destination are mutually
-// aligned, and otherwise (the caller's dest is anywhere, the source sits at start * typesize inside a block) they are unaligned
-// dwordx4 loads, which gfx950's global memory takes (mem_prims.h).
+// grid-stride and finds its range by bisection (row_prims.h: tile_owner).  It first reads the verdict of the blocks the range depends on - a
+// failed range is not written at all - and then copies (row_prims.h: wave_copy_tile; the caller's dest is anywhere, the source sits at
+// start * typesize inside a block).
 // Algorithmic HBM bytes per range: nbytes read (L2-warm: the decode kernels have just written them) + nbytes written.
 constexpr int GI_THREADS = 64;          // one wave per workgroup: the verdict is a wave-wide vote
 constexpr uint32_t GI_TILE = 16384;     // 16 steps of 64 lanes x 16 bytes
@@ -823,11 +822,7 @@ __global__ __launch_bounds__(GI_THREADS) void k_getitem_gather(const GatherRange
   const uint32_t lane = threadIdx.x;
   const uint32_t ntiles = tile_first[nranges];
   for (uint32_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    uint32_t r = 0, hi = (uint32_t)nranges;      // tile_first[r] <= t < tile_first[hi]; of equal entries (ranges without tiles) the last one
-    while (hi - r > 1u) {
-      const uint32_t mid = (r + hi) >> 1;
-      if (tile_first[mid] <= t) r = mid; else hi = mid;
-    }
+    const uint32_t r = tile_owner(tile_first, nranges, t);
     const GatherRange g = ranges[r];
     bool bad = false;
     for (int32_t k = (int32_t)lane; k < g.nstatus; k += GI_THREADS) bad |= status[g.status0 + k] < 0;
@@ -835,14 +830,7 @@ __global__ __launch_bounds__(GI_THREADS) void k_getitem_gather(const GatherRange
     const uint32_t off = (t - tile_first[r]) * GI_TILE;
     if (off >= g.nbytes) continue;
     const uint32_t n = g.nbytes - off < GI_TILE ? g.nbytes - off : GI_TILE;
-    const gu8* s = as_global(g.src) + off;
-    gu8* d = as_global(g.dst) + off;
-    uint32_t head = (uint32_t)((16u - ((uint32_t)(uintptr_t)d & 15u)) & 15u);
-    if (head > n) head = n;
-    const uint32_t body = (n - head) & ~15u, tail = n - head - body;
-    if (lane < head) d[lane] = s[lane];
-    for (uint32_t k = lane * 16u; k < body; k += GI_THREADS * 16u) g_st16(d + head + k, g_ld16(s + head + k));
-    if (lane < tail) d[head + body + lane] = s[head + body + lane];
+    wave_copy_tile<false>(as_global(g.dst) + off, as_global(g.src) + off, n, n, lane);
   }
 }
 

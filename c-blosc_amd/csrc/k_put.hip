@@ -1,19 +1,20 @@
 // k_put.hip — rows written into compressed chunks by a device index table (include/blosc_gpu_put.h; engine.hip: engine_put).
 //
-// k_take.hip mirrored.  The chunks of a call are one array of rows (dev_types.h: TakeChunk); the chunks some valid index names are decoded
-// whole into plaintext slots, pass by pass, and the chunks of a pass are a range [c0, c1) of the call's chunks (PutChunk[c1 - c0]).
+// k_take.hip mirrored, over the same pieces (row_prims.h).  The chunks of a call are one array of rows (dev_types.h: TakeChunk); the chunks some
+// valid index names are decoded whole into plaintext slots, pass by pass, and the chunks of a pass are a range [c0, c1) of the call's chunks
+// (PutChunk[c1 - c0]).
 // Three kernels, none persistent:
 //   k_put_claim     one lane per index: the row's owner word takes the minimum of nidx - 1 - k over the indices k that name the row, so the
 //                   LAST occurrence owns it (atomicMin at L2; the words are read by the next kernel only, behind the kernel boundary);
-//   k_put_scatter   k_take_gather's lane mapping with loads and stores exchanged: index k stores rows + k * row_bytes into its row of the
-//                   slot if it owns the row - whole rows, never a mix - and answers status[k];
+//   k_put_scatter   k_take_gather's lane mapping (move_row) with source and destination exchanged: index k stores rows + k * row_bytes into
+//                   its row of the slot if it owns the row - whole rows, never a mix - and answers status[k];
 //   k_put_assemble  every chunk of the pass to its place in the new container, from the source (carried over) or from the slot the encoder
-//                   wrote (rewritten), and zeros up to the next offset: k_getitem_gather's tiles.
+//                   wrote (rewritten), and zeros up to the next offset: tiles of one wave (tile_owner, wave_copy_tile).
 // The mark kernel of a put is k_take_mark, unchanged, over a table that gives every chunk ONE block of nbytes: a flag per touched chunk.
 #pragma once
 #include "dev_types.h"
 #include "mem_prims.h"
-#include "k_take.hip"
+#include "row_prims.h"
 
 namespace bamd {
 
@@ -21,22 +22,14 @@ constexpr uint32_t PA_TILE = 16384;     // k_put_assemble: 16 steps of 64 lanes 
 constexpr int PA_THREADS = 64;
 constexpr int PA_WAVES_PER_CU = 16;
 
-#define PUT_ROW_FIRST_IN_LDS(first, in_lds)                                                                              \
-  __shared__ int64_t first[TK_LDS_CHUNKS];                                                                               \
-  const bool in_lds = nchunks <= TK_LDS_CHUNKS;                                                                          \
-  if (in_lds) {                                                                                                          \
-    for (int i = (int)threadIdx.x; i < nchunks; i += TK_THREADS) first[i] = chunks[i].row_first;                         \
-    __syncthreads();                                                                                                     \
-  }
-
 __global__ __launch_bounds__(TK_THREADS) void k_put_claim(const TakeChunk* __restrict__ chunks /*[nchunks + 1]*/, int nchunks,
                                                          const PutChunk* __restrict__ put /*[c1 - c0]*/, int c0, int c1,
                                                          const int64_t* __restrict__ index, size_t nidx, uint32_t* __restrict__ owner) {
-  PUT_ROW_FIRST_IN_LDS(first, in_lds)
+  TK_ROW_FIRST_IN_LDS(first, in_lds)
   const int64_t nrows = chunks[nchunks].row_first;
   for (size_t k = (size_t)blockIdx.x * TK_THREADS + threadIdx.x; k < nidx; k += (size_t)gridDim.x * TK_THREADS) {
     const int64_t r = index[k];
-    if (r < 0 || r >= nrows) continue;
+    if (take_no_row(r, nrows)) continue;
     const int c = (int)take_chunk_of(first, chunks, nchunks, in_lds, r);
     if (c < c0 || c >= c1) continue;      // a chunk of another pass
     const PutChunk p = put[c - c0];
@@ -45,19 +38,15 @@ __global__ __launch_bounds__(TK_THREADS) void k_put_claim(const TakeChunk* __res
   }
 }
 
-// Lane mapping, chosen by the host from row_bytes, the same for every row: 2^lanes_log2 consecutive lanes serve one index, consecutive groups
-// consecutive k - the loads of a wave cover one contiguous piece of `rows`.
-//   row_bytes <= 16: one lane per row; one load and one store of the natural width where row_bytes is 2 / 4 / 8 / 16 and both addresses are
-//                    aligned for it, byte moves otherwise;
-//   larger rows:     bytes up to the first 16-byte boundary of the row in its SLOT, aligned 16-byte stores fed by unaligned dwordx4 loads from
-//                    `rows` (mem_prims.h), bytes behind them.
+// 2^lanes_log2 consecutive lanes serve one index (row_prims.h: move_row, into the row's place in its slot), consecutive groups consecutive k -
+// the loads of a wave cover one contiguous piece of `rows`.
 // An index of a chunk that did not decode answers -1; an index outside the rows is answered where first_pass is set.
 __global__ __launch_bounds__(TK_THREADS) void k_put_scatter(const TakeChunk* __restrict__ chunks /*[nchunks + 1]*/, int nchunks,
                                                            const PutChunk* __restrict__ put /*[c1 - c0]*/, int c0, int c1,
                                                            const uint32_t* __restrict__ owner, const int64_t* __restrict__ index, size_t nidx,
                                                            uint32_t row_bytes, int lanes_log2, const uint8_t* __restrict__ rows,
                                                            int32_t* __restrict__ status /*may be nullptr*/, uint32_t* __restrict__ failed, int first_pass) {
-  PUT_ROW_FIRST_IN_LDS(first, in_lds)
+  TK_ROW_FIRST_IN_LDS(first, in_lds)
   const int64_t nrows = chunks[nchunks].row_first;
   const uint32_t G = 1u << lanes_log2, sub = threadIdx.x & (G - 1u);
   const size_t per_group = (size_t)(TK_THREADS >> lanes_log2);      // indices of one workgroup and step
@@ -66,8 +55,8 @@ __global__ __launch_bounds__(TK_THREADS) void k_put_scatter(const TakeChunk* __r
     const size_t k = k0 + (threadIdx.x >> lanes_log2);
     if (k >= nidx) continue;
     const int64_t r = index[k];
-    if (r < 0 || r >= nrows) {      // no row of any chunk: answered once
-      if (first_pass && sub == 0) { if (status) status[k] = -1; nfail++; }
+    if (take_no_row(r, nrows)) {
+      if (first_pass && sub == 0) take_fail(status, k, -1, nfail);
       continue;
     }
     const int c = (int)take_chunk_of(first, chunks, nchunks, in_lds, r);
@@ -75,66 +64,31 @@ __global__ __launch_bounds__(TK_THREADS) void k_put_scatter(const TakeChunk* __r
     const PutChunk p = put[c - c0];
     if (!p.slot) continue;
     if (p.status < 0) {                   // the chunk did not decode: it is carried over as it is
-      if (sub == 0) { if (status) status[k] = -1; nfail++; }
+      if (sub == 0) take_fail(status, k, -1, nfail);
       continue;
     }
     const uint64_t row = (uint64_t)(r - chunks[c].row_first);
-    if (owner[p.owner_first + row] == (uint32_t)(nidx - 1 - k)) {
-      const gu8* s = as_global(rows) + k * (size_t)row_bytes;
-      gu8* d = as_global(p.slot) + row * row_bytes;
-      if (row_bytes <= 16u) {
-        const uint32_t a = (uint32_t)(uintptr_t)s | (uint32_t)(uintptr_t)d;
-        if (row_bytes == 16u && !(a & 15u)) g_st16(d, g_ld16(s));
-        else if (row_bytes == 8u && !(a & 7u)) g_st8(d, g_ld8(s));
-        else if (row_bytes == 4u && !(a & 3u)) g_st4(d, g_ld4(s));
-        else if (row_bytes == 2u && !(a & 1u)) g_st2(d, g_ld2(s));
-        else for (uint32_t i = 0; i < row_bytes; i++) d[i] = s[i];
-      } else {
-        const uint32_t head = (16u - ((uint32_t)(uintptr_t)d & 15u)) & 15u;      // < row_bytes
-        const uint32_t body = (row_bytes - head) & ~15u, tail = row_bytes - head - body;
-        for (uint32_t i = sub; i < head; i += G) d[i] = s[i];
-        for (uint32_t o = sub * 16u; o < body; o += G * 16u) g_st16(d + head + o, g_ld16(s + head + o));
-        for (uint32_t i = sub; i < tail; i += G) d[head + body + i] = s[head + body + i];
-      }
-    }
+    if (owner[p.owner_first + row] == (uint32_t)(nidx - 1 - k))
+      move_row(as_global(p.slot) + row * row_bytes, as_global(rows) + k * (size_t)row_bytes, row_bytes, sub, G);
     if (sub == 0 && status) status[k] = (int32_t)row_bytes;      // winner or not: the row holds what the last occurrence brought
   }
   if (nfail) atomicAdd(failed, nfail);
 }
 
 // One-wave workgroups over tiles of PA_TILE bytes of the pass's chunks: copy c covers nbytes + pad bytes of the container - the chunk, then zeros -
-// and tile_first[c] is the number of tiles in front of it (a chunk that ends behind the caller's destsize has none).  Bytes up to the first
-// 16-byte boundary of the DESTINATION, aligned 16-byte stores fed by unaligned loads, bytes behind them; nothing beyond src + nbytes is read.
+// and tile_first[c] is the number of tiles in front of it (a chunk that ends behind the caller's destsize has none).
 __global__ __launch_bounds__(PA_THREADS) void k_put_assemble(const PutCopy* __restrict__ copies, const uint32_t* __restrict__ tile_first /*[ncopies + 1]*/, int ncopies) {
   const uint32_t lane = threadIdx.x;
   const uint32_t ntiles = tile_first[ncopies];
   for (uint32_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    uint32_t c = 0, hi = (uint32_t)ncopies;      // tile_first[c] <= t < tile_first[hi]; of equal entries (copies without tiles) the last one
-    while (hi - c > 1u) {
-      const uint32_t mid = (c + hi) >> 1;
-      if (tile_first[mid] <= t) c = mid; else hi = mid;
-    }
+    const uint32_t c = tile_owner(tile_first, ncopies, t);
     const PutCopy g = copies[c];
     const uint32_t total = g.nbytes + g.pad, off = (t - tile_first[c]) * PA_TILE;
     if (off >= total) continue;
     const uint32_t n = total - off < PA_TILE ? total - off : PA_TILE;
     const uint32_t live = off >= g.nbytes ? 0u : (g.nbytes - off < n ? g.nbytes - off : n);      // bytes of the tile that come from src
-    const gu8* s = as_global(g.src) + off;
-    gu8* d = as_global(g.dst) + off;
-    uint32_t head = (uint32_t)((16u - ((uint32_t)(uintptr_t)d & 15u)) & 15u);
-    if (head > n) head = n;
-    const uint32_t body = (n - head) & ~15u, tail = n - head - body;
-    if (lane < head) d[lane] = lane < live ? s[lane] : (uint8_t)0;
-    for (uint32_t k = lane * 16u; k < body; k += PA_THREADS * 16u) {
-      const uint32_t at = head + k;
-      if (at + 16u <= live) g_st16(d + at, g_ld16(s + at));
-      else if (at >= live) g_st16(d + at, make_uint4(0u, 0u, 0u, 0u));
-      else for (uint32_t i = 0; i < 16u; i++) d[at + i] = at + i < live ? s[at + i] : (uint8_t)0;      // the chunk's last bytes and the first zeros
-    }
-    if (lane < tail) { const uint32_t at = head + body + lane; d[at] = at < live ? s[at] : (uint8_t)0; }
+    wave_copy_tile<true>(as_global(g.dst) + off, as_global(g.src) + off, n, live, lane);
   }
 }
-
-#undef PUT_ROW_FIRST_IN_LDS
 
 }  // namespace bamd

@@ -1,8 +1,8 @@
 // k_where.hip — the rows of compressed chunks whose field satisfies a predicate (include/blosc_gpu_where.h; engine.hip: engine_where).
 //
 // The chunks of a pass are decoded whole into plaintext slots (dev_types.h: WhereChunk).  A pass is cut into tiles of WH_TILE rows that never
-// straddle a chunk; tile_first[c] is the number of tiles in front of chunk c of the pass, and a tile finds its chunk by bisection, as
-// k_put_assemble's tiles do.  Three kernels per pass, and no workgroup ever waits for another one:
+// straddle a chunk; tile_first[c] is the number of tiles in front of chunk c of the pass, and a tile finds its chunk by bisection
+// (row_prims.h: tile_owner).  Three kernels per pass, and no workgroup ever waits for another one:
 //   k_where_mark    one lane per row: the field's key against the constant's (dev_types.h: WherePred), one __ballot word per 64 rows, the
 //                   tile's count, and that count added to its chunk's counter (an integer atomic at L2: the sum does not depend on the order);
 //   k_where_scan    ONE workgroup: the exclusive prefix of the pass's tile counts, started at the call's running total, which lives in
@@ -14,48 +14,11 @@
 #pragma once
 #include "dev_types.h"
 #include "mem_prims.h"
+#include "row_prims.h"      // the WH_* tile constants, tile_owner, where_field, where_test
 
 namespace bamd {
 
-constexpr int WH_THREADS = 256;
-constexpr int WH_WAVES = WH_THREADS / 64;
-constexpr int WH_STEPS = 4;                                  // steps of WH_THREADS rows per tile
-constexpr uint32_t WH_TILE = WH_THREADS * WH_STEPS;          // rows of a tile
-constexpr int WH_WORDS = WH_WAVES * WH_STEPS;                // mask words of a tile: word s * WH_WAVES + w holds rows [64 (s * WH_WAVES + w), + 64)
-constexpr int WH_WAVES_PER_CU = 32;                          // the grid: a choice, not a residency
 constexpr int WH_SCAN_THREADS = 1024;
-
-// the chunk of tile t, t < tile_first[nchunks]: the last c with tile_first[c] <= t (chunks without tiles share their successor's entry)
-__device__ __forceinline__ uint32_t where_chunk_of(const uint32_t* __restrict__ tile_first, int nchunks, uint32_t t) {
-  uint32_t c = 0, hi = (uint32_t)nchunks;
-  while (hi - c > 1u) {
-    const uint32_t mid = (c + hi) >> 1;
-    if (tile_first[mid] <= t) c = mid; else hi = mid;
-  }
-  return c;
-}
-
-// the field at p, whatever its address (mem_prims.h: unaligned loads)
-__device__ __forceinline__ uint64_t where_field(const gu8* p, uint32_t bytes) {
-  if (bytes == 1u) return (uint64_t)p[0];
-  if (bytes == 2u) return (uint64_t)g_ld2(p);
-  if (bytes == 4u) return (uint64_t)g_ld4(p);
-  return g_ld8(p);
-}
-
-__device__ __forceinline__ bool where_test(const WherePred& q, uint64_t v) {
-  bool nan;
-  const int64_t k = where_key(v, q.kind, q.bytes, q.inf, &nan);
-  if (nan || q.nan) return q.op == 1;
-  switch (q.op) {
-    case 0: return k == q.key;
-    case 1: return k != q.key;
-    case 2: return k < q.key;
-    case 3: return k <= q.key;
-    case 4: return k > q.key;
-    default: return k >= q.key;
-  }
-}
 
 // masks [ntiles * WH_WORDS], tile_count [ntiles]: of this pass, every word written.  chunk_count: the counters of the pass's chunks.
 __global__ __launch_bounds__(WH_THREADS) void k_where_mark(const WhereChunk* __restrict__ chunks /*[nchunks]*/, const uint32_t* __restrict__ tile_first /*[nchunks + 1]*/,
@@ -66,7 +29,7 @@ __global__ __launch_bounds__(WH_THREADS) void k_where_mark(const WhereChunk* __r
   const uint32_t ntiles = tile_first[nchunks];
   uint32_t held = 0, held_chunk = 0;      // thread 0: matches of held_chunk not yet added to its counter - one atomic per chunk the workgroup meets, not per tile
   for (uint32_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const uint32_t c = where_chunk_of(tile_first, nchunks, t);
+    const uint32_t c = tile_owner(tile_first, nchunks, t);
     const WhereChunk ch = chunks[c];
     const uint32_t row0 = (t - tile_first[c]) * WH_TILE;
     const gu8* base = as_global(ch.slot) + q.offset;
@@ -133,7 +96,7 @@ __global__ __launch_bounds__(WH_THREADS) void k_where_write(const WhereChunk* __
   for (uint32_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
     const uint64_t tile_at = tile_base[t];
     if (!tile_count[t] || tile_at >= capacity) continue;      // (the same for the whole workgroup: no barrier is left out by some)
-    const uint32_t c = where_chunk_of(tile_first, nchunks, t);
+    const uint32_t c = tile_owner(tile_first, nchunks, t);
     const int64_t row0 = chunks[c].row_first + (int64_t)(t - tile_first[c]) * WH_TILE;
     if (tid < (uint32_t)WH_WORDS) word_count[tid] = (uint32_t)__builtin_popcountll(masks[(size_t)t * WH_WORDS + tid]);
     __syncthreads();

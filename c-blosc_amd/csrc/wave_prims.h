@@ -206,11 +206,15 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
   for (int m = 32; m >= 1; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m, 64);
   return v;
 }
+// lane l ^ m's 64-bit value: the cross-lane builtins carry 32 bits, so it moves as two halves
+__device__ __forceinline__ uint64_t wave_xor_u64(uint64_t v, int m) {
+  const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m, 64);
+  return ((uint64_t)hi << 32) | lo;
+}
 // the smallest of the lanes' 64-bit keys, in every lane (k_encode.hip: k_candidate_select)
 __device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
   for (int m = 32; m >= 1; m >>= 1) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m, 64);
-    const uint64_t o = ((uint64_t)hi << 32) | lo;
+    const uint64_t o = wave_xor_u64(v, m);
     v = o < v ? o : v;
   }
   return v;

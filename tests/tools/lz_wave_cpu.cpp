@@ -5,6 +5,7 @@
 //   /opt/rocm/lib/llvm/bin/clang++ -std=c++17 -O1 -shared -fPIC -I tests/tools/wave_emu -I c-blosc_amd/csrc -x c++ \
 //       tests/tools/lz_wave_cpu.cpp -o tests/tools/liblz_wave_cpu.so
 #define WAVE_EMU_IMPLEMENTATION
+#include <sys/mman.h>
 #include <hip/hip_runtime.h>
 #include "dev_types.h"
 #include "k_filters.hip"
@@ -235,4 +236,49 @@ extern "C" int emu_lz_encode(int kind, const uint8_t* src, int n, uint8_t* dst, 
   if (rendezvous) *rendezvous = wave_emu::last_rendezvous();
   free(j.tab); free(j.seqbuf);
   return (int)j.result;
+}
+
+// ---- the pieces the row kernels and k_getitem_gather share (row_prims.h), each on its own: tests/test_wave_emu_row_prims.py ----
+namespace {
+// the n readable bytes of s, copied so that they END at an unreadable page: a load beyond them is a fault, which wave_emu reports
+struct Guarded {
+  uint8_t* map; size_t len; const uint8_t* s;
+  Guarded(const uint8_t* src, size_t n) {
+    const size_t page = (size_t)sysconf(_SC_PAGESIZE), body = (n / page + 1) * page;
+    len = body + page;
+    map = (uint8_t*)mmap(nullptr, len, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
+    if (map == (uint8_t*)MAP_FAILED || mprotect(map + body, page, PROT_NONE)) abort();
+    memcpy(map + body - n, src, n);
+    s = map + body - n;
+  }
+  ~Guarded() { munmap(map, len); }
+};
+struct RJob { int what; const uint32_t* tile_first; int n; uint32_t* owner; uint8_t* d; const uint8_t* s; uint32_t bytes, live, G; };
+void row_body(int lane, void* arg) {
+  RJob* j = (RJob*)arg;
+  using namespace bamd;
+  if (j->what == 0) for (uint32_t t = (uint32_t)lane; t < j->tile_first[j->n]; t += 64u) j->owner[t] = tile_owner(j->tile_first, j->n, t);
+  else if (j->what == 1) { if ((uint32_t)lane < j->G) move_row((gu8*)j->d, (const gu8*)j->s, j->bytes, (uint32_t)lane, j->G); }
+  else if (j->what == 2) wave_copy_tile<false>((gu8*)j->d, (const gu8*)j->s, j->bytes, j->live, (uint32_t)lane);
+  else wave_copy_tile<true>((gu8*)j->d, (const gu8*)j->s, j->bytes, j->live, (uint32_t)lane);
+}
+}  // namespace
+// owner_out[t] = tile_owner(tile_first, n, t) for every t < tile_first[n]
+extern "C" void emu_tile_owner(const uint32_t* tile_first, int n, uint32_t* owner_out) {
+  RJob j = {0, tile_first, n, owner_out, nullptr, nullptr, 0, 0, 0};
+  wave_emu::run(row_body, &j);
+}
+// one row of row_bytes bytes from s to d by a group of 2^lanes_log2 lanes (a group of 128 is two wavefronts).  guard: s is read from a copy
+// that ends at an unreadable page
+extern "C" void emu_move_row(uint8_t* d, const uint8_t* s, unsigned row_bytes, int lanes_log2, int guard) {
+  Guarded g(s, guard ? row_bytes : 0);
+  RJob j = {1, nullptr, 0, nullptr, d, guard ? g.s : s, row_bytes, 0, 1u << lanes_log2};
+  wave_emu::run_group(j.G > 64u ? (int)j.G : 64, row_body, &j);
+}
+// a tile of n bytes from s to d by one wave; zeros: the first `live` bytes from s, zeros behind them.  guard: as above, over the bytes
+// the copy may read (n, or live)
+extern "C" void emu_copy_tile(int zeros, uint8_t* d, const uint8_t* s, unsigned n, unsigned live, int guard) {
+  Guarded g(s, guard ? (zeros ? live : n) : 0);
+  RJob j = {zeros ? 3 : 2, nullptr, 0, nullptr, d, guard ? g.s : s, n, live, 0};
+  wave_emu::run(row_body, &j);
 }

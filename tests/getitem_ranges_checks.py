@@ -103,17 +103,20 @@ def odd_slots(widths):
     return at, off + 64
 
 
-def check_batch(pkgmod, lib, mem, oracle, chunks, ranges, what=""):
+def check_batch(pkgmod, lib, mem, oracle, chunks, ranges, what="", stream=None, keep=None):
     """one blosc_gpu_getitem_batch over `ranges` = (chunk, start, nitems) triples: every result and every byte the oracle's; destinations at odd
-    offsets inside one buffer of sentinels; every byte outside the slices and every byte of a failed range's slot still the sentinel"""
+    offsets inside one buffer of sentinels; every byte outside the slices and every byte of a failed range's slot still the sentinel.
+    stream: the caller's stream (default the NULL stream); keep: a dict that receives the results and the whole buffer as the call left them"""
     want = expected(oracle, chunks, ranges)
     at, total = odd_slots(slot_widths(chunks, ranges))
     assert all(a % 2 == 1 for a in at)
     dev = [mem.put(c) for c in chunks]
     out, base = mem.filled(total, SENTINEL)
     b = pkgmod.ItemRanges(ranges, lib=lib)
-    assert b.batch([p for _, p in dev], [base + a for a in at]) == 0, what
+    assert b.batch([p for _, p in dev], [base + a for a in at], stream=stream) == 0, what
     got = b.results()
+    if keep is not None:
+        keep.update(results=np.array(got, np.int64), bytes=mem.get(out)[:total].copy())
     exp = np.full(total, SENTINEL, np.uint8)
     for a, (r, data) in zip(at, want):
         if r > 0: exp[a:a + r] = data

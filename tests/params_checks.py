@@ -100,7 +100,7 @@ class Calls:
         return b.offsets(), b.results(), self.mem.get(h)[:destsize + GUARD]
 
     # ---- the calls with parameters per chunk ----
-    def new_batch(self, hosts, rows, caps=None, dest_at=None, src=None):
+    def new_batch(self, hosts, rows, caps=None, dest_at=None, src=None, stream=None):
         """one blosc_gpu_compress_batch_params into one sentinel-filled buffer, chunk i at dest_at[0][i] (default: guarded slots wide
         enough for the whole chunk whatever caps[i]) -> (results, image, offsets of the destinations)"""
         n, sizes = len(hosts), [h.size for h in hosts]
@@ -109,22 +109,22 @@ class Calls:
         h, base = self.mem.filled(total, SENTINEL)
         b = self.pkg.DeviceBatch(src if src is not None else self.src(hosts), sizes, [base + a for a in at], caps)
         for k in range(n): b.res[k] = -777
-        assert b.compress_params(rows, lib=self.lib) == 0
+        assert b.compress_params(rows, stream=stream, lib=self.lib) == 0
         return b.results(), self.mem.get(h)[:total], at
 
-    def new_packed(self, hosts, rows, align, destsize):
+    def new_packed(self, hosts, rows, align, destsize, stream=None):
         b = self.pkg.PackedBatch(len(hosts), lib=self.lib)
         h, base = self.mem.filled(destsize + GUARD, FILL)
-        assert b.compress_params(self.src(hosts), [x.size for x in hosts], rows, base if destsize else None, destsize, align) == 0
+        assert b.compress_params(self.src(hosts), [x.size for x in hosts], rows, base if destsize else None, destsize, align, stream=stream) == 0
         return b.offsets(), b.results(), self.mem.get(h)[:destsize + GUARD]
 
-    def unpack(self, buf, off, total):
+    def unpack(self, buf, off, total, stream=None):
         """the container through the existing blosc_gpu_decompress_packed -> (results, plain bytes)"""
         n = len(off) - 1
         b = self.pkg.PackedBatch(n, lib=self.lib)
         hc, pc = self.mem.put(buf)
         ho, po = self.mem.filled(total + GUARD, FILL)
-        assert b.decompress(pc, buf.size, off, po, total) == 0
+        assert b.decompress(pc, buf.size, off, po, total, stream=stream) == 0
         out = self.mem.get(ho)
         assert np.all(out[total:total + GUARD] == FILL)
         return b.results(), out[:total]
@@ -151,19 +151,24 @@ def check_one_setting(calls, hosts, s, align=16):
 
 
 # ---- case 2 ----
-def check_every_setting_in_one_batch(calls, hosts, settings, ref_chunks, oracle, ref, aligns=(1, 16, 4096)):
+def check_every_setting_in_one_batch(calls, hosts, settings, ref_chunks, oracle, ref, aligns=(1, 16, 4096), stream=None, keep=None):
+    """stream: the caller's stream of the new calls (default the NULL stream); keep: a dict that receives what they gave"""
     order = interleave(hosts, settings)
     batch = [hosts[d] for d, _ in order]
     rows = [calls.row(settings[s]) for _, s in order]
     want = [ref_chunks[s][d] for d, s in order]
     assert all(settings[order[i][1]] is not settings[order[i + 1][1]] for i in range(len(order) - 1))
-    res, image, at = calls.new_batch(batch, rows)
+    res, image, at = calls.new_batch(batch, rows, stream=stream)
+    if keep is not None:
+        keep.update(batch_cbytes=np.array(res, np.int64), batch_image=image)
     assert res == [c.size for c in want], ("cbytes", [(i, r, c.size) for i, (r, c) in enumerate(zip(res, want)) if r != c.size][:6])
     check_written(image, at, want, "every deterministic setting, batch form", [h.size + 16 for h in batch])
     total = sum(h.size for h in batch)
     for align in aligns:
         need = host_offsets([c.size for c in want], align)[-1]
-        off, cb, buf = calls.new_packed(batch, rows, align, need)
+        off, cb, buf = calls.new_packed(batch, rows, align, need, stream=stream)
+        if keep is not None:
+            keep.update({f"packed_offsets_align{align}": np.array(off, np.int64), f"packed_cbytes_align{align}": np.array(cb, np.int64), f"packed_container_align{align}": buf})
         check_container(buf, off, cb, want, align, need, ("every deterministic setting", align))
         assert off == host_offsets(cb, align)
         if align == aligns[0]:
@@ -171,7 +176,7 @@ def check_every_setting_in_one_batch(calls, hosts, settings, ref_chunks, oracle,
             for c, (d, s) in zip(chunks, order):
                 assert header(c)["typesize"] == settings[s].T
             check_chunks_decode(chunks, batch, oracle, ref)
-            r, out = calls.unpack(buf[:need], off, total)
+            r, out = calls.unpack(buf[:need], off, total, stream=stream)
             assert r == [h.size for h in batch] and np.array_equal(out, np.concatenate(batch)), "blosc_gpu_decompress_packed cannot read it back"
 
 

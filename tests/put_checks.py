@@ -77,8 +77,8 @@ def bound(chunks, align):
     return sum(-(-(header(c)["nbytes"] + 16) // align) * align for c in chunks)
 
 
-def run_put(pkgmod, lib, mem, source, chunks, row_bytes, index, rows, params, align=1, offset=0, with_status=True, destsize=None):
-    """One call.  `rows` lies `offset` bytes behind a 16-byte boundary, dest (destsize bytes, default the bound) inside a buffer of sentinels,
+def run_put(pkgmod, lib, mem, source, chunks, row_bytes, index, rows, params, align=1, offset=0, with_status=True, destsize=None, stream=None):
+    """One call (stream: the caller's stream, default the NULL stream).  `rows` lies `offset` bytes behind a 16-byte boundary, dest (destsize bytes, default the bound) inside a buffer of sentinels,
     the status table between sentinel words.  Returns (answer, dest bytes, status or None, the RowPut); the sentinels around dest and status
     and the bytes of the source are asserted here"""
     idx = np.ascontiguousarray(np.asarray(index, np.int64))
@@ -95,7 +95,7 @@ def run_put(pkgmod, lib, mem, source, chunks, row_bytes, index, rows, params, al
     before = [mem.get(h).copy() for h, _ in source.keep] if not source.packed else mem.get(source.keep[0]).copy()
     put = pkgmod.RowPut(row_bytes, lib=lib)
     args = (index_ptr if nidx else None, nidx, (rows_base + 16 + offset) if nidx else None, params, base + at, cap, align, (st_base + 16) if with_status else None)
-    rc = put.packed(source.container, source.size, source.offsets, *args) if source.packed else put.batch(source.ptrs, *args)
+    rc = put.packed(source.container, source.size, source.offsets, *args, stream=stream) if source.packed else put.batch(source.ptrs, *args, stream=stream)
     buf = mem.get(out)
     assert np.all(buf[:at] == SENTINEL) and np.all(buf[at + cap:] == SENTINEL), "bytes outside dest were written"
     status = None
@@ -109,11 +109,16 @@ def run_put(pkgmod, lib, mem, source, chunks, row_bytes, index, rows, params, al
     return rc, buf[at:at + cap].copy(), status, put
 
 
-def check_put(pkgmod, lib, mem, oracle, source, chunks, row_bytes, index, params, align=1, offset=0, with_status=True, destsize=None, seed=7, what=""):
-    """everything include/blosc_gpu_put.h says about one call that passes the census.  Returns (dest bytes, the RowPut, the expected plaintexts)"""
+def check_put(pkgmod, lib, mem, oracle, source, chunks, row_bytes, index, params, align=1, offset=0, with_status=True, destsize=None, seed=7, what="",
+              stream=None, keep=None):
+    """everything include/blosc_gpu_put.h says about one call that passes the census.  Returns (dest bytes, the RowPut, the expected plaintexts).
+    keep: a dict that receives what the call gave (dest, status and the host tables), for callers that compare two calls"""
     rows = new_rows(len(index), row_bytes, seed)
     want_plain, want_rew, want_status = expected(oracle, chunks, row_bytes, index, rows)
-    rc, dest, status, put = run_put(pkgmod, lib, mem, source, chunks, row_bytes, index, rows, params, align, offset, with_status, destsize)
+    rc, dest, status, put = run_put(pkgmod, lib, mem, source, chunks, row_bytes, index, rows, params, align, offset, with_status, destsize, stream)
+    if keep is not None:
+        keep.update(dest=dest, status=status, offsets=np.array(put.offsets(), np.int64), cbytes=np.array(put.results(), np.int64),
+                    rewritten=np.array(put.rewritten(), np.int64), chunk_rows=np.array(put.chunk_rows(), np.int64), failed=np.array([put.failed()], np.int64))
     what = (what, "row_bytes", row_bytes, "offset", offset, "align", align, "status" if with_status else "no status")
     cap = dest.size
     assert rc == 0, (what, rc)

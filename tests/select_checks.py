@@ -65,7 +65,7 @@ class Calls(pc.Calls):
         super().__init__(pkgmod, lib, mem, blocksize)
         pkgmod.declare_select(lib)
 
-    def select_batch(self, hosts, first, rows, caps=None):
+    def select_batch(self, hosts, first, rows, caps=None, stream=None):
         """one blosc_gpu_compress_batch_select into guarded slots of one sentinel-filled buffer -> (results, choices, candidate answers,
         image, offsets of the destinations)"""
         n, sizes = len(hosts), [h.size for h in hosts]
@@ -74,14 +74,14 @@ class Calls(pc.Calls):
         h, base = self.mem.filled(total, SENTINEL)
         b = self.pkg.DeviceBatch(self.src(hosts), sizes, [base + a for a in at], caps)
         for k in range(n): b.res[k] = -777
-        assert b.compress_select(first, rows, lib=self.lib) == 0
+        assert b.compress_select(first, rows, stream=stream, lib=self.lib) == 0
         return b.results(), b.choices(), b.candidate_results(), self.mem.get(h)[:total], at
 
-    def select_packed(self, hosts, first, rows, align, destsize, sizing=False):
+    def select_packed(self, hosts, first, rows, align, destsize, sizing=False, stream=None):
         """one blosc_gpu_compress_packed_select (sizing: dest NULL, destsize 0) -> (offsets, results, choices, candidate answers, buffer)"""
         b = self.pkg.PackedBatch(len(hosts), lib=self.lib)
         h, base = self.mem.filled(destsize + GUARD, FILL)
-        assert b.compress_select(self.src(hosts), [x.size for x in hosts], first, rows, None if sizing else base, 0 if sizing else destsize, align) == 0
+        assert b.compress_select(self.src(hosts), [x.size for x in hosts], first, rows, None if sizing else base, 0 if sizing else destsize, align, stream=stream) == 0
         return b.offsets(), b.results(), b.choices(), b.candidate_results(), self.mem.get(h)[:destsize + GUARD]
 
 
@@ -111,22 +111,28 @@ def check_inputs_of_the_first_check(hosts, settings, ref):
     return choice
 
 
-def check_deterministic(calls, hosts, settings, ref, oracle, reflib, aligns=(1, 16)):
+def check_deterministic(calls, hosts, settings, ref, oracle, reflib, aligns=(1, 16), stream=None, keep=None):
+    """stream: the caller's stream of the select calls (default the NULL stream); keep: a dict that receives what they gave"""
     n, S = len(hosts), len(settings)
     want_choice, want = winners(ref, n)
     first, rows = tables([[calls.row(s) for s in settings]] * n)
     flat = [ref[s][d].size for d in range(n) for s in range(S)]
-    res, choice, cand, image, at = calls.select_batch(hosts, first, rows)
+    res, choice, cand, image, at = calls.select_batch(hosts, first, rows, stream=stream)
+    if keep is not None:
+        keep.update(batch_cbytes=np.array(res, np.int64), batch_choice=np.array(choice, np.int64), batch_candidates=np.array(cand, np.int64), batch_image=image)
     assert cand == flat, ("candidate answers", [(e, a, b) for e, (a, b) in enumerate(zip(cand, flat)) if a != b][:6])
     assert choice == want_choice and res == [c.size for c in want], (choice, want_choice, res)
     check_written(image, at, want, "deterministic candidates, batch form", [h.size + 16 for h in hosts])
     # the rows of the 0-byte and the 100-byte chunk through the _params call: the same chunks
     for d in (EMPTY, TINY):
-        r1, im1, at1 = calls.new_batch([hosts[d]], [rows[first[d]]])
+        r1, im1, at1 = calls.new_batch([hosts[d]], [rows[first[d]]], stream=stream)
         assert r1 == [res[d]] and np.array_equal(im1[at1[0]:at1[0] + r1[0]], image[at[d]:at[d] + res[d]])
     for align in aligns:
         need = host_offsets([c.size for c in want], align)[-1]
-        off, cb, choice, cand, buf = calls.select_packed(hosts, first, rows, align, need)
+        off, cb, choice, cand, buf = calls.select_packed(hosts, first, rows, align, need, stream=stream)
+        if keep is not None:
+            keep.update({f"packed_offsets_align{align}": np.array(off, np.int64), f"packed_cbytes_align{align}": np.array(cb, np.int64), f"packed_container_align{align}": buf,
+                         f"packed_choice_align{align}": np.array(choice, np.int64), f"packed_candidates_align{align}": np.array(cand, np.int64)})
         assert cand == flat and choice == want_choice, (align, choice, want_choice)
         check_container(buf, off, cb, want, align, need, ("deterministic candidates, packed form", align))
     check_chunks_decode([buf[off[d]:off[d] + cb[d]] for d in range(n)], hosts, oracle, reflib)

@@ -163,10 +163,10 @@ class TakeSource:
             self.container, self.size, self.offsets = self.keep[1], int(container.size), [int(o) for o in offsets]
         self.packed = chunks is None
 
-    def call(self, take, index_ptr, nidx, dest, status):
+    def call(self, take, index_ptr, nidx, dest, status, stream=None):
         if self.packed:
-            return take.packed(self.container, self.size, self.offsets, index_ptr, nidx, dest, status)
-        return take.batch(self.ptrs, index_ptr, nidx, dest, status)
+            return take.packed(self.container, self.size, self.offsets, index_ptr, nidx, dest, status, stream=stream)
+        return take.batch(self.ptrs, index_ptr, nidx, dest, status, stream=stream)
 
 
 def pack_container(chunks, align=256):
@@ -182,8 +182,8 @@ def pack_container(chunks, align=256):
 GUARD = 48
 
 
-def run_take(pkgmod, lib, mem, source, row_bytes, index, offset=0, with_status=True):
-    """One call.  dest lies `offset` bytes behind a 16-byte boundary inside a buffer of sentinels, the status table between sentinel words.
+def run_take(pkgmod, lib, mem, source, row_bytes, index, offset=0, with_status=True, stream=None):
+    """One call (stream: the caller's stream, default the NULL stream).  dest lies `offset` bytes behind a 16-byte boundary inside a buffer of sentinels, the status table between sentinel words.
     Returns (answer, dest bytes [nidx, row_bytes], status [nidx] or None, chunk_rows, failed); the sentinels around both are asserted here"""
     idx = np.ascontiguousarray(np.asarray(index, np.int64))
     nidx = int(idx.size)
@@ -194,7 +194,7 @@ def run_take(pkgmod, lib, mem, source, row_bytes, index, offset=0, with_status=T
     at = (-base) % 16 + 16 + offset
     st_h, st_base = (mem.filled(4 * (nidx + 8), SENTINEL) if with_status else (None, 0))
     take = pkgmod.RowTake(row_bytes, lib=lib)
-    rc = source.call(take, index_ptr if nidx else None, nidx, (base + at) if nidx else None, (st_base + 16) if with_status else None)
+    rc = source.call(take, index_ptr if nidx else None, nidx, (base + at) if nidx else None, (st_base + 16) if with_status else None, stream)
     buf = mem.get(out)[:total + 2 * GUARD]
     assert np.all(buf[:at] == SENTINEL) and np.all(buf[at + total:] == SENTINEL), "bytes outside dest were written"
     status = None
@@ -206,10 +206,13 @@ def run_take(pkgmod, lib, mem, source, row_bytes, index, offset=0, with_status=T
     return rc, buf[at:at + total].reshape(nidx, row_bytes).copy(), status, take.chunk_rows(), take.failed()
 
 
-def check_take(pkgmod, lib, mem, source, chunks, rows_plain, row_bytes, index, offset=0, with_status=True, row_code=None, what=""):
-    """the bytes, the status table, failed_out and chunk_rows_out of one call; rows with a negative status still hold the sentinel"""
+def check_take(pkgmod, lib, mem, source, chunks, rows_plain, row_bytes, index, offset=0, with_status=True, row_code=None, what="", stream=None, keep=None):
+    """the bytes, the status table, failed_out and chunk_rows_out of one call; rows with a negative status still hold the sentinel.
+    keep: a dict that receives what the call gave (dest, status, chunk_rows, failed), for callers that compare two calls"""
     want_status, want = expected(rows_plain, row_bytes, index, row_code)
-    rc, got, status, rows, failed = run_take(pkgmod, lib, mem, source, row_bytes, index, offset, with_status)
+    rc, got, status, rows, failed = run_take(pkgmod, lib, mem, source, row_bytes, index, offset, with_status, stream)
+    if keep is not None:
+        keep.update(dest=got, status=status, chunk_rows=np.array(rows, np.int64), failed=np.array([failed], np.int64))
     what = (what, "row_bytes", row_bytes, "offset", offset, "status" if with_status else "no status")
     assert rc == 0, (what, rc)
     assert rows == chunk_rows(chunks, row_bytes), (what, rows)

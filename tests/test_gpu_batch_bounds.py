@@ -1,6 +1,7 @@
 """blosc_gpu_compress_batch / blosc_gpu_decompress_batch on the device the way no other test calls them (include/blosc_gpu.h): a destsize
 of its own per chunk, from 0 to ample; sentinels in front of and behind every destination; caller addresses of every residue modulo 16 on
-both sides - and the packed, getitem-ranges, checksum and cbuffer-sizes calls on a stream of their own.  The checkers are
+both sides - and the packed, take, put, per-chunk-parameter, select, getitem-ranges, checksum and cbuffer-sizes calls on a stream of their
+own.  The checkers are
 tests/batch_bounds_checks.py's (tests/test_emu_batch_bounds.py runs them on the emulated library); shapes: 40 KiB + 24 bytes where the
 setting's blocks are not split, 5 x 64 KiB + 24 where they are, blocksize 8192 forced."""
 import ctypes as C
@@ -9,11 +10,16 @@ import numpy as np
 import pytest
 
 import checksum_checks as cs
+import concurrent_checks as cc
+import params_checks as pc
+import select_checks as sc
 from batch_bounds_checks import (DETERMINISTIC, OTHERS, SHUFFLES, TYPESIZES, check_capacity, check_odd_compress, check_odd_decompress, check_policy,
                                  compress_call, guarded_slots, is_split, mixed_hosts, stock_chunks)
 from getitem_ranges_checks import BIG, BLOCKSIZE, SENTINEL, SMALL, TorchMem, chunk_ranges, expected, odd_slots, plain, prefix, slot_widths
 from helpers import orc_compress, ptr
 from packed_checks import FILL, check_container, host_offsets
+from put_checks import check_put
+from take_checks import check_take
 
 pytestmark = pytest.mark.gpu
 ROWS = [(c, l, True) for c, l in DETERMINISTIC] + [(c, l, False) for c, l in OTHERS]
@@ -95,6 +101,104 @@ def stock_container(oracle):
               orc_compress(oracle, plain(SMALL, seed=5), 4, 5, 2, "lz4", blocksize=BLOCKSIZE)[1], orc_compress(oracle, rng.integers(0, 256, 9000, dtype=np.uint8), 4, 5, 1, "lz4")[1],
               orc_compress(oracle, plain(100), 4, 5, 1, "lz4")[1], orc_compress(oracle, plain(0), 4, 5, 1, "lz4")[1]]
     return chunks, container_of(chunks)
+
+
+class SideMem:
+    """the checkers' `mem` for a call on a side stream: everything happens on that stream and nothing waits for it.  put() enqueues the copy
+    from pinned memory into a zeroed buffer, filled() the fill; behind side_feed's producer both are still on their way when the call is
+    made.  get() waits for the stream and reads the device - except the first get() of a buffer that was put() and never read: that one
+    answers the bytes on their way (put_checks.run_put looks at its sources before the call), and the next one reads the device"""
+    def __init__(self, stream):
+        import torch
+        self.torch, self.s, self.dev, self.pinned, self.on_their_way = torch, stream, torch.device("cuda:0"), [], {}
+
+    def put(self, a):
+        a = np.ascontiguousarray(a).copy()
+        with self.torch.cuda.stream(self.s):
+            t = self.torch.zeros(max(a.size, 1), dtype=self.torch.uint8, device=self.dev)
+            if a.size:
+                self.pinned.append(self.torch.from_numpy(a).pin_memory())
+                t[:a.size].copy_(self.pinned[-1], non_blocking=True)
+        self.on_their_way[id(t)] = (t, a if a.size else np.zeros(1, np.uint8))      # (holding t: its id stays its own)
+        return t, t.data_ptr()
+
+    def filled(self, n, value):
+        with self.torch.cuda.stream(self.s):
+            t = self.torch.full((max(n, 1),), value, dtype=self.torch.uint8, device=self.dev)
+        return t, t.data_ptr()
+
+    def get(self, h):
+        if id(h) in self.on_their_way:
+            return self.on_their_way.pop(id(h))[1]
+        with self.torch.cuda.stream(self.s):
+            return h.cpu().numpy()
+
+
+def busy_side_mem():
+    """a SideMem on a new stream that side_feed has given some tens of milliseconds of unrelated work -> (stream, mem, what must stay alive)"""
+    s, keep = side_feed(device_zeros(64), np.zeros(64, np.uint8))
+    return s, SideMem(s), keep
+
+
+@pytest.fixture(scope="module")
+def env(pkg, lib, mem, oracle, ref):
+    """concurrent_checks' environment of the row tables: the writers of their chunks"""
+    made = cc.Env(pkg, cc.Recorder(lib), mem, oracle, ref)
+    yield made
+    made.close()      # (the global split mode, as it was found)
+
+
+ROW_TABLES = [(("blosclz", 17, 2), 17), (("lz4", 8, 1), 4080)]      # (codec, typesize, filter) and row size: lanes share a row; rows cross blocks
+
+
+def test_take_calls_on_a_side_stream(pkg, lib, env):
+    """blosc_gpu_take_batch / blosc_gpu_take_packed with a non-NULL stream; the chunks or the container, the index table and the sentinels of
+    dest and status are still on their way on that stream when the call is made.  The answers are take_checks.check_take's.  Cannot prove
+    ordering (see above); the first run of these calls on a stream of the caller's at all."""
+    for k, (setting, row_bytes) in enumerate(ROW_TABLES):
+        t = cc.RowTable(env, setting, row_bytes, turn=k)
+        for form in ("batch", "packed"):
+            s, side, keep = busy_side_mem()
+            source = cc.both_sources(side, t.chunks)[form]
+            check_take(pkg, lib, side, source, t.chunks, t.rows_plain, row_bytes, t.index, offset=5, what=(t.name, form, "side stream"), stream=s.cuda_stream)
+            s.synchronize()
+
+
+def test_put_calls_on_a_side_stream(pkg, lib, mem, oracle, env):
+    """blosc_gpu_put_batch / blosc_gpu_put_packed with a non-NULL stream; the chunks or the container, the index table and the new rows are
+    still on their way on that stream when the call is made.  The answers are put_checks.check_put's, and the container is the NULL
+    stream's byte for byte.  Cannot prove ordering (see above); the first run of these calls on a stream of the caller's at all."""
+    for k, (setting, row_bytes) in enumerate(ROW_TABLES):
+        t = cc.RowTable(env, setting, row_bytes, turn=k)
+        for form in ("batch", "packed"):
+            null, _, _ = check_put(pkg, lib, mem, oracle, t.sources[form], t.chunks, row_bytes, t.index, t.params, 256, 3, True, what=(t.name, form, "NULL stream"))
+            s, side, keep = busy_side_mem()
+            source = cc.both_sources(side, t.chunks)[form]
+            got, _, _ = check_put(pkg, lib, side, oracle, source, t.chunks, row_bytes, t.index, t.params, 256, 3, True, what=(t.name, form, "side stream"),
+                                  stream=s.cuda_stream)
+            s.synchronize()
+            assert np.array_equal(got, null), (t.name, form, "the side stream's container differs from the NULL stream's")
+
+
+def test_params_and_select_calls_on_a_side_stream(pkg, lib, mem, oracle, ref, env):
+    """blosc_gpu_compress_batch_params / _packed_params / _batch_select / _packed_select with a non-NULL stream, their sources still on their
+    way on that stream when they are called.  The answers are params_checks.check_every_setting_in_one_batch's and
+    select_checks.check_deterministic's, their yardstick the existing call on the NULL stream.  Cannot prove ordering (see above); the first
+    run of these calls on a stream of the caller's at all."""
+    hosts = mixed_hosts(SMALL)[:5]
+    yard_calls = sc.Calls(pkg, lib, mem, BLOCKSIZE)
+    settings, candidates = pc.deterministic_settings(2 * BLOCKSIZE), sc.candidates()
+    ref_chunks, yard = pc.reference_chunks(yard_calls, hosts, settings), sc.yardstick(yard_calls, hosts, candidates)
+    s, side, keep = busy_side_mem()
+    calls = sc.Calls(pkg, lib, side, BLOCKSIZE)
+    calls.src(hosts)
+    pc.check_every_setting_in_one_batch(calls, hosts, settings, ref_chunks, oracle, ref, aligns=(1, 256), stream=s.cuda_stream)
+    s.synchronize()
+    s, side, keep = busy_side_mem()
+    calls = sc.Calls(pkg, lib, side, BLOCKSIZE)
+    calls.src(hosts)
+    sc.check_deterministic(calls, hosts, candidates, yard, oracle, ref, aligns=(1, 256), stream=s.cuda_stream)
+    s.synchronize()
 
 
 def test_packed_calls_on_a_side_stream(pkg, lib, mem, oracle, ref):

@@ -230,15 +230,19 @@ def run_where(lib, mem, source, row_bytes, pred, capacity, null_table=False, str
     return rc, words[GUARD:GUARD + capacity].copy(), out
 
 
-def check_where(lib, mem, source, chunks, rows_plain, row_bytes, pred_args, pkgmod, capacity=None, dead=(), codes=None, stream=None, what=""):
+def check_where(lib, mem, source, chunks, rows_plain, row_bytes, pred_args, pkgmod, capacity=None, dead=(), codes=None, stream=None, what="", keep=None):
     """one call against numpy: the answer 0, the prefix of the table exact and ascending, every word from min(total, capacity) on untouched, the
     total, the per-chunk counts (codes: {chunk: the decoder's answer} for the chunks of `dead`), the rows and the unread rows.
-    capacity None: the total + 5.  Returns numpy's table"""
+    capacity None: the total + 5.  Returns numpy's table.  keep: a dict that receives what the call gave (the whole table, the total, the
+    per-chunk counts, the rows, unread), for callers that compare two calls"""
     offset, kind, nbytes, op, constant = pred_args
     want = expected(rows_plain, row_bytes, offset, kind, nbytes, op, constant, dead)
     cap = want.size + 5 if capacity is None else capacity
     rc, table, out = run_where(lib, mem, source, row_bytes, predicate(pkgmod, kind, nbytes, op, constant, offset), cap, null_table=(capacity == 0),
                                stream=stream)
+    if keep is not None:
+        keep.update(table=table, total=np.array([out.total.value, out.unread.value], np.uint64), matches=np.array(list(out.matches)[:out.n], np.int64),
+                    chunk_rows=np.array(list(out.rows)[:out.n], np.int64))
     what = (what, "row_bytes", row_bytes, "offset", offset, kind_name(kind, nbytes), OPS[op].__name__, hex(constant), "capacity", cap)
     assert rc == 0, (what, rc)
     rows = chunk_rows(chunks, row_bytes)

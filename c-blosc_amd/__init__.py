@@ -1,7 +1,7 @@
 """c-blosc_amd — Python-side loader for libblosc_amd.so (ctypes; test / bench plumbing only).
 
 The product is the C-ABI shared library built from ``csrc/`` (see ``include/blosc.h`` and
-``include/blosc_gpu.h``, ``include/blosc_gpu_packed.h``, ``include/blosc_gpu_params.h``, ``include/blosc_gpu_select.h``, ``include/blosc_gpu_getitem.h``, ``include/blosc_gpu_take.h``, ``include/blosc_gpu_put.h``, ``include/blosc_gpu_where.h``, ``include/blosc_gpu_aggregate.h``, ``include/blosc_gpu_checksum.h``).  This module only locates it, declares argument types and offers small
+``include/blosc_gpu.h``, ``include/blosc_gpu_packed.h``, ``include/blosc_gpu_params.h``, ``include/blosc_gpu_select.h``, ``include/blosc_gpu_getitem.h``, ``include/blosc_gpu_take.h``, ``include/blosc_gpu_put.h``, ``include/blosc_gpu_where.h``, ``include/blosc_gpu_aggregate.h``, ``include/blosc_gpu_clauses.h``, ``include/blosc_gpu_checksum.h``).  This module only locates it, declares argument types and offers small
 numpy conveniences that mirror how the reference is driven from Python through ctypes
 (SURVEY.md §A.8).  There is no CPU implementation here: if the library is missing, ``load()``
 raises; if there is no GPU, the library's calls return errors.
@@ -57,6 +57,10 @@ WHERE_SYMBOLS = [       # include/blosc_gpu_where.h
 AGGREGATE_SYMBOLS = [   # include/blosc_gpu_aggregate.h
     "blosc_gpu_aggregate_batch", "blosc_gpu_aggregate_packed",
 ]
+CLAUSES_SYMBOLS = [     # include/blosc_gpu_clauses.h
+    "blosc_gpu_where_clauses_batch", "blosc_gpu_where_clauses_packed", "blosc_gpu_aggregate_clauses_batch", "blosc_gpu_aggregate_clauses_packed",
+]
+MAX_TERMS = 16          # BLOSC_GPU_MAX_TERMS; clause numbers are 0 ... 15
 WHERE_EQ, WHERE_NE, WHERE_LT, WHERE_LE, WHERE_GT, WHERE_GE = range(6)
 FIELD_UINT, FIELD_INT, FIELD_FLOAT, FIELD_BFLOAT16 = range(4)
 CHECKSUM_ADLER32, CHECKSUM_CRC32 = 1, 2
@@ -106,6 +110,25 @@ def predicate(kind, nbytes, op, value, offset=0):
     if len(raw) != nbytes or nbytes > 8:
         raise ValueError(f"{len(raw)} bytes of value for a field of {nbytes}")
     return Predicate(offset, nbytes, kind, op, (C.c_uint8 * 8)(*raw))
+
+
+class Term(C.Structure):
+    """blosc_gpu_term (include/blosc_gpu_clauses.h): one test of a term list and the number of the clause it belongs to"""
+    _fields_ = [("test", Predicate), ("clause", C.c_uint32), ("pad_", C.c_uint32)]
+
+
+def term(pred, clause):
+    """A Term: the Predicate `pred` (see predicate()) as a member of clause `clause`, 0 ... 15.  A row passes a list of terms when every
+    clause that occurs in it has at least one true term"""
+    if not 0 <= clause < MAX_TERMS:
+        raise ValueError(f"clause {clause}: 0 ... {MAX_TERMS - 1}")
+    return Term(pred, clause, 0)
+
+
+def terms_table(terms):
+    """(the host array of blosc_gpu_term a call takes, its length) from a list of Term; no terms: (None, 0)"""
+    rows = list(terms or [])
+    return ((Term * len(rows))(*rows) if rows else None), len(rows)
 
 
 class Field(C.Structure):
@@ -223,6 +246,11 @@ def _signatures():
         # include/blosc_gpu_aggregate.h
         "blosc_gpu_aggregate_batch": ([i, pp, sz, P(Field), P(Predicate), P(Aggregate), P(Aggregate), ip, ip, zp, vp], i),
         "blosc_gpu_aggregate_packed": ([i, vp, sz, zp, sz, P(Field), P(Predicate), P(Aggregate), P(Aggregate), ip, ip, zp, vp], i),
+        # include/blosc_gpu_clauses.h
+        "blosc_gpu_where_clauses_batch": ([i, pp, sz, P(Term), i, vp, sz, zp, ip, ip, zp, vp], i),
+        "blosc_gpu_where_clauses_packed": ([i, vp, sz, zp, sz, P(Term), i, vp, sz, zp, ip, ip, zp, vp], i),
+        "blosc_gpu_aggregate_clauses_batch": ([i, pp, sz, P(Field), P(Term), i, P(Aggregate), P(Aggregate), ip, ip, zp, vp], i),
+        "blosc_gpu_aggregate_clauses_packed": ([i, vp, sz, zp, sz, P(Field), P(Term), i, P(Aggregate), P(Aggregate), ip, ip, zp, vp], i),
         # include/blosc_gpu_checksum.h
         "blosc_gpu_checksum_batch": ([i, i, pp, zp, P(C.c_uint), vp], i),
         "blosc_gpu_checksum_packed": ([i, i, vp, sz, zp, zp, P(C.c_uint), vp], i),
@@ -253,7 +281,7 @@ def declare(L):
     return L
 
 
-declare_packed = declare_params = declare_select = declare_getitem = declare_take = declare_put = declare_where = declare_aggregate = declare_checksum = declare    # the names from when every header had a function of its own
+declare_packed = declare_params = declare_select = declare_getitem = declare_take = declare_put = declare_where = declare_aggregate = declare_clauses = declare_checksum = declare    # the names from when every header had a function of its own
 
 
 # ---- numpy conveniences (host buffers through the stock entry points) --------------------------
@@ -603,6 +631,42 @@ class RowAggregate:
 
     def unread(self):
         return int(self.nunread.value)
+
+
+class RowWhereClauses(RowWhere):
+    """RowWhere for include/blosc_gpu_clauses.h: batch() and packed() take a list of Term (see term()) in the predicate's place - the rows for
+    which every clause of the list has a true term - through blosc_gpu_where_clauses_*.  The outputs are RowWhere's."""
+
+    def batch(self, src_ptrs, terms, index_out, capacity, stream=None):
+        self._outputs(len(src_ptrs))
+        table, n = terms_table(terms)
+        return self.lib.blosc_gpu_where_clauses_batch(self.nchunks, (C.c_void_p * max(self.nchunks, 1))(*src_ptrs), self.row_bytes, table, n, index_out,
+                                                      capacity, C.byref(self.ntotal), self.matches, self.rows, C.byref(self.nunread), stream)
+
+    def packed(self, container, containersize, offsets, terms, index_out, capacity, stream=None):
+        self._outputs(len(offsets) - 1)
+        table, n = terms_table(terms)
+        return self.lib.blosc_gpu_where_clauses_packed(self.nchunks, container, containersize, (C.c_size_t * (self.nchunks + 1))(*offsets), self.row_bytes,
+                                                       table, n, index_out, capacity, C.byref(self.ntotal), self.matches, self.rows,
+                                                       C.byref(self.nunread), stream)
+
+
+class RowAggregateClauses(RowAggregate):
+    """RowAggregate for include/blosc_gpu_clauses.h: batch() and packed() take a list of Term (see term()) in the filter's place (None or
+    empty: every row) through blosc_gpu_aggregate_clauses_*.  The outputs are RowAggregate's."""
+
+    def batch(self, src_ptrs, fld, terms=None, stream=None):
+        self._outputs(len(src_ptrs))
+        table, n = terms_table(terms)
+        return self.lib.blosc_gpu_aggregate_clauses_batch(self.nchunks, (C.c_void_p * max(self.nchunks, 1))(*src_ptrs), self.row_bytes, C.byref(fld), table, n,
+                                                          C.byref(self.result), self.per_chunk, self.status, self.rows, C.byref(self.nunread), stream)
+
+    def packed(self, container, containersize, offsets, fld, terms=None, stream=None):
+        self._outputs(len(offsets) - 1)
+        table, n = terms_table(terms)
+        return self.lib.blosc_gpu_aggregate_clauses_packed(self.nchunks, container, containersize, (C.c_size_t * (self.nchunks + 1))(*offsets), self.row_bytes,
+                                                           C.byref(fld), table, n, C.byref(self.result), self.per_chunk, self.status, self.rows,
+                                                           C.byref(self.nunread), stream)
 
 
 def checksums(kind, ptrs, sizes, lib=None, stream=None):

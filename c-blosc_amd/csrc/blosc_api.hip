@@ -24,6 +24,7 @@
 #include "../../include/blosc_gpu_put.h"
 #include "../../include/blosc_gpu_where.h"
 #include "../../include/blosc_gpu_aggregate.h"
+#include "../../include/blosc_gpu_clauses.h"
 #include "../../include/blosc_gpu_checksum.h"
 #include "blosc_format.h"
 #include "dev_types.h"
@@ -775,6 +776,102 @@ int blosc_gpu_aggregate_packed(int nchunks, const void* container, size_t contai
   if (nchunks > 0 && (!container || !offsets)) return -1;
   return aggregate_call(nchunks, jobs_from_spans(nchunks, container, containersize, offsets, nullptr, BLOSC_MIN_HEADER_LENGTH), row_bytes, f,
                         filter ? &q : nullptr, total_out, chunk_out, chunk_status_out, chunk_rows_out, unread_out, stream);
+}
+
+// ---- where and aggregate by a term list (include/blosc_gpu_clauses.h) -------------------------------
+static_assert(sizeof(blosc_gpu_term) == 32 && BLOSC_GPU_MAX_TERMS == WH_MAX_TERMS, "blosc_gpu_term; the kernels' table holds every term");
+// terms_opening(): the list's own checks, and the list as the kernels evaluate it (dev_types.h: WhereTerms) - every term through
+// where_opening(), which refuses what blosc_gpu_where_* refuses and gives its key, `inf` and NaN flag; the distinct (offset, bytes) pairs, in
+// front of them the aggregated field where there is one; the terms sorted by the pair they read.  min_terms: 1 (where) or 0 (aggregate)
+static int terms_opening(int nchunks, size_t row_bytes, const blosc_gpu_term* terms, int nterms, int min_terms, const AggField* aggregated, WhereTerms* out) {
+  if (nterms < min_terms || nterms > BLOSC_GPU_MAX_TERMS || (nterms > 0) != (terms != nullptr)) return -1;
+  WhereTerms w{};
+  WherePred q[WH_MAX_TERMS];
+  uint32_t field_of[WH_MAX_TERMS];
+  if (aggregated) { w.offset[0] = aggregated->offset; w.bytes[0] = aggregated->bytes; w.nfields = 1; }
+  for (int t = 0; t < nterms; t++) {
+    if (terms[t].clause >= 16 || terms[t].pad_ != 0) return -1;
+    const int c = where_opening(nchunks, row_bytes, &terms[t].test, nullptr, 0, &q[t]);
+    if (c != kGo) return c;
+    uint32_t f = 0;
+    while (f < w.nfields && (w.offset[f] != q[t].offset || w.bytes[f] != q[t].bytes)) f++;
+    if (f == w.nfields) { w.offset[f] = q[t].offset; w.bytes[f] = q[t].bytes; w.nfields++; }
+    field_of[t] = f;
+    w.clauses |= 1u << terms[t].clause;
+  }
+  for (uint32_t f = 0; f < w.nfields; f++) {
+    w.first[f] = w.nterms;
+    for (int t = 0; t < nterms; t++)
+      if (field_of[t] == f) { w.test[w.nterms] = q[t]; w.bit[w.nterms] = 1u << terms[t].clause; w.nterms++; }
+  }
+  for (uint32_t f = w.nfields; f <= (uint32_t)WH_MAX_FIELDS; f++) w.first[f] = w.nterms;
+  *out = w;
+  return kGo;
+}
+static int where_clauses_opening(int nchunks, size_t row_bytes, const blosc_gpu_term* terms, int nterms, const int64_t* index_out, size_t capacity, WhereTerms* w) {
+  if (nchunks < 0 || row_bytes < 1 || row_bytes > 65536) return -1;
+  if (capacity && (!index_out || capacity > SIZE_MAX / sizeof(int64_t))) return -1;
+  return terms_opening(nchunks, row_bytes, terms, nterms, 1, nullptr, w);
+}
+static int where_clauses_call(int nchunks, const Table<Job>& jobs, size_t row_bytes, const WhereTerms& w, int64_t* index_out, size_t capacity, size_t* total_out,
+                              int* chunk_matches_out, int* chunk_rows_out, size_t* unread_out, void* stream) {
+  if (!jobs) return -1;
+  if (nchunks == 0) { if (total_out) *total_out = 0; if (unread_out) *unread_out = 0; return 0; }      // no chunk to count, no row to read
+  return engine_where_terms(nchunks, jobs.get(), row_bytes, w, index_out, capacity, total_out, chunk_matches_out, chunk_rows_out, unread_out, (hipStream_t)stream);
+}
+int blosc_gpu_where_clauses_batch(int nchunks, const void* const* src, size_t row_bytes, const blosc_gpu_term* terms, int nterms, int64_t* index_out,
+                                  size_t capacity, size_t* total_out, int* chunk_matches_out, int* chunk_rows_out, size_t* unread_out, void* stream) {
+  WhereTerms w;
+  const int c = where_clauses_opening(nchunks, row_bytes, terms, nterms, index_out, capacity, &w);
+  if (c != kGo) return c;
+  if (nchunks > 0 && !src) return -1;
+  return where_clauses_call(nchunks, jobs_from_arrays(nchunks, src, nullptr, nullptr, nullptr), row_bytes, w, index_out, capacity, total_out, chunk_matches_out,
+                            chunk_rows_out, unread_out, stream);
+}
+int blosc_gpu_where_clauses_packed(int nchunks, const void* container, size_t containersize, const size_t* offsets, size_t row_bytes, const blosc_gpu_term* terms,
+                                   int nterms, int64_t* index_out, size_t capacity, size_t* total_out, int* chunk_matches_out, int* chunk_rows_out,
+                                   size_t* unread_out, void* stream) {
+  WhereTerms w;
+  const int c = where_clauses_opening(nchunks, row_bytes, terms, nterms, index_out, capacity, &w);
+  if (c != kGo) return c;
+  if (nchunks > 0 && (!container || !offsets)) return -1;
+  // index_out against the source container as a whole (the engine checks it against every chunk)
+  const uintptr_t s0 = (uintptr_t)container, s1 = s0 + containersize, d0 = (uintptr_t)index_out, d1 = d0 + capacity * sizeof(int64_t);
+  if (nchunks > 0 && capacity && containersize && s0 < d1 && d0 < s1) return -1;
+  return where_clauses_call(nchunks, jobs_from_spans(nchunks, container, containersize, offsets, nullptr, BLOSC_MIN_HEADER_LENGTH), row_bytes, w, index_out,
+                            capacity, total_out, chunk_matches_out, chunk_rows_out, unread_out, stream);
+}
+static int aggregate_clauses_opening(int nchunks, size_t row_bytes, const blosc_gpu_field* field, const blosc_gpu_term* terms, int nterms, AggField* f, WhereTerms* w) {
+  WherePred unused;
+  const int c = aggregate_opening(nchunks, row_bytes, field, nullptr, f, &unused);
+  return c != kGo ? c : terms_opening(nchunks, row_bytes, terms, nterms, 0, f, w);
+}
+static int aggregate_clauses_call(int nchunks, const Table<Job>& jobs, size_t row_bytes, const AggField& f, const WhereTerms& w, blosc_gpu_aggregate* total_out,
+                                  blosc_gpu_aggregate* chunk_out, int* chunk_status_out, int* chunk_rows_out, size_t* unread_out, void* stream) {
+  if (!jobs) return -1;
+  if (nchunks == 0) return aggregate_call(0, jobs, row_bytes, f, nullptr, total_out, chunk_out, chunk_status_out, chunk_rows_out, unread_out, stream);      // the total of nothing
+  return engine_aggregate_terms(nchunks, jobs.get(), row_bytes, f, w, (AggResult*)total_out, (AggResult*)chunk_out, chunk_status_out, chunk_rows_out, unread_out,
+                                (hipStream_t)stream);
+}
+int blosc_gpu_aggregate_clauses_batch(int nchunks, const void* const* src, size_t row_bytes, const blosc_gpu_field* field, const blosc_gpu_term* terms, int nterms,
+                                      blosc_gpu_aggregate* total_out, blosc_gpu_aggregate* chunk_out, int* chunk_status_out, int* chunk_rows_out,
+                                      size_t* unread_out, void* stream) {
+  AggField f; WhereTerms w;
+  const int c = aggregate_clauses_opening(nchunks, row_bytes, field, terms, nterms, &f, &w);
+  if (c != kGo) return c;
+  if (nchunks > 0 && !src) return -1;
+  return aggregate_clauses_call(nchunks, jobs_from_arrays(nchunks, src, nullptr, nullptr, nullptr), row_bytes, f, w, total_out, chunk_out, chunk_status_out,
+                                chunk_rows_out, unread_out, stream);
+}
+int blosc_gpu_aggregate_clauses_packed(int nchunks, const void* container, size_t containersize, const size_t* offsets, size_t row_bytes,
+                                       const blosc_gpu_field* field, const blosc_gpu_term* terms, int nterms, blosc_gpu_aggregate* total_out,
+                                       blosc_gpu_aggregate* chunk_out, int* chunk_status_out, int* chunk_rows_out, size_t* unread_out, void* stream) {
+  AggField f; WhereTerms w;
+  const int c = aggregate_clauses_opening(nchunks, row_bytes, field, terms, nterms, &f, &w);
+  if (c != kGo) return c;
+  if (nchunks > 0 && (!container || !offsets)) return -1;
+  return aggregate_clauses_call(nchunks, jobs_from_spans(nchunks, container, containersize, offsets, nullptr, BLOSC_MIN_HEADER_LENGTH), row_bytes, f, w,
+                                total_out, chunk_out, chunk_status_out, chunk_rows_out, unread_out, stream);
 }
 
 // ---- adler32 / crc32 of many runs (include/blosc_gpu_checksum.h) ---------------------------------------

@@ -157,6 +157,24 @@ struct WherePred {
   int32_t nan;           // the constant is a NaN
   int32_t pad_;
 };
+// WhereTerms: a term list (include/blosc_gpu_clauses.h) as k_where_mark_terms and k_aggregate_tiles_terms evaluate it.  A table in device
+// memory that every lane reads at the same index: it is the same for all rows, so it travels in scalar registers.
+//   fields   the distinct (offset, bytes) pairs the terms read, each loaded once per row.  In aggregate field 0 is ALWAYS the aggregated
+//            one, whether a term tests it or not, so that the kernel takes its value at a constant index;
+//   test     the terms as WherePred, SORTED by the field they read: those of field f are test[first[f]] ... test[first[f + 1] - 1], so the
+//            kernel walks the fields at constant indices and the terms of each under a uniform bound - no register array is indexed at run time;
+//   bit      1 << clause of test[t];  clauses: the OR of all of them.  A row passes when the bits of its true terms make up `clauses`.
+constexpr int WH_MAX_TERMS = 16;
+constexpr int WH_MAX_FIELDS = WH_MAX_TERMS + 1;
+struct WhereTerms {
+  uint32_t nterms, nfields;
+  uint32_t clauses;
+  uint32_t pad_;
+  uint32_t offset[WH_MAX_FIELDS], bytes[WH_MAX_FIELDS];
+  uint32_t first[WH_MAX_FIELDS + 1];
+  uint32_t bit[WH_MAX_TERMS];
+  WherePred test[WH_MAX_TERMS];
+};
 // v: the field's `bytes` bytes, little endian, zero-extended.  *nan (floating point): the pattern is a NaN
 #if defined(__HIPCC__) || defined(__HIP__)
 __host__ __device__

@@ -104,6 +104,14 @@ struct AggField;
 struct AggResult;
 int engine_aggregate(int nchunks, const Job* chunks, size_t row_bytes, const AggField& field, const WherePred* filter, AggResult* total_out,
                      AggResult* chunk_out, int* chunk_status_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream);
+// The two calls above for a term list (include/blosc_gpu_clauses.h): the rows for which every clause of the list has a true term.  terms: the
+// caller's list as the kernels evaluate it (dev_types.h: WhereTerms; in aggregate its field 0 is `field`, and no terms let every row through).
+// Everything else as above: the same body runs behind another mark / tile kernel.
+struct WhereTerms;
+int engine_where_terms(int nchunks, const Job* chunks, size_t row_bytes, const WhereTerms& terms, int64_t* index_out, size_t capacity, size_t* total_out,
+                       int* chunk_matches_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream);
+int engine_aggregate_terms(int nchunks, const Job* chunks, size_t row_bytes, const AggField& field, const WhereTerms& terms, AggResult* total_out,
+                           AggResult* chunk_out, int* chunk_status_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream);
 
 // zlib's adler32 (kind 1) / crc32 (kind 2) of n runs in device memory (include/blosc_gpu_checksum.h): runs[i].src and runs[i].srcsize;
 // an empty run's pointer is never read.  digests[] is written only when the call answers 0.

@@ -2181,8 +2181,17 @@ int engine_put(int nchunks, const Job* chunks, size_t row_bytes, size_t nidx, co
 //   3. the chunks' counters come down, last synchronisation; the caller's host tables are written.
 // Synchronisations: 2 + 2 per pass that holds a row, whatever the rows and the matches.
 // Workspace per tile of WH_TILE rows: WH_WORDS mask words, a count and a base (140 bytes per 1024 rows).
-int engine_where(int nchunks, const Job* chunks, size_t row_bytes, const WherePred& pred, int64_t* index_out, size_t capacity, size_t* total_out,
-                 int* chunk_matches_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream) {
+// The body is written once for the one predicate and for a term list (include/blosc_gpu_clauses.h): `mark` launches the pass's mark kernel
+// under its own profile name; `terms` (nullptr: none) goes up once, behind the counters, and `mark` receives its device address.
+namespace {
+struct MarkPass {      // what a mark kernel is launched with
+  dim3 grid; const WhereChunk* d_chunks; const uint32_t* d_tiles; int in_pass; uint32_t row_bytes;
+  uint64_t* d_masks; uint32_t* d_tile_count; uint32_t* d_count;
+};
+}  // namespace
+template <class Mark>
+static int where_passes(int nchunks, const Job* chunks, size_t row_bytes, const WhereTerms* terms, Mark mark, int64_t* index_out, size_t capacity,
+                        size_t* total_out, int* chunk_matches_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream) {
   CtxGuard ctx; EngineState& st = *ctx.st;
   if (ensure_device(st)) return -1;
   // ---- the census; then index_out against every source - a call that fails the second writes nothing at all ----
@@ -2194,13 +2203,17 @@ int engine_where(int nchunks, const Job* chunks, size_t row_bytes, const WherePr
   if (capacity && overlaps_a_source(rs.jobs, rs.hdrs, (uintptr_t)index_out, (uintptr_t)index_out + capacity * sizeof(int64_t))) return -1;
   rs.rows_to(chunk_rows_out);
   // ---- the passes: per tile its mask words, a count and a base; the running total and the chunks' counters come down at the end ----
-  const size_t back_bytes = sizeof(uint64_t) + sizeof(uint32_t) * (n ? n : 1);
-  if (rs.deal_tiles(st, sizeof(uint64_t) * WH_WORDS + sizeof(uint32_t) + sizeof(uint64_t), back_bytes)) return -1;
+  const size_t back_bytes = sizeof(uint64_t) + sizeof(uint32_t) * (n ? n : 1), o_terms = align_up(back_bytes, 16);
+  if (rs.deal_tiles(st, sizeof(uint64_t) * WH_WORDS + sizeof(uint32_t) + sizeof(uint64_t), o_terms + (terms ? sizeof(WhereTerms) : 0))) return -1;
   uint8_t *D = rs.D, *P = rs.P;
   const size_t o_back = rs.o_back;
   uint64_t* d_running = (uint64_t*)(D + o_back);
   uint32_t* d_count = (uint32_t*)(D + o_back + sizeof(uint64_t));
   HIP_TRY(hipMemsetAsync(D + o_back, 0, back_bytes, stream));
+  if (terms) {
+    memcpy(P + o_back + o_terms, terms, sizeof(WhereTerms));
+    HIP_TRY(hipMemcpyAsync(D + o_back + o_terms, P + o_back + o_terms, sizeof(WhereTerms), hipMemcpyHostToDevice, stream));
+  }
   for (size_t p = 0; p < rs.npass; p++) {
     bool holds_rows = false;
     if (rs.decode_tiles(st, p, stream, &holds_rows)) return -1;
@@ -2214,12 +2227,8 @@ int engine_where(int nchunks, const Job* chunks, size_t row_bytes, const WherePr
       const WhereChunk* d_chunks = rs.d_chunks();
       const uint32_t* d_tiles = rs.d_tiles();
       const dim3 grid(persistent_grid(st, ntiles, WH_WAVES_PER_CU / WH_WAVES));
-      {
-        ProfScope ps(st, stream, "k_where_mark");
-        hipLaunchKernelGGL(k_where_mark, grid, dim3(WH_THREADS), 0, stream, d_chunks, d_tiles, (int)(c1 - c0), (uint32_t)row_bytes, pred, d_masks, d_tile_count,
-                           d_count + c0);
-        HIP_TRY(hipGetLastError());
-      }
+      if (mark(st, stream, MarkPass{grid, d_chunks, d_tiles, (int)(c1 - c0), (uint32_t)row_bytes, d_masks, d_tile_count, d_count + c0},
+               (const WhereTerms*)(D + o_back + o_terms))) return -1;
       if (capacity) {
         {
           ProfScope ps(st, stream, "k_where_scan");
@@ -2247,6 +2256,27 @@ int engine_where(int nchunks, const Job* chunks, size_t row_bytes, const WherePr
   if (unread_out) *unread_out = rs.unread;
   return 0;
 }
+int engine_where(int nchunks, const Job* chunks, size_t row_bytes, const WherePred& pred, int64_t* index_out, size_t capacity, size_t* total_out,
+                 int* chunk_matches_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream) {
+  auto mark = [&pred](EngineState& st, hipStream_t stream, const MarkPass& m, const WhereTerms*) {
+    ProfScope ps(st, stream, "k_where_mark");
+    hipLaunchKernelGGL(k_where_mark, m.grid, dim3(WH_THREADS), 0, stream, m.d_chunks, m.d_tiles, m.in_pass, m.row_bytes, pred, m.d_masks, m.d_tile_count, m.d_count);
+    HIP_TRY(hipGetLastError());
+    return 0;
+  };
+  return where_passes(nchunks, chunks, row_bytes, nullptr, mark, index_out, capacity, total_out, chunk_matches_out, chunk_rows_out, unread_out, stream);
+}
+int engine_where_terms(int nchunks, const Job* chunks, size_t row_bytes, const WhereTerms& terms, int64_t* index_out, size_t capacity, size_t* total_out,
+                       int* chunk_matches_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream) {
+  auto mark = [](EngineState& st, hipStream_t stream, const MarkPass& m, const WhereTerms* d_terms) {
+    ProfScope ps(st, stream, "k_where_mark_terms");
+    hipLaunchKernelGGL(k_where_mark_terms, m.grid, dim3(WH_THREADS), 0, stream, m.d_chunks, m.d_tiles, m.in_pass, m.row_bytes, d_terms, m.d_masks, m.d_tile_count,
+                       m.d_count);
+    HIP_TRY(hipGetLastError());
+    return 0;
+  };
+  return where_passes(nchunks, chunks, row_bytes, &terms, mark, index_out, capacity, total_out, chunk_matches_out, chunk_rows_out, unread_out, stream);
+}
 
 // ---------------------------------------------------------------------------------------------
 // aggregate (include/blosc_gpu_aggregate.h): count, sum, min and max of a row field, per chunk and for the call
@@ -2273,8 +2303,16 @@ static void aggregate_fold(AggResult* total, const AggResult& c, const AggField&
     total->max_row = c.max_row; total->max = c.max;
   }
 }
-int engine_aggregate(int nchunks, const Job* chunks, size_t row_bytes, const AggField& field, const WherePred* filter, AggResult* total_out,
-                     AggResult* chunk_out, int* chunk_status_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream) {
+// The body is written once, as where's: `tiles` launches the pass's tile kernel under its own profile name; `terms` (nullptr: none) goes up
+// once, behind the chunks' results, and `tiles` receives its device address.
+namespace {
+struct TilesPass {      // what a tile kernel is launched with
+  dim3 grid; const WhereChunk* d_chunks; const uint32_t* d_tiles; int in_pass; uint32_t row_bytes; AggPartial* d_partials;
+};
+}  // namespace
+template <class Tiles>
+static int aggregate_passes(int nchunks, const Job* chunks, size_t row_bytes, const AggField& field, const WhereTerms* terms, Tiles tiles, AggResult* total_out,
+                            AggResult* chunk_out, int* chunk_status_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream) {
   CtxGuard ctx; EngineState& st = *ctx.st;
   if (ensure_device(st)) return -1;
   RowScan rs;
@@ -2284,10 +2322,13 @@ int engine_aggregate(int nchunks, const Job* chunks, size_t row_bytes, const Agg
   rs.rows_to(chunk_rows_out);
   if (!usable) return -1;
   const size_t back_bytes = sizeof(AggResult) * (n ? n : 1);
-  if (rs.deal_tiles(st, sizeof(AggPartial), back_bytes)) return -1;
+  if (rs.deal_tiles(st, sizeof(AggPartial), back_bytes + (terms ? sizeof(WhereTerms) : 0))) return -1;
   uint8_t *D = rs.D, *P = rs.P;
   AggResult* d_results = (AggResult*)(D + rs.o_back);
-  const WherePred q = filter ? *filter : WherePred{};
+  if (terms) {
+    memcpy(P + rs.o_back + back_bytes, terms, sizeof(WhereTerms));
+    HIP_TRY(hipMemcpyAsync(D + rs.o_back + back_bytes, P + rs.o_back + back_bytes, sizeof(WhereTerms), hipMemcpyHostToDevice, stream));
+  }
   for (size_t p = 0; p < rs.npass; p++) {
     bool holds_rows = false;
     if (rs.decode_tiles(st, p, stream, &holds_rows)) return -1;
@@ -2295,12 +2336,8 @@ int engine_aggregate(int nchunks, const Job* chunks, size_t row_bytes, const Agg
     const int in_pass = (int)(rs.c1 - rs.c0);
     Carver wv; wv.off = rs.at;
     AggPartial* d_partials = (AggPartial*)(D + wv.take(sizeof(AggPartial) * rs.ntiles));
-    {
-      ProfScope ps(st, stream, "k_aggregate_tiles");
-      hipLaunchKernelGGL(k_aggregate_tiles, dim3(persistent_grid(st, rs.ntiles, WH_WAVES_PER_CU / WH_WAVES)), dim3(WH_THREADS), 0, stream, rs.d_chunks(),
-                         rs.d_tiles(), in_pass, (uint32_t)row_bytes, field, q, filter ? 1 : 0, d_partials);
-      HIP_TRY(hipGetLastError());
-    }
+    if (tiles(st, stream, TilesPass{dim3(persistent_grid(st, rs.ntiles, WH_WAVES_PER_CU / WH_WAVES)), rs.d_chunks(), rs.d_tiles(), in_pass, (uint32_t)row_bytes, d_partials},
+              (const WhereTerms*)(D + rs.o_back + back_bytes))) return -1;
     ProfScope ps(st, stream, "k_aggregate_chunks");
     hipLaunchKernelGGL(k_aggregate_chunks, dim3(persistent_grid(st, (size_t)in_pass, WH_WAVES_PER_CU / WH_WAVES)), dim3(WH_THREADS), 0, stream, rs.d_chunks(),
                        rs.d_tiles(), in_pass, (uint32_t)row_bytes, field, (const AggPartial*)d_partials, d_results + rs.c0);
@@ -2324,6 +2361,28 @@ int engine_aggregate(int nchunks, const Job* chunks, size_t row_bytes, const Agg
   if (total_out) *total_out = total;
   if (unread_out) *unread_out = rs.unread;
   return 0;
+}
+int engine_aggregate(int nchunks, const Job* chunks, size_t row_bytes, const AggField& field, const WherePred* filter, AggResult* total_out,
+                     AggResult* chunk_out, int* chunk_status_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream) {
+  const WherePred q = filter ? *filter : WherePred{};
+  const int filtered = filter ? 1 : 0;
+  auto tiles = [&field, &q, filtered](EngineState& st, hipStream_t stream, const TilesPass& m, const WhereTerms*) {
+    ProfScope ps(st, stream, "k_aggregate_tiles");
+    hipLaunchKernelGGL(k_aggregate_tiles, m.grid, dim3(WH_THREADS), 0, stream, m.d_chunks, m.d_tiles, m.in_pass, m.row_bytes, field, q, filtered, m.d_partials);
+    HIP_TRY(hipGetLastError());
+    return 0;
+  };
+  return aggregate_passes(nchunks, chunks, row_bytes, field, nullptr, tiles, total_out, chunk_out, chunk_status_out, chunk_rows_out, unread_out, stream);
+}
+int engine_aggregate_terms(int nchunks, const Job* chunks, size_t row_bytes, const AggField& field, const WhereTerms& terms, AggResult* total_out,
+                           AggResult* chunk_out, int* chunk_status_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream) {
+  auto tiles = [&field](EngineState& st, hipStream_t stream, const TilesPass& m, const WhereTerms* d_terms) {
+    ProfScope ps(st, stream, "k_aggregate_tiles_terms");
+    hipLaunchKernelGGL(k_aggregate_tiles_terms, m.grid, dim3(WH_THREADS), 0, stream, m.d_chunks, m.d_tiles, m.in_pass, m.row_bytes, field, d_terms, m.d_partials);
+    HIP_TRY(hipGetLastError());
+    return 0;
+  };
+  return aggregate_passes(nchunks, chunks, row_bytes, field, &terms, tiles, total_out, chunk_out, chunk_status_out, chunk_rows_out, unread_out, stream);
 }
 
 // blosc_getitem / blosc_gpu_getitem: one chunk, one range, one result, each pointer host or device memory.  What only this call has: a stream

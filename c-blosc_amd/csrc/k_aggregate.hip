@@ -109,6 +109,40 @@ __global__ __launch_bounds__(WH_THREADS) void k_aggregate_tiles(const WhereChunk
   }
 }
 
+// k_aggregate_tiles for a term list (include/blosc_gpu_clauses.h; row_prims.h: where_terms_test): the same tiles, grid, order of additions
+// and AggPartial, so k_aggregate_chunks runs behind it as it is.  Field 0 of the list is the aggregated one (dev_types.h: WhereTerms): the
+// row's value is what where_terms_test loaded for it, whether a term tests it or not.  No terms: every row.
+__global__ __launch_bounds__(WH_THREADS) void k_aggregate_tiles_terms(const WhereChunk* __restrict__ chunks /*[nchunks]*/, const uint32_t* __restrict__ tile_first /*[nchunks + 1]*/,
+                                                                     int nchunks, uint32_t row_bytes, AggField f, const WhereTerms* __restrict__ terms,
+                                                                     AggPartial* __restrict__ partials) {
+  __shared__ AggAcc waves[WH_WAVES];
+  const uint32_t tid = threadIdx.x;
+  const uint32_t ntiles = tile_first[nchunks];
+  const bool fp = f.kind == 2;
+  for (uint32_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const uint32_t c = tile_owner(tile_first, nchunks, t);
+    const WhereChunk ch = chunks[c];
+    const uint32_t row0 = (t - tile_first[c]) * WH_TILE;
+    const gu8* base = as_global(ch.slot);
+    AggAcc a = agg_none();
+#pragma unroll 1
+    for (int s = 0; s < WH_STEPS; s++) {
+      const uint32_t r = row0 + (uint32_t)s * WH_THREADS + tid;
+      if (ch.status < 0 || r >= ch.rows) continue;
+      uint64_t v[WH_MAX_FIELDS];
+      if (!where_terms_test(terms, base + (size_t)r * row_bytes, v)) continue;
+      bool nan;
+      const int64_t key = where_key(v[0], f.kind, f.bytes, f.inf, &nan);
+      a.count++;
+      if (nan) { a.nans++; continue; }
+      agg_extreme(a, key, r);
+      a.sum = fp ? agg_u64(agg_f64(a.sum) + agg_f64(widen_to_f64(v[0], f.bytes, f.mant))) : a.sum + (f.kind == 1 ? (uint64_t)key : v[0]);
+    }
+    a = agg_workgroup(a, waves, tid, fp);
+    if (tid == 0) partials[t] = AggPartial{a.min_key, a.max_key, a.sum, a.min_row, a.max_row, a.count, a.nans};
+  }
+}
+
 // results [nchunks]: the entries of the pass's chunks in the call's table, every one written
 __global__ __launch_bounds__(WH_THREADS) void k_aggregate_chunks(const WhereChunk* __restrict__ chunks, const uint32_t* __restrict__ tile_first, int nchunks,
                                                                 uint32_t row_bytes, AggField f, const AggPartial* __restrict__ partials,

@@ -5,6 +5,7 @@
 // (row_prims.h: tile_owner).  Three kernels per pass, and no workgroup ever waits for another one:
 //   k_where_mark    one lane per row: the field's key against the constant's (dev_types.h: WherePred), one __ballot word per 64 rows, the
 //                   tile's count, and that count added to its chunk's counter (an integer atomic at L2: the sum does not depend on the order);
+//                   k_where_mark_terms is the same for a term list (include/blosc_gpu_clauses.h), with the same outputs;
 //   k_where_scan    ONE workgroup: the exclusive prefix of the pass's tile counts, started at the call's running total, which lives in
 //                   device memory and is carried to the next pass - the passes order themselves on the stream;
 //   k_where_write   one lane per row again: tile base + the counts of the words in front of its own (LDS) + the set bits below its lane
@@ -39,6 +40,51 @@ __global__ __launch_bounds__(WH_THREADS) void k_where_mark(const WhereChunk* __r
       const uint32_t r = row0 + (uint32_t)s * WH_THREADS + tid;
       bool hit = false;
       if (ch.status >= 0 && r < ch.rows) hit = where_test(q, where_field(base + (size_t)r * row_bytes, q.bytes));
+      const uint64_t m = __ballot(hit);
+      if (lane == 0) masks[(size_t)t * WH_WORDS + (uint32_t)s * WH_WAVES + wave] = m;
+      count += (uint32_t)__builtin_popcountll(m);
+    }
+    if (lane == 0) wave_count[wave] = count;
+    __syncthreads();
+    if (tid == 0) {
+      uint32_t total = 0;
+      for (int w = 0; w < WH_WAVES; w++) total += wave_count[w];
+      tile_count[t] = total;
+      if (c != held_chunk) {
+        if (held) atomicAdd(&chunk_count[held_chunk], held);
+        held = 0; held_chunk = c;
+      }
+      held += total;
+    }
+    __syncthreads();      // wave_count is written again by the next tile
+  }
+  if (tid == 0 && held) atomicAdd(&chunk_count[held_chunk], held);
+}
+
+// k_where_mark for a term list (include/blosc_gpu_clauses.h; row_prims.h: where_terms_test): the same tiles, grid and outputs, so
+// k_where_scan and k_where_write run behind it as they are.  terms: the list in device memory, read at lane-uniform indices.
+__global__ __launch_bounds__(WH_THREADS) void k_where_mark_terms(const WhereChunk* __restrict__ chunks /*[nchunks]*/, const uint32_t* __restrict__ tile_first /*[nchunks + 1]*/,
+                                                                int nchunks, uint32_t row_bytes, const WhereTerms* __restrict__ terms,
+                                                                uint64_t* __restrict__ masks, uint32_t* __restrict__ tile_count,
+                                                                uint32_t* __restrict__ chunk_count) {
+  __shared__ uint32_t wave_count[WH_WAVES];
+  const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+  const uint32_t ntiles = tile_first[nchunks];
+  uint32_t held = 0, held_chunk = 0;      // thread 0, as in k_where_mark: one atomic per chunk the workgroup meets
+  for (uint32_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const uint32_t c = tile_owner(tile_first, nchunks, t);
+    const WhereChunk ch = chunks[c];
+    const uint32_t row0 = (t - tile_first[c]) * WH_TILE;
+    const gu8* base = as_global(ch.slot);
+    uint32_t count = 0;      // of this wave's words: the same in all its lanes
+#pragma unroll 1
+    for (int s = 0; s < WH_STEPS; s++) {
+      const uint32_t r = row0 + (uint32_t)s * WH_THREADS + tid;
+      bool hit = false;
+      if (ch.status >= 0 && r < ch.rows) {
+        uint64_t v[WH_MAX_FIELDS];
+        hit = where_terms_test(terms, base + (size_t)r * row_bytes, v);
+      }
       const uint64_t m = __ballot(hit);
       if (lane == 0) masks[(size_t)t * WH_WORDS + (uint32_t)s * WH_WAVES + wave] = m;
       count += (uint32_t)__builtin_popcountll(m);

@@ -1,6 +1,7 @@
 // row_prims.h — the device pieces that the row kernels (k_take.hip, k_put.hip, k_where.hip, k_aggregate.hip) and k_getitem_gather
 // (k_decode.hip) share, each defined once: the owner of a tile, the chunk of a row, one row moved by a group of lanes, a tile copied by a
-// wave, a row's field and its predicate.  A rule is stated here, at its helper; tests/test_wave_emu_row_prims.py runs them one by one.
+// wave, a row's field, its predicate and a list of them.  A rule is stated here, at its helper; tests/test_wave_emu_row_prims.py and
+// tests/test_wave_emu_clauses.py run them one by one.
 #pragma once
 #include "dev_types.h"
 #include "mem_prims.h"
@@ -133,6 +134,37 @@ __device__ __forceinline__ bool where_test(const WherePred& q, uint64_t v) {
     case 4: return k > q.key;
     default: return k >= q.key;
   }
+}
+
+// A term list on the row at `row` (dev_types.h: WhereTerms; include/blosc_gpu_clauses.h): true when every clause of the list has a true
+// term.  The row's distinct fields go to v[0] ... v[nfields - 1], every one loaded once and all of them before the first comparison - the
+// loads are independent, so a row that spans several sectors waits for them together.  q is read at indices that are the same in every
+// lane: the fields at constant indices under the uniform bound nfields, the terms of a field under its uniform range.  No lane leaves early.
+__device__ __forceinline__ bool where_terms_test(const WhereTerms* __restrict__ q, const gu8* row, uint64_t (&v)[WH_MAX_FIELDS]) {
+  const uint32_t nfields = q->nfields;
+  uint32_t lo[WH_MAX_FIELDS], hi[WH_MAX_FIELDS];      // where_field's loads, each into the register it stays in: nothing here waits for one of them
+#pragma unroll
+  for (int f = 0; f < WH_MAX_FIELDS; f++)
+    if ((uint32_t)f < nfields) {
+      const gu8* p = row + q->offset[f];
+      const uint32_t b = q->bytes[f];
+      hi[f] = 0u;
+      if (b == 8u) { lo[f] = g_ld4(p); hi[f] = g_ld4(p + 4); }
+      else if (b == 4u) lo[f] = g_ld4(p);
+      else if (b == 2u) lo[f] = g_ld2(p);
+      else lo[f] = (uint32_t)p[0];
+    }
+  uint32_t met = 0;      // the clauses that have a true term
+#pragma unroll
+  for (int f = 0; f < WH_MAX_FIELDS; f++)
+    if ((uint32_t)f < nfields) {
+      v[f] = (uint64_t)hi[f] << 32 | lo[f];
+      for (uint32_t t = q->first[f], t1 = q->first[f + 1]; t < t1; t++) {
+        const WherePred p = q->test[t];
+        met |= where_test(p, v[f]) ? q->bit[t] : 0u;
+      }
+    }
+  return met == q->clauses;
 }
 
 }  // namespace bamd

@@ -13,6 +13,8 @@ back by a device index tensor: index_select on the compressed table, one blosc_g
 table - by blosc_gpu_where_packed (include/blosc_gpu_where.h), holding one pass of plaintext at a time.
 `aggregate_rows` reduces a column over such rows - count, sum, min, max and the rows of the extremes, per chunk and for the table - by
 blosc_gpu_aggregate_packed (include/blosc_gpu_aggregate.h), without an index table.
+`where_rows_clauses` / `aggregate_rows_clauses` are the two for SEVERAL comparisons - an AND of OR clauses over any columns: a range, two
+columns, a small key set - in one call and one decode (include/blosc_gpu_clauses.h).
 
 Like blpk.py's device functions this module only drives the library: `lib` is the ctypes handle (load() of the package), memory comes
 from a `mem` with blpk.TorchMem's alloc().  There is no CPU implementation: without the library and a GPU the calls fail.
@@ -293,6 +295,91 @@ def aggregate_rows(lib, container, offsets, meta, column=0, where=None, mem=None
     agg = pkg.RowAggregate(row_bytes, lib=lib)
     if agg.packed(container.data_ptr(), int(container.numel()), list(offsets), pkg.field(kind, element, offset=column * element), pred, stream) != 0:
         raise RuntimeError(f"blosc_gpu_aggregate_packed failed; rows per chunk (negative: the chunk's code): {agg.chunk_rows()}")
+    if agg.chunk_rows() != [int(shape[0]) for _, shape in meta]:
+        raise RuntimeError(f"the container does not hold this table: rows per chunk {agg.chunk_rows()}")
+    if agg.unread():
+        raise RuntimeError(f"{agg.unread()} of {sum(agg.chunk_rows())} rows were not read (chunks that do not decode: {agg.chunk_status()})")
+
+    def scalar(raw):
+        return torch.tensor(list(raw[:element]), dtype=torch.uint8).view(dtype)[0].item()
+
+    def result(a, chunks):
+        total = a.sum.f if dtype.is_floating_point else (a.sum.i if kind == pkg.FIELD_INT else a.sum.u)
+        return Aggregated(int(a.count), int(a.nans), total, scalar(a.min) if a.min_row >= 0 else None, scalar(a.max) if a.max_row >= 0 else None,
+                          int(a.min_row) if a.min_row >= 0 else None, int(a.max_row) if a.max_row >= 0 else None, chunks)
+
+    return result(agg.total(), [result(c, None) for c in agg.chunks()])
+
+
+def _clause_terms(pkg, meta, call, clauses, *columns):
+    """`clauses` as the list of Term a call of include/blosc_gpu_clauses.h takes, and what _table_fields reads from `meta` (`columns`: more
+    columns to check).  clauses: a list that is ANDed; each entry is (op, value, column) or a list of such triples that is ORed - entry k is
+    clause k.  op and value are where_rows': the value goes through _where_predicate unchanged.  ValueError for an entry that is neither, an
+    empty OR list, more than 16 clauses and more than 16 terms"""
+    groups = []
+    for entry in clauses or []:
+        group = [entry] if isinstance(entry, tuple) else list(entry) if isinstance(entry, list) else None
+        if group is None or any(not isinstance(t, tuple) or len(t) != 3 for t in group):
+            raise ValueError(f"clause {entry!r}: (op, value, column) or a list of such triples")
+        if not group:
+            raise ValueError("an OR list without a comparison matches no row: leave the clause out or give it one")
+        groups.append(group)
+    if len(groups) > pkg.MAX_TERMS or sum(map(len, groups)) > pkg.MAX_TERMS:
+        raise ValueError(f"{len(groups)} clauses of {sum(map(len, groups))} terms: a call takes {pkg.MAX_TERMS} of each")
+    dtype, kind, element, row_bytes = _table_fields(pkg, meta, call, *columns, *[t[2] for g in groups for t in g])
+    terms = [pkg.term(_where_predicate(pkg, dtype, kind, element, op, value, column), k) for k, g in enumerate(groups) for op, value, column in g]
+    return terms, dtype, kind, element, row_bytes
+
+
+def where_rows_clauses(lib, container, offsets, meta, clauses, max_matches=None, mem=None, stream=None):
+    """where_rows for several comparisons at once: torch.nonzero of an AND of OR clauses over the columns of the table pack_rows packed, by
+    blosc_gpu_where_clauses_packed (include/blosc_gpu_clauses.h) - one decode, whatever the number of comparisons.  clauses: a list that is
+    ANDed; each entry is (op, value, column) or a list of such triples that is ORed:
+        [(">=", t0, 0), ("<", t1, 0)]                        t0 <= column 0 < t1
+        [(">=", t0, 0), [("==", 3, 1), ("==", 5, 1)]]        column 0 >= t0 and column 1 in {3, 5}
+    op, value and column are where_rows', with the same rounding to a floating-point dtype and the same ValueError for a value an integer
+    dtype does not hold; at most 16 comparisons in at most 16 clauses, at least one.  max_matches, the two calls without it, the result
+    (index, total) and the errors raised are where_rows'."""
+    import torch
+    pkg = _sibling("", "__init__.py")
+    mem = mem if mem is not None else _sibling("blpk", "blpk.py").TorchMem()
+    pkg.declare_clauses(lib)
+    terms, dtype, kind, element, row_bytes = _clause_terms(pkg, meta, "blosc_gpu_where_clauses_packed", clauses)
+    if not terms:
+        raise ValueError("where_rows_clauses takes at least one comparison")
+    where = pkg.RowWhereClauses(row_bytes, lib=lib)
+
+    def call(ptr, capacity):
+        if where.packed(container.data_ptr(), int(container.numel()), list(offsets), terms, ptr, capacity, stream) != 0:
+            raise RuntimeError(f"blosc_gpu_where_clauses_packed failed; rows per chunk (negative: the chunk's code): {where.chunk_rows()}")
+        if where.chunk_rows() != [int(shape[0]) for _, shape in meta]:
+            raise RuntimeError(f"the container does not hold this table: rows per chunk {where.chunk_rows()}")
+        if where.unread():
+            raise RuntimeError(f"{where.unread()} of {sum(where.chunk_rows())} rows were not read (chunks that do not decode: {where.chunk_matches()})")
+        return where.total()
+
+    if max_matches is not None and max_matches < 0:
+        raise ValueError("max_matches must not be negative")
+    total = call(None, 0) if max_matches is None else None      # the counting call
+    capacity = total if max_matches is None else int(max_matches)
+    dest, keep = mem.alloc(capacity * 8)
+    if capacity:
+        total = call(dest, capacity)
+    elif total is None:
+        total = call(None, 0)
+    return keep[:min(total, capacity) * 8].view(torch.int64), total
+
+
+def aggregate_rows_clauses(lib, container, offsets, meta, column=0, clauses=None, mem=None, stream=None):
+    """aggregate_rows over the rows that an AND of OR clauses lets through (clauses: where_rows_clauses'; None or empty: every row), by ONE
+    blosc_gpu_aggregate_clauses_packed (include/blosc_gpu_clauses.h).  Returns an Aggregated, as aggregate_rows does, and raises as it does."""
+    import torch
+    pkg = _sibling("", "__init__.py")
+    pkg.declare_clauses(lib)
+    terms, dtype, kind, element, row_bytes = _clause_terms(pkg, meta, "blosc_gpu_aggregate_clauses_packed", clauses, column)
+    agg = pkg.RowAggregateClauses(row_bytes, lib=lib)
+    if agg.packed(container.data_ptr(), int(container.numel()), list(offsets), pkg.field(kind, element, offset=column * element), terms, stream) != 0:
+        raise RuntimeError(f"blosc_gpu_aggregate_clauses_packed failed; rows per chunk (negative: the chunk's code): {agg.chunk_rows()}")
     if agg.chunk_rows() != [int(shape[0]) for _, shape in meta]:
         raise RuntimeError(f"the container does not hold this table: rows per chunk {agg.chunk_rows()}")
     if agg.unread():

@@ -1,7 +1,7 @@
 """c-blosc_amd — Python-side loader for libblosc_amd.so (ctypes; test / bench plumbing only).
 
 The product is the C-ABI shared library built from ``csrc/`` (see ``include/blosc.h`` and
-``include/blosc_gpu.h``, ``include/blosc_gpu_packed.h``, ``include/blosc_gpu_params.h``, ``include/blosc_gpu_select.h``, ``include/blosc_gpu_getitem.h``, ``include/blosc_gpu_take.h``, ``include/blosc_gpu_put.h``, ``include/blosc_gpu_where.h``, ``include/blosc_gpu_aggregate.h``, ``include/blosc_gpu_clauses.h``, ``include/blosc_gpu_checksum.h``).  This module only locates it, declares argument types and offers small
+``include/blosc_gpu.h``, ``include/blosc_gpu_packed.h``, ``include/blosc_gpu_params.h``, ``include/blosc_gpu_select.h``, ``include/blosc_gpu_getitem.h``, ``include/blosc_gpu_take.h``, ``include/blosc_gpu_put.h``, ``include/blosc_gpu_where.h``, ``include/blosc_gpu_aggregate.h``, ``include/blosc_gpu_clauses.h``, ``include/blosc_gpu_zones.h``, ``include/blosc_gpu_checksum.h``).  This module only locates it, declares argument types and offers small
 numpy conveniences that mirror how the reference is driven from Python through ctypes
 (SURVEY.md §A.8).  There is no CPU implementation here: if the library is missing, ``load()``
 raises; if there is no GPU, the library's calls return errors.
@@ -60,7 +60,12 @@ AGGREGATE_SYMBOLS = [   # include/blosc_gpu_aggregate.h
 CLAUSES_SYMBOLS = [     # include/blosc_gpu_clauses.h
     "blosc_gpu_where_clauses_batch", "blosc_gpu_where_clauses_packed", "blosc_gpu_aggregate_clauses_batch", "blosc_gpu_aggregate_clauses_packed",
 ]
+ZONES_SYMBOLS = [       # include/blosc_gpu_zones.h
+    "blosc_gpu_aggregate_fields_batch", "blosc_gpu_aggregate_fields_packed", "blosc_gpu_zone_excludes", "blosc_gpu_where_zoned_batch",
+    "blosc_gpu_where_zoned_packed", "blosc_gpu_aggregate_zoned_batch", "blosc_gpu_aggregate_zoned_packed",
+]
 MAX_TERMS = 16          # BLOSC_GPU_MAX_TERMS; clause numbers are 0 ... 15
+MAX_ZONE_FIELDS = 16    # BLOSC_GPU_MAX_ZONE_FIELDS
 WHERE_EQ, WHERE_NE, WHERE_LT, WHERE_LE, WHERE_GT, WHERE_GE = range(6)
 FIELD_UINT, FIELD_INT, FIELD_FLOAT, FIELD_BFLOAT16 = range(4)
 CHECKSUM_ADLER32, CHECKSUM_CRC32 = 1, 2
@@ -251,6 +256,15 @@ def _signatures():
         "blosc_gpu_where_clauses_packed": ([i, vp, sz, zp, sz, P(Term), i, vp, sz, zp, ip, ip, zp, vp], i),
         "blosc_gpu_aggregate_clauses_batch": ([i, pp, sz, P(Field), P(Term), i, P(Aggregate), P(Aggregate), ip, ip, zp, vp], i),
         "blosc_gpu_aggregate_clauses_packed": ([i, vp, sz, zp, sz, P(Field), P(Term), i, P(Aggregate), P(Aggregate), ip, ip, zp, vp], i),
+        # include/blosc_gpu_zones.h
+        "blosc_gpu_aggregate_fields_batch": ([i, pp, sz, P(Field), i, P(Term), i, P(Aggregate), P(Aggregate), ip, ip, zp, vp], i),
+        "blosc_gpu_aggregate_fields_packed": ([i, vp, sz, zp, sz, P(Field), i, P(Term), i, P(Aggregate), P(Aggregate), ip, ip, zp, vp], i),
+        "blosc_gpu_zone_excludes": ([P(Term), i, P(Field), i, P(Aggregate), C.c_uint64], i),
+        "blosc_gpu_where_zoned_batch": ([i, pp, sz, P(Term), i, P(Field), i, P(Aggregate), vp, sz, zp, ip, ip, zp, P(C.c_uint8), vp], i),
+        "blosc_gpu_where_zoned_packed": ([i, vp, sz, zp, sz, P(Term), i, P(Field), i, P(Aggregate), vp, sz, zp, ip, ip, zp, P(C.c_uint8), vp], i),
+        "blosc_gpu_aggregate_zoned_batch": ([i, pp, sz, P(Field), P(Term), i, P(Field), i, P(Aggregate), P(Aggregate), P(Aggregate), ip, ip, zp, P(C.c_uint8), vp], i),
+        "blosc_gpu_aggregate_zoned_packed": ([i, vp, sz, zp, sz, P(Field), P(Term), i, P(Field), i, P(Aggregate), P(Aggregate), P(Aggregate), ip, ip, zp,
+                                              P(C.c_uint8), vp], i),
         # include/blosc_gpu_checksum.h
         "blosc_gpu_checksum_batch": ([i, i, pp, zp, P(C.c_uint), vp], i),
         "blosc_gpu_checksum_packed": ([i, i, vp, sz, zp, zp, P(C.c_uint), vp], i),
@@ -281,7 +295,7 @@ def declare(L):
     return L
 
 
-declare_packed = declare_params = declare_select = declare_getitem = declare_take = declare_put = declare_where = declare_aggregate = declare_clauses = declare_checksum = declare    # the names from when every header had a function of its own
+declare_packed = declare_params = declare_select = declare_getitem = declare_take = declare_put = declare_where = declare_aggregate = declare_clauses = declare_zones = declare_checksum = declare    # the names from when every header had a function of its own
 
 
 # ---- numpy conveniences (host buffers through the stock entry points) --------------------------
@@ -667,6 +681,131 @@ class RowAggregateClauses(RowAggregate):
         return self.lib.blosc_gpu_aggregate_clauses_packed(self.nchunks, container, containersize, (C.c_size_t * (self.nchunks + 1))(*offsets), self.row_bytes,
                                                            C.byref(fld), table, n, C.byref(self.result), self.per_chunk, self.status, self.rows,
                                                            C.byref(self.nunread), stream)
+
+
+def fields_table(fields):
+    """(the host array of blosc_gpu_field a call takes, its length) from a list of Field; no fields: (None, 0)"""
+    rows = list(fields or [])
+    return ((Field * len(rows))(*rows) if rows else None), len(rows)
+
+
+class RowAggregateFields:
+    """Helper for blosc_gpu_aggregate_fields_* (include/blosc_gpu_zones.h): the aggregates of up to 16 Field of the rows a list of Term lets
+    through (None or empty: every row), in ONE decode.  batch() and packed() return the call's answer.  totals() is one Aggregate per field,
+    chunks() every chunk's list of them, entries() the ctypes array [nchunks * nfields], chunk-major - with no terms, the zone map the zoned
+    calls read; chunk_status(), chunk_rows() and unread() are RowAggregate's."""
+
+    def __init__(self, row_bytes, lib=None):
+        self.row_bytes = row_bytes
+        self.lib = lib if lib is not None else load()
+        self._outputs(0, 1)
+
+    def _outputs(self, nchunks, nfields):
+        self.nchunks, self.nfields = nchunks, nfields
+        self.result = (Aggregate * max(nfields, 1))()
+        self.per_chunk = (Aggregate * max(nchunks * nfields, 1))()
+        self.status = (C.c_int * max(nchunks, 1))()
+        self.rows = (C.c_int * max(nchunks, 1))()
+        self.nunread = C.c_size_t(0)
+
+    def batch(self, src_ptrs, fields, terms=None, stream=None):
+        ftab, nf = fields_table(fields)
+        self._outputs(len(src_ptrs), nf)
+        table, n = terms_table(terms)
+        return self.lib.blosc_gpu_aggregate_fields_batch(self.nchunks, (C.c_void_p * max(self.nchunks, 1))(*src_ptrs), self.row_bytes, ftab, nf, table, n,
+                                                         self.result, self.per_chunk, self.status, self.rows, C.byref(self.nunread), stream)
+
+    def packed(self, container, containersize, offsets, fields, terms=None, stream=None):
+        ftab, nf = fields_table(fields)
+        self._outputs(len(offsets) - 1, nf)
+        table, n = terms_table(terms)
+        return self.lib.blosc_gpu_aggregate_fields_packed(self.nchunks, container, containersize, (C.c_size_t * (self.nchunks + 1))(*offsets), self.row_bytes,
+                                                          ftab, nf, table, n, self.result, self.per_chunk, self.status, self.rows, C.byref(self.nunread),
+                                                          stream)
+
+    def totals(self):
+        return list(self.result)[:self.nfields]
+
+    def entries(self):
+        return self.per_chunk
+
+    def chunks(self):
+        return [list(self.per_chunk)[k * self.nfields:(k + 1) * self.nfields] for k in range(self.nchunks)]
+
+    def chunk_status(self):
+        return list(self.status)[:self.nchunks]
+
+    def chunk_rows(self):
+        return list(self.rows)[:self.nchunks]
+
+    def unread(self):
+        return int(self.nunread.value)
+
+
+def zone_excludes(terms, zfields, entries, chunk_rows, lib=None):
+    """blosc_gpu_zone_excludes (include/blosc_gpu_zones.h): 1 if no row of a chunk of chunk_rows rows, whose fields `zfields` the Aggregate
+    `entries` describe, can pass the list of Term; 0 if one may; negative for arguments the rule refuses.  Host only"""
+    L = lib if lib is not None else load()
+    table, n = terms_table(terms)
+    ftab, nf = fields_table(zfields)
+    etab = (Aggregate * nf)(*entries) if nf else None
+    return L.blosc_gpu_zone_excludes(table, n, ftab, nf, etab, chunk_rows)
+
+
+class RowWhereZoned(RowWhere):
+    """RowWhereClauses through blosc_gpu_where_zoned_* (include/blosc_gpu_zones.h): batch() and packed() take, behind the list of Term, the
+    zone fields (a list of Field) and the map - a ctypes array of Aggregate [nchunks * len(zfields)], chunk-major, RowAggregateFields.entries()
+    of a call without terms.  pruned() is 1 for every chunk that was not decoded.  The other outputs are RowWhere's."""
+
+    def _zoned(self, nchunks):
+        self._outputs(nchunks)
+        self.skipped = (C.c_uint8 * max(nchunks, 1))()
+
+    def batch(self, src_ptrs, terms, zfields, zones, index_out, capacity, stream=None):
+        self._zoned(len(src_ptrs))
+        table, n = terms_table(terms)
+        ftab, nf = fields_table(zfields)
+        return self.lib.blosc_gpu_where_zoned_batch(self.nchunks, (C.c_void_p * max(self.nchunks, 1))(*src_ptrs), self.row_bytes, table, n, ftab, nf, zones,
+                                                    index_out, capacity, C.byref(self.ntotal), self.matches, self.rows, C.byref(self.nunread), self.skipped,
+                                                    stream)
+
+    def packed(self, container, containersize, offsets, terms, zfields, zones, index_out, capacity, stream=None):
+        self._zoned(len(offsets) - 1)
+        table, n = terms_table(terms)
+        ftab, nf = fields_table(zfields)
+        return self.lib.blosc_gpu_where_zoned_packed(self.nchunks, container, containersize, (C.c_size_t * (self.nchunks + 1))(*offsets), self.row_bytes,
+                                                     table, n, ftab, nf, zones, index_out, capacity, C.byref(self.ntotal), self.matches, self.rows,
+                                                     C.byref(self.nunread), self.skipped, stream)
+
+    def pruned(self):
+        return list(self.skipped)[:self.nchunks]
+
+
+class RowAggregateZoned(RowAggregate):
+    """RowAggregateClauses through blosc_gpu_aggregate_zoned_* (include/blosc_gpu_zones.h): zfields, zones and pruned() as in RowWhereZoned."""
+
+    def _zoned(self, nchunks):
+        self._outputs(nchunks)
+        self.skipped = (C.c_uint8 * max(nchunks, 1))()
+
+    def batch(self, src_ptrs, fld, terms, zfields, zones, stream=None):
+        self._zoned(len(src_ptrs))
+        table, n = terms_table(terms)
+        ftab, nf = fields_table(zfields)
+        return self.lib.blosc_gpu_aggregate_zoned_batch(self.nchunks, (C.c_void_p * max(self.nchunks, 1))(*src_ptrs), self.row_bytes, C.byref(fld), table, n,
+                                                        ftab, nf, zones, C.byref(self.result), self.per_chunk, self.status, self.rows, C.byref(self.nunread),
+                                                        self.skipped, stream)
+
+    def packed(self, container, containersize, offsets, fld, terms, zfields, zones, stream=None):
+        self._zoned(len(offsets) - 1)
+        table, n = terms_table(terms)
+        ftab, nf = fields_table(zfields)
+        return self.lib.blosc_gpu_aggregate_zoned_packed(self.nchunks, container, containersize, (C.c_size_t * (self.nchunks + 1))(*offsets), self.row_bytes,
+                                                         C.byref(fld), table, n, ftab, nf, zones, C.byref(self.result), self.per_chunk, self.status, self.rows,
+                                                         C.byref(self.nunread), self.skipped, stream)
+
+    def pruned(self):
+        return list(self.skipped)[:self.nchunks]
 
 
 def checksums(kind, ptrs, sizes, lib=None, stream=None):

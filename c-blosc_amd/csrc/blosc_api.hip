@@ -25,6 +25,7 @@
 #include "../../include/blosc_gpu_where.h"
 #include "../../include/blosc_gpu_aggregate.h"
 #include "../../include/blosc_gpu_clauses.h"
+#include "../../include/blosc_gpu_zones.h"
 #include "../../include/blosc_gpu_checksum.h"
 #include "blosc_format.h"
 #include "dev_types.h"
@@ -872,6 +873,188 @@ int blosc_gpu_aggregate_clauses_packed(int nchunks, const void* container, size_
   if (nchunks > 0 && (!container || !offsets)) return -1;
   return aggregate_clauses_call(nchunks, jobs_from_spans(nchunks, container, containersize, offsets, nullptr, BLOSC_MIN_HEADER_LENGTH), row_bytes, f, w,
                                 total_out, chunk_out, chunk_status_out, chunk_rows_out, unread_out, stream);
+}
+
+// ---- zone maps (include/blosc_gpu_zones.h) ----------------------------------------------------------
+static_assert(BLOSC_GPU_MAX_ZONE_FIELDS == 16, "blosc_gpu_zones.h");
+static uint64_t little_endian(const uint8_t* p, uint32_t bytes) {
+  uint64_t v = 0;
+  for (uint32_t i = 0; i < bytes; i++) v |= (uint64_t)p[i] << (8 * i);
+  return v;
+}
+// fields_opening(): nfields fields through aggregate_opening(), the list through terms_opening() without an aggregated field in front
+static int fields_opening(int nchunks, size_t row_bytes, const blosc_gpu_field* fields, int nfields, const blosc_gpu_term* terms, int nterms, AggField* f, WhereTerms* w) {
+  if (nfields < 1 || nfields > BLOSC_GPU_MAX_ZONE_FIELDS || !fields) return -1;
+  WherePred unused;
+  for (int k = 0; k < nfields; k++) {
+    const int c = aggregate_opening(nchunks, row_bytes, &fields[k], nullptr, &f[k], &unused);
+    if (c != kGo) return c;
+  }
+  return terms_opening(nchunks, row_bytes, terms, nterms, 0, nullptr, w);
+}
+static int fields_call(int nchunks, const Table<Job>& jobs, size_t row_bytes, const AggField* f, int nfields, const WhereTerms& w, blosc_gpu_aggregate* total_out,
+                       blosc_gpu_aggregate* chunk_out, int* chunk_status_out, int* chunk_rows_out, size_t* unread_out, void* stream) {
+  if (!jobs) return -1;
+  if (nchunks == 0) {      // no chunk to read: the totals of nothing
+    for (int k = 0; total_out && k < nfields; k++) { memset(&total_out[k], 0, sizeof *total_out); total_out[k].min_row = total_out[k].max_row = -1; }
+    if (unread_out) *unread_out = 0;
+    return 0;
+  }
+  return engine_aggregate_fields(nchunks, jobs.get(), row_bytes, f, nfields, w, (AggResult*)total_out, (AggResult*)chunk_out, chunk_status_out, chunk_rows_out,
+                                 unread_out, (hipStream_t)stream);
+}
+int blosc_gpu_aggregate_fields_batch(int nchunks, const void* const* src, size_t row_bytes, const blosc_gpu_field* fields, int nfields, const blosc_gpu_term* terms,
+                                     int nterms, blosc_gpu_aggregate* total_out, blosc_gpu_aggregate* chunk_out, int* chunk_status_out, int* chunk_rows_out,
+                                     size_t* unread_out, void* stream) {
+  AggField f[BLOSC_GPU_MAX_ZONE_FIELDS]; WhereTerms w;
+  const int c = fields_opening(nchunks, row_bytes, fields, nfields, terms, nterms, f, &w);
+  if (c != kGo) return c;
+  if (nchunks > 0 && !src) return -1;
+  return fields_call(nchunks, jobs_from_arrays(nchunks, src, nullptr, nullptr, nullptr), row_bytes, f, nfields, w, total_out, chunk_out, chunk_status_out,
+                     chunk_rows_out, unread_out, stream);
+}
+int blosc_gpu_aggregate_fields_packed(int nchunks, const void* container, size_t containersize, const size_t* offsets, size_t row_bytes,
+                                      const blosc_gpu_field* fields, int nfields, const blosc_gpu_term* terms, int nterms, blosc_gpu_aggregate* total_out,
+                                      blosc_gpu_aggregate* chunk_out, int* chunk_status_out, int* chunk_rows_out, size_t* unread_out, void* stream) {
+  AggField f[BLOSC_GPU_MAX_ZONE_FIELDS]; WhereTerms w;
+  const int c = fields_opening(nchunks, row_bytes, fields, nfields, terms, nterms, f, &w);
+  if (c != kGo) return c;
+  if (nchunks > 0 && (!container || !offsets)) return -1;
+  return fields_call(nchunks, jobs_from_spans(nchunks, container, containersize, offsets, nullptr, BLOSC_MIN_HEADER_LENGTH), row_bytes, f, nfields, w, total_out,
+                     chunk_out, chunk_status_out, chunk_rows_out, unread_out, stream);
+}
+
+// The rule, as the header states it: whether a term can be true in a chunk whose field the INFORMING entry e describes
+static bool zone_term_can_be_true(const blosc_gpu_predicate& q, const AggField& f, const blosc_gpu_aggregate& e) {
+  bool nan = false, unused;
+  const int64_t k = where_key(little_endian(q.value, f.bytes), f.kind, f.bytes, f.inf, &nan);
+  if (nan || e.nans == e.rows) return q.op == BLOSC_GPU_WHERE_NE;
+  const int64_t lo = where_key(little_endian(e.min, f.bytes), f.kind, f.bytes, f.inf, &unused);
+  const int64_t hi = where_key(little_endian(e.max, f.bytes), f.kind, f.bytes, f.inf, &unused);
+  switch (q.op) {
+    case BLOSC_GPU_WHERE_LT: return lo < k;
+    case BLOSC_GPU_WHERE_LE: return lo <= k;
+    case BLOSC_GPU_WHERE_GT: return hi > k;
+    case BLOSC_GPU_WHERE_GE: return hi >= k;
+    case BLOSC_GPU_WHERE_EQ: return lo <= k && k <= hi;
+    default: return !(lo == k && hi == k && e.nans == 0);
+  }
+}
+int blosc_gpu_zone_excludes(const blosc_gpu_term* terms, int nterms, const blosc_gpu_field* zfields, int nzfields, const blosc_gpu_aggregate* entry,
+                            uint64_t chunk_rows) {
+  if (nterms < 0 || nterms > BLOSC_GPU_MAX_TERMS || nzfields < 0 || nzfields > BLOSC_GPU_MAX_ZONE_FIELDS) return -1;
+  if ((nterms && !terms) || (nzfields && (!zfields || !entry))) return -1;
+  AggField unused;
+  for (int f = 0; f < nzfields; f++)
+    if (zfields[f].pad_ != 0 || !field_of_table(zfields[f].kind, zfields[f].bytes, 0, 8, &unused)) return -1;
+  uint32_t occurs = 0, open = 0;      // the clauses of the list; those with a term that can be true
+  for (int t = 0; t < nterms; t++) {
+    const blosc_gpu_predicate& q = terms[t].test;
+    AggField tf;
+    if (terms[t].clause >= 16 || terms[t].pad_ != 0 || q.op < BLOSC_GPU_WHERE_EQ || q.op > BLOSC_GPU_WHERE_GE) return -1;
+    if (!field_of_table(q.kind, q.bytes, 0, 8, &tf)) return -1;
+    bool can = true;
+    for (int f = 0; f < nzfields; f++) {
+      const blosc_gpu_aggregate& e = entry[f];
+      if (zfields[f].offset != q.offset || zfields[f].bytes != q.bytes || zfields[f].kind != q.kind) continue;
+      if (e.rows != chunk_rows || !chunk_rows || e.count != e.rows || !((e.min_row >= 0 && e.max_row >= 0) || e.nans == e.rows)) continue;      // no information
+      can = zone_term_can_be_true(q, tf, e);
+      break;
+    }
+    occurs |= 1u << terms[t].clause;
+    if (can) open |= 1u << terms[t].clause;
+  }
+  return occurs != open ? 1 : 0;
+}
+
+// zones_opening(): the map's own checks;  zone_prune(): what the engine asks behind the census (engine.h: RowPrune) - the cheap guard, then the rule
+namespace {
+struct ZoneMap { const blosc_gpu_term* terms; int nterms; const blosc_gpu_field* zfields; int nzfields; const blosc_gpu_aggregate* zones; };
+}  // namespace
+static int zones_opening(size_t row_bytes, const blosc_gpu_field* zfields, int nzfields, const blosc_gpu_aggregate* zones) {
+  if (nzfields < 0 || nzfields > BLOSC_GPU_MAX_ZONE_FIELDS || (nzfields && (!zfields || !zones))) return -1;
+  AggField unused;
+  for (int f = 0; f < nzfields; f++)
+    if (zfields[f].pad_ != 0 || !field_of_table(zfields[f].kind, zfields[f].bytes, zfields[f].offset, row_bytes, &unused)) return -1;
+  return kGo;
+}
+static int zone_prune(const void* ctx, size_t chunk, uint64_t rows) {
+  const ZoneMap& z = *(const ZoneMap*)ctx;
+  if (!z.nzfields) return 0;
+  const blosc_gpu_aggregate* entry = z.zones + chunk * (size_t)z.nzfields;
+  for (int f = 0; f < z.nzfields; f++)
+    if (entry[f].rows != 0 && entry[f].rows != rows) return -1;      // a map of another container
+  return blosc_gpu_zone_excludes(z.terms, z.nterms, z.zfields, z.nzfields, entry, rows);
+}
+static int where_zoned_call(int nchunks, const Table<Job>& jobs, size_t row_bytes, const WhereTerms& w, const ZoneMap& z, int64_t* index_out, size_t capacity,
+                            size_t* total_out, int* chunk_matches_out, int* chunk_rows_out, size_t* unread_out, uint8_t* chunk_pruned_out, void* stream) {
+  if (!jobs) return -1;
+  if (nchunks == 0) { if (total_out) *total_out = 0; if (unread_out) *unread_out = 0; return 0; }
+  const RowPrune prune{zone_prune, &z, chunk_pruned_out};
+  return engine_where_terms(nchunks, jobs.get(), row_bytes, w, index_out, capacity, total_out, chunk_matches_out, chunk_rows_out, unread_out, (hipStream_t)stream,
+                            &prune);
+}
+int blosc_gpu_where_zoned_batch(int nchunks, const void* const* src, size_t row_bytes, const blosc_gpu_term* terms, int nterms, const blosc_gpu_field* zfields,
+                                int nzfields, const blosc_gpu_aggregate* zones, int64_t* index_out, size_t capacity, size_t* total_out, int* chunk_matches_out,
+                                int* chunk_rows_out, size_t* unread_out, uint8_t* chunk_pruned_out, void* stream) {
+  WhereTerms w;
+  int c = where_clauses_opening(nchunks, row_bytes, terms, nterms, index_out, capacity, &w);
+  if (c == kGo) c = zones_opening(row_bytes, zfields, nzfields, zones);
+  if (c != kGo) return c;
+  if (nchunks > 0 && !src) return -1;
+  const ZoneMap z{terms, nterms, zfields, nzfields, zones};
+  return where_zoned_call(nchunks, jobs_from_arrays(nchunks, src, nullptr, nullptr, nullptr), row_bytes, w, z, index_out, capacity, total_out, chunk_matches_out,
+                          chunk_rows_out, unread_out, chunk_pruned_out, stream);
+}
+int blosc_gpu_where_zoned_packed(int nchunks, const void* container, size_t containersize, const size_t* offsets, size_t row_bytes, const blosc_gpu_term* terms,
+                                 int nterms, const blosc_gpu_field* zfields, int nzfields, const blosc_gpu_aggregate* zones, int64_t* index_out, size_t capacity,
+                                 size_t* total_out, int* chunk_matches_out, int* chunk_rows_out, size_t* unread_out, uint8_t* chunk_pruned_out, void* stream) {
+  WhereTerms w;
+  int c = where_clauses_opening(nchunks, row_bytes, terms, nterms, index_out, capacity, &w);
+  if (c == kGo) c = zones_opening(row_bytes, zfields, nzfields, zones);
+  if (c != kGo) return c;
+  if (nchunks > 0 && (!container || !offsets)) return -1;
+  // index_out against the source container as a whole (the engine checks it against every chunk)
+  const uintptr_t s0 = (uintptr_t)container, s1 = s0 + containersize, d0 = (uintptr_t)index_out, d1 = d0 + capacity * sizeof(int64_t);
+  if (nchunks > 0 && capacity && containersize && s0 < d1 && d0 < s1) return -1;
+  const ZoneMap z{terms, nterms, zfields, nzfields, zones};
+  return where_zoned_call(nchunks, jobs_from_spans(nchunks, container, containersize, offsets, nullptr, BLOSC_MIN_HEADER_LENGTH), row_bytes, w, z, index_out,
+                          capacity, total_out, chunk_matches_out, chunk_rows_out, unread_out, chunk_pruned_out, stream);
+}
+static int aggregate_zoned_call(int nchunks, const Table<Job>& jobs, size_t row_bytes, const AggField& f, const WhereTerms& w, const ZoneMap& z,
+                                blosc_gpu_aggregate* total_out, blosc_gpu_aggregate* chunk_out, int* chunk_status_out, int* chunk_rows_out, size_t* unread_out,
+                                uint8_t* chunk_pruned_out, void* stream) {
+  if (!jobs) return -1;
+  if (nchunks == 0) return aggregate_call(0, jobs, row_bytes, f, nullptr, total_out, chunk_out, chunk_status_out, chunk_rows_out, unread_out, stream);
+  const RowPrune prune{zone_prune, &z, chunk_pruned_out};
+  return engine_aggregate_terms(nchunks, jobs.get(), row_bytes, f, w, (AggResult*)total_out, (AggResult*)chunk_out, chunk_status_out, chunk_rows_out, unread_out,
+                                (hipStream_t)stream, &prune);
+}
+int blosc_gpu_aggregate_zoned_batch(int nchunks, const void* const* src, size_t row_bytes, const blosc_gpu_field* field, const blosc_gpu_term* terms, int nterms,
+                                    const blosc_gpu_field* zfields, int nzfields, const blosc_gpu_aggregate* zones, blosc_gpu_aggregate* total_out,
+                                    blosc_gpu_aggregate* chunk_out, int* chunk_status_out, int* chunk_rows_out, size_t* unread_out, uint8_t* chunk_pruned_out,
+                                    void* stream) {
+  AggField f; WhereTerms w;
+  int c = aggregate_clauses_opening(nchunks, row_bytes, field, terms, nterms, &f, &w);
+  if (c == kGo) c = zones_opening(row_bytes, zfields, nzfields, zones);
+  if (c != kGo) return c;
+  if (nchunks > 0 && !src) return -1;
+  const ZoneMap z{terms, nterms, zfields, nzfields, zones};
+  return aggregate_zoned_call(nchunks, jobs_from_arrays(nchunks, src, nullptr, nullptr, nullptr), row_bytes, f, w, z, total_out, chunk_out, chunk_status_out,
+                              chunk_rows_out, unread_out, chunk_pruned_out, stream);
+}
+int blosc_gpu_aggregate_zoned_packed(int nchunks, const void* container, size_t containersize, const size_t* offsets, size_t row_bytes, const blosc_gpu_field* field,
+                                     const blosc_gpu_term* terms, int nterms, const blosc_gpu_field* zfields, int nzfields, const blosc_gpu_aggregate* zones,
+                                     blosc_gpu_aggregate* total_out, blosc_gpu_aggregate* chunk_out, int* chunk_status_out, int* chunk_rows_out, size_t* unread_out,
+                                     uint8_t* chunk_pruned_out, void* stream) {
+  AggField f; WhereTerms w;
+  int c = aggregate_clauses_opening(nchunks, row_bytes, field, terms, nterms, &f, &w);
+  if (c == kGo) c = zones_opening(row_bytes, zfields, nzfields, zones);
+  if (c != kGo) return c;
+  if (nchunks > 0 && (!container || !offsets)) return -1;
+  const ZoneMap z{terms, nterms, zfields, nzfields, zones};
+  return aggregate_zoned_call(nchunks, jobs_from_spans(nchunks, container, containersize, offsets, nullptr, BLOSC_MIN_HEADER_LENGTH), row_bytes, f, w, z, total_out,
+                              chunk_out, chunk_status_out, chunk_rows_out, unread_out, chunk_pruned_out, stream);
 }
 
 // ---- adler32 / crc32 of many runs (include/blosc_gpu_checksum.h) ---------------------------------------

@@ -107,11 +107,24 @@ int engine_aggregate(int nchunks, const Job* chunks, size_t row_bytes, const Agg
 // The two calls above for a term list (include/blosc_gpu_clauses.h): the rows for which every clause of the list has a true term.  terms: the
 // caller's list as the kernels evaluate it (dev_types.h: WhereTerms; in aggregate its field 0 is `field`, and no terms let every row through).
 // Everything else as above: the same body runs behind another mark / tile kernel.
+// prune (include/blosc_gpu_zones.h; nullptr: none): behind the census excludes(ctx, chunk, its rows) is asked for every chunk - 1: the chunk
+// is not decoded and answers what a decoded chunk without a match answers, 0: it is, negative: the call answers -1 with nothing but
+// chunk_rows_out written.  pruned_out (host [nchunks], may be nullptr): 1 for every chunk that holds rows and was not decoded.
 struct WhereTerms;
+struct RowPrune {
+  int (*excludes)(const void* ctx, size_t chunk, uint64_t rows);
+  const void* ctx;
+  uint8_t* pruned_out;
+};
 int engine_where_terms(int nchunks, const Job* chunks, size_t row_bytes, const WhereTerms& terms, int64_t* index_out, size_t capacity, size_t* total_out,
-                       int* chunk_matches_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream);
+                       int* chunk_matches_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream, const RowPrune* prune = nullptr);
 int engine_aggregate_terms(int nchunks, const Job* chunks, size_t row_bytes, const AggField& field, const WhereTerms& terms, AggResult* total_out,
-                           AggResult* chunk_out, int* chunk_status_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream);
+                           AggResult* chunk_out, int* chunk_status_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream,
+                           const RowPrune* prune = nullptr);
+// engine_aggregate_terms for nfields fields in one decode (include/blosc_gpu_zones.h): terms holds the tested fields only (no field 0 of the
+// aggregate), total_out [nfields], chunk_out [nchunks * nfields] chunk-major; every entry is what engine_aggregate_terms answers for its field.
+int engine_aggregate_fields(int nchunks, const Job* chunks, size_t row_bytes, const AggField* fields, int nfields, const WhereTerms& terms, AggResult* total_out,
+                            AggResult* chunk_out, int* chunk_status_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream);
 
 // zlib's adler32 (kind 1) / crc32 (kind 2) of n runs in device memory (include/blosc_gpu_checksum.h): runs[i].src and runs[i].srcsize;
 // an empty run's pointer is never read.  digests[] is written only when the call answers 0.

@@ -29,6 +29,7 @@
 #include "k_put.hip"
 #include "k_where.hip"
 #include "k_aggregate.hip"
+#include "k_zones.hip"
 
 namespace bamd {
 
@@ -1833,6 +1834,7 @@ struct RowScan {
   std::vector<Header> hdrs; std::vector<Job> jobs; std::vector<TakeChunk> table;
   std::vector<int> rows_of, pass_of, code;      // rows_of: the chunk's rows or its negative code; code, negative: what the decoder answered
   std::vector<uint8_t> live;                    // [n], the caller's, between census() and deal()
+  std::vector<uint8_t> pruned;                  // [n] or empty, the caller's, in front of deal_tiles(): chunks that hold rows and are not to be decoded
   std::vector<uint8_t*> slot_of;                // the plaintext of a live chunk once its pass is decoded
   std::vector<uint32_t> tiles_of;
   size_t o_chunks = 0, o_tiles = 0, o_back = 0, o_ws = 0;
@@ -1905,11 +1907,24 @@ struct RowScan {
     std::vector<size_t> extra_of(n);
     live.assign(n, 0); tiles_of.assign(n, 0);
     for (size_t k = 0; k < n; k++) {
-      live[k] = rows_of[k] != 0;
-      tiles_of[k] = (uint32_t)(((size_t)rows_of[k] + WH_TILE - 1) / WH_TILE);
+      live[k] = rows_of[k] != 0 && !(pruned.size() && pruned[k]);
+      tiles_of[k] = live[k] ? (uint32_t)(((size_t)rows_of[k] + WH_TILE - 1) / WH_TILE) : 0u;      // a pruned chunk has no tile: nothing looks at it
       extra_of[k] = tile_bytes * tiles_of[k];
     }
     return deal(st, extra_of, std::min(g_getitem_pass_bytes.load(), (size_t)1 << 30), sizeof(WhereChunk), back_bytes);
+  }
+  // The zoned calls (include/blosc_gpu_zones.h), behind the census: the caller's rule on every chunk that holds rows.  false: the rule
+  // refused the call.  pruned_out (may be nullptr) is written once every chunk has been asked
+  bool prune(const RowPrune* by) {
+    if (!by) return true;
+    pruned.assign(n, 0);
+    for (size_t k = 0; k < n; k++) {
+      const int x = by->excludes(by->ctx, k, (uint64_t)rows_of[k]);
+      if (x < 0) return false;
+      pruned[k] = rows_of[k] != 0 && x > 0;
+    }
+    if (by->pruned_out) std::copy(pruned.begin(), pruned.end(), by->pruned_out);
+    return true;
   }
   const WhereChunk* d_chunks() const { return (const WhereChunk*)(D + o_chunks) + c0; }
   const uint32_t* d_tiles() const { return (const uint32_t*)(D + o_tiles) + c0 + pass; }
@@ -2191,7 +2206,7 @@ struct MarkPass {      // what a mark kernel is launched with
 }  // namespace
 template <class Mark>
 static int where_passes(int nchunks, const Job* chunks, size_t row_bytes, const WhereTerms* terms, Mark mark, int64_t* index_out, size_t capacity,
-                        size_t* total_out, int* chunk_matches_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream) {
+                        size_t* total_out, int* chunk_matches_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream, const RowPrune* prune = nullptr) {
   CtxGuard ctx; EngineState& st = *ctx.st;
   if (ensure_device(st)) return -1;
   // ---- the census; then index_out against every source - a call that fails the second writes nothing at all ----
@@ -2202,6 +2217,7 @@ static int where_passes(int nchunks, const Job* chunks, size_t row_bytes, const 
   if (!usable) { rs.rows_to(chunk_rows_out); return -1; }
   if (capacity && overlaps_a_source(rs.jobs, rs.hdrs, (uintptr_t)index_out, (uintptr_t)index_out + capacity * sizeof(int64_t))) return -1;
   rs.rows_to(chunk_rows_out);
+  if (!rs.prune(prune)) return -1;
   // ---- the passes: per tile its mask words, a count and a base; the running total and the chunks' counters come down at the end ----
   const size_t back_bytes = sizeof(uint64_t) + sizeof(uint32_t) * (n ? n : 1), o_terms = align_up(back_bytes, 16);
   if (rs.deal_tiles(st, sizeof(uint64_t) * WH_WORDS + sizeof(uint32_t) + sizeof(uint64_t), o_terms + (terms ? sizeof(WhereTerms) : 0))) return -1;
@@ -2267,7 +2283,7 @@ int engine_where(int nchunks, const Job* chunks, size_t row_bytes, const WherePr
   return where_passes(nchunks, chunks, row_bytes, nullptr, mark, index_out, capacity, total_out, chunk_matches_out, chunk_rows_out, unread_out, stream);
 }
 int engine_where_terms(int nchunks, const Job* chunks, size_t row_bytes, const WhereTerms& terms, int64_t* index_out, size_t capacity, size_t* total_out,
-                       int* chunk_matches_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream) {
+                       int* chunk_matches_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream, const RowPrune* prune) {
   auto mark = [](EngineState& st, hipStream_t stream, const MarkPass& m, const WhereTerms* d_terms) {
     ProfScope ps(st, stream, "k_where_mark_terms");
     hipLaunchKernelGGL(k_where_mark_terms, m.grid, dim3(WH_THREADS), 0, stream, m.d_chunks, m.d_tiles, m.in_pass, m.row_bytes, d_terms, m.d_masks, m.d_tile_count,
@@ -2275,7 +2291,7 @@ int engine_where_terms(int nchunks, const Job* chunks, size_t row_bytes, const W
     HIP_TRY(hipGetLastError());
     return 0;
   };
-  return where_passes(nchunks, chunks, row_bytes, &terms, mark, index_out, capacity, total_out, chunk_matches_out, chunk_rows_out, unread_out, stream);
+  return where_passes(nchunks, chunks, row_bytes, &terms, mark, index_out, capacity, total_out, chunk_matches_out, chunk_rows_out, unread_out, stream, prune);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2310,9 +2326,14 @@ struct TilesPass {      // what a tile kernel is launched with
   dim3 grid; const WhereChunk* d_chunks; const uint32_t* d_tiles; int in_pass; uint32_t row_bytes; AggPartial* d_partials;
 };
 }  // namespace
+// Several fields (include/blosc_gpu_zones.h): nf partials per tile and nf results per chunk, chunk-major; `tiles` receives the device address
+// of the field table, which goes up behind the term list, and k_aggregate_chunks_fields folds in k_aggregate_chunks' place.  several false:
+// one field, no table, and both launches take what they always took.  prune (nullptr: none): the zoned calls' rule, asked behind the census;
+// a chunk it excludes is in no launch and answers its rows and nothing else.
 template <class Tiles>
-static int aggregate_passes(int nchunks, const Job* chunks, size_t row_bytes, const AggField& field, const WhereTerms* terms, Tiles tiles, AggResult* total_out,
-                            AggResult* chunk_out, int* chunk_status_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream) {
+static int aggregate_passes(int nchunks, const Job* chunks, size_t row_bytes, const AggField* fields, size_t nf, bool several, const WhereTerms* terms, Tiles tiles,
+                            AggResult* total_out, AggResult* chunk_out, int* chunk_status_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream,
+                            const RowPrune* prune = nullptr) {
   CtxGuard ctx; EngineState& st = *ctx.st;
   if (ensure_device(st)) return -1;
   RowScan rs;
@@ -2320,14 +2341,19 @@ static int aggregate_passes(int nchunks, const Job* chunks, size_t row_bytes, co
   if (rs.census(st, nchunks, chunks, row_bytes, stream, &usable)) return -1;
   const size_t n = rs.n;
   rs.rows_to(chunk_rows_out);
-  if (!usable) return -1;
-  const size_t back_bytes = sizeof(AggResult) * (n ? n : 1);
-  if (rs.deal_tiles(st, sizeof(AggPartial), back_bytes + (terms ? sizeof(WhereTerms) : 0))) return -1;
+  if (!usable || !rs.prune(prune)) return -1;
+  const size_t back_bytes = sizeof(AggResult) * nf * (n ? n : 1), o_fields = back_bytes + (terms ? sizeof(WhereTerms) : 0);
+  if (rs.deal_tiles(st, sizeof(AggPartial) * nf, o_fields + (several ? sizeof(AggField) * nf : 0))) return -1;
   uint8_t *D = rs.D, *P = rs.P;
   AggResult* d_results = (AggResult*)(D + rs.o_back);
+  const AggField* d_fields = (const AggField*)(D + rs.o_back + o_fields);
   if (terms) {
     memcpy(P + rs.o_back + back_bytes, terms, sizeof(WhereTerms));
     HIP_TRY(hipMemcpyAsync(D + rs.o_back + back_bytes, P + rs.o_back + back_bytes, sizeof(WhereTerms), hipMemcpyHostToDevice, stream));
+  }
+  if (several) {
+    memcpy(P + rs.o_back + o_fields, fields, sizeof(AggField) * nf);
+    HIP_TRY(hipMemcpyAsync(D + rs.o_back + o_fields, P + rs.o_back + o_fields, sizeof(AggField) * nf, hipMemcpyHostToDevice, stream));
   }
   for (size_t p = 0; p < rs.npass; p++) {
     bool holds_rows = false;
@@ -2335,30 +2361,41 @@ static int aggregate_passes(int nchunks, const Job* chunks, size_t row_bytes, co
     if (!holds_rows) continue;
     const int in_pass = (int)(rs.c1 - rs.c0);
     Carver wv; wv.off = rs.at;
-    AggPartial* d_partials = (AggPartial*)(D + wv.take(sizeof(AggPartial) * rs.ntiles));
+    AggPartial* d_partials = (AggPartial*)(D + wv.take(sizeof(AggPartial) * nf * rs.ntiles));
     if (tiles(st, stream, TilesPass{dim3(persistent_grid(st, rs.ntiles, WH_WAVES_PER_CU / WH_WAVES)), rs.d_chunks(), rs.d_tiles(), in_pass, (uint32_t)row_bytes, d_partials},
-              (const WhereTerms*)(D + rs.o_back + back_bytes))) return -1;
+              (const WhereTerms*)(D + rs.o_back + back_bytes), d_fields)) return -1;
+    if (several) {
+      ProfScope ps(st, stream, "k_aggregate_chunks_fields");
+      hipLaunchKernelGGL(k_aggregate_chunks_fields, dim3(persistent_grid(st, (size_t)in_pass * nf, WH_WAVES_PER_CU / WH_WAVES)), dim3(WH_THREADS), 0, stream,
+                         rs.d_chunks(), rs.d_tiles(), in_pass, (uint32_t)row_bytes, d_fields, (int)nf, (const AggPartial*)d_partials, d_results + rs.c0 * nf);
+      HIP_TRY(hipGetLastError());
+      continue;
+    }
     ProfScope ps(st, stream, "k_aggregate_chunks");
     hipLaunchKernelGGL(k_aggregate_chunks, dim3(persistent_grid(st, (size_t)in_pass, WH_WAVES_PER_CU / WH_WAVES)), dim3(WH_THREADS), 0, stream, rs.d_chunks(),
-                       rs.d_tiles(), in_pass, (uint32_t)row_bytes, field, (const AggPartial*)d_partials, d_results + rs.c0);
+                       rs.d_tiles(), in_pass, (uint32_t)row_bytes, fields[0], (const AggPartial*)d_partials, d_results + rs.c0);
     HIP_TRY(hipGetLastError());
   }
-  // ---- collect: the chunks' entries; a chunk without rows, or one that did not decode, was in no launch or counts nothing ----
+  // ---- collect: the chunks' entries; a chunk without rows, a pruned one, or one that did not decode, was in no launch or counts nothing ----
   const AggResult* h_results = (const AggResult*)(P + rs.o_back);
-  if (n) HIP_TRY(hipMemcpyAsync(P + rs.o_back, d_results, sizeof(AggResult) * n, hipMemcpyDeviceToHost, stream));
+  if (n) HIP_TRY(hipMemcpyAsync(P + rs.o_back, d_results, sizeof(AggResult) * nf * n, hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
   prof_collect(st);
-  AggResult total;
-  aggregate_none(&total);
+  std::vector<AggResult> total(nf);
+  for (size_t f = 0; f < nf; f++) aggregate_none(&total[f]);
   for (size_t k = 0; k < n; k++) {
-    AggResult r;
-    aggregate_none(&r);
-    if (rs.rows_of[k] && rs.code[k] >= 0) r = h_results[k];
-    aggregate_fold(&total, r, field);
-    if (chunk_out) chunk_out[k] = r;
+    const bool skipped = rs.pruned.size() && rs.pruned[k];
+    for (size_t f = 0; f < nf; f++) {
+      AggResult r;
+      aggregate_none(&r);
+      if (skipped) r.rows = (uint64_t)rs.rows_of[k];      // what a decoded chunk without a match answers
+      else if (rs.rows_of[k] && rs.code[k] >= 0) r = h_results[k * nf + f];
+      aggregate_fold(&total[f], r, fields[f]);
+      if (chunk_out) chunk_out[k * nf + f] = r;
+    }
     if (chunk_status_out) chunk_status_out[k] = rs.code[k];
   }
-  if (total_out) *total_out = total;
+  if (total_out) std::copy(total.begin(), total.end(), total_out);
   if (unread_out) *unread_out = rs.unread;
   return 0;
 }
@@ -2366,23 +2403,35 @@ int engine_aggregate(int nchunks, const Job* chunks, size_t row_bytes, const Agg
                      AggResult* chunk_out, int* chunk_status_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream) {
   const WherePred q = filter ? *filter : WherePred{};
   const int filtered = filter ? 1 : 0;
-  auto tiles = [&field, &q, filtered](EngineState& st, hipStream_t stream, const TilesPass& m, const WhereTerms*) {
+  auto tiles = [&field, &q, filtered](EngineState& st, hipStream_t stream, const TilesPass& m, const WhereTerms*, const AggField*) {
     ProfScope ps(st, stream, "k_aggregate_tiles");
     hipLaunchKernelGGL(k_aggregate_tiles, m.grid, dim3(WH_THREADS), 0, stream, m.d_chunks, m.d_tiles, m.in_pass, m.row_bytes, field, q, filtered, m.d_partials);
     HIP_TRY(hipGetLastError());
     return 0;
   };
-  return aggregate_passes(nchunks, chunks, row_bytes, field, nullptr, tiles, total_out, chunk_out, chunk_status_out, chunk_rows_out, unread_out, stream);
+  return aggregate_passes(nchunks, chunks, row_bytes, &field, 1, false, nullptr, tiles, total_out, chunk_out, chunk_status_out, chunk_rows_out, unread_out, stream);
 }
 int engine_aggregate_terms(int nchunks, const Job* chunks, size_t row_bytes, const AggField& field, const WhereTerms& terms, AggResult* total_out,
-                           AggResult* chunk_out, int* chunk_status_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream) {
-  auto tiles = [&field](EngineState& st, hipStream_t stream, const TilesPass& m, const WhereTerms* d_terms) {
+                           AggResult* chunk_out, int* chunk_status_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream, const RowPrune* prune) {
+  auto tiles = [&field](EngineState& st, hipStream_t stream, const TilesPass& m, const WhereTerms* d_terms, const AggField*) {
     ProfScope ps(st, stream, "k_aggregate_tiles_terms");
     hipLaunchKernelGGL(k_aggregate_tiles_terms, m.grid, dim3(WH_THREADS), 0, stream, m.d_chunks, m.d_tiles, m.in_pass, m.row_bytes, field, d_terms, m.d_partials);
     HIP_TRY(hipGetLastError());
     return 0;
   };
-  return aggregate_passes(nchunks, chunks, row_bytes, field, &terms, tiles, total_out, chunk_out, chunk_status_out, chunk_rows_out, unread_out, stream);
+  return aggregate_passes(nchunks, chunks, row_bytes, &field, 1, false, &terms, tiles, total_out, chunk_out, chunk_status_out, chunk_rows_out, unread_out, stream, prune);
+}
+int engine_aggregate_fields(int nchunks, const Job* chunks, size_t row_bytes, const AggField* fields, int nfields, const WhereTerms& terms, AggResult* total_out,
+                            AggResult* chunk_out, int* chunk_status_out, int* chunk_rows_out, size_t* unread_out, hipStream_t stream) {
+  auto tiles = [nfields](EngineState& st, hipStream_t stream, const TilesPass& m, const WhereTerms* d_terms, const AggField* d_fields) {
+    ProfScope ps(st, stream, "k_aggregate_tiles_fields");
+    hipLaunchKernelGGL(k_aggregate_tiles_fields, m.grid, dim3(WH_THREADS), 0, stream, m.d_chunks, m.d_tiles, m.in_pass, m.row_bytes, d_fields, nfields, d_terms,
+                       m.d_partials);
+    HIP_TRY(hipGetLastError());
+    return 0;
+  };
+  return aggregate_passes(nchunks, chunks, row_bytes, fields, (size_t)nfields, true, &terms, tiles, total_out, chunk_out, chunk_status_out, chunk_rows_out, unread_out,
+                          stream);
 }
 
 // blosc_getitem / blosc_gpu_getitem: one chunk, one range, one result, each pointer host or device memory.  What only this call has: a stream

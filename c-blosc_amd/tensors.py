@@ -15,6 +15,8 @@ table - by blosc_gpu_where_packed (include/blosc_gpu_where.h), holding one pass 
 blosc_gpu_aggregate_packed (include/blosc_gpu_aggregate.h), without an index table.
 `where_rows_clauses` / `aggregate_rows_clauses` are the two for SEVERAL comparisons - an AND of OR clauses over any columns: a range, two
 columns, a small key set - in one call and one decode (include/blosc_gpu_clauses.h).
+`aggregate_rows_fields` reduces several columns in one decode, `zone_map` keeps the per-chunk minimum and maximum of up to 16 columns as a
+`Zones`, and the two clause functions take it as `zones=` and do not decode the chunks it excludes (include/blosc_gpu_zones.h).
 
 Like blpk.py's device functions this module only drives the library: `lib` is the ctypes handle (load() of the package), memory comes
 from a `mem` with blpk.TorchMem's alloc().  There is no CPU implementation: without the library and a GPU the calls fail.
@@ -331,7 +333,7 @@ def _clause_terms(pkg, meta, call, clauses, *columns):
     return terms, dtype, kind, element, row_bytes
 
 
-def where_rows_clauses(lib, container, offsets, meta, clauses, max_matches=None, mem=None, stream=None):
+def where_rows_clauses(lib, container, offsets, meta, clauses, max_matches=None, mem=None, stream=None, zones=None):
     """where_rows for several comparisons at once: torch.nonzero of an AND of OR clauses over the columns of the table pack_rows packed, by
     blosc_gpu_where_clauses_packed (include/blosc_gpu_clauses.h) - one decode, whatever the number of comparisons.  clauses: a list that is
     ANDed; each entry is (op, value, column) or a list of such triples that is ORed:
@@ -339,7 +341,10 @@ def where_rows_clauses(lib, container, offsets, meta, clauses, max_matches=None,
         [(">=", t0, 0), [("==", 3, 1), ("==", 5, 1)]]        column 0 >= t0 and column 1 in {3, 5}
     op, value and column are where_rows', with the same rounding to a floating-point dtype and the same ValueError for a value an integer
     dtype does not hold; at most 16 comparisons in at most 16 clauses, at least one.  max_matches, the two calls without it, the result
-    (index, total) and the errors raised are where_rows'."""
+    (index, total) and the errors raised are where_rows'.
+    zones: a Zones of this container (zone_map) - the chunks whose entries show that no row can pass are not decoded
+    (blosc_gpu_where_zoned_packed, include/blosc_gpu_zones.h); the answer is the same as long as the map describes the container.  A map that
+    was not refreshed after put_rows makes the call miss rows: that is the caller's to prevent (Zones.refresh).  None: no map."""
     import torch
     pkg = _sibling("", "__init__.py")
     mem = mem if mem is not None else _sibling("blpk", "blpk.py").TorchMem()
@@ -347,10 +352,17 @@ def where_rows_clauses(lib, container, offsets, meta, clauses, max_matches=None,
     terms, dtype, kind, element, row_bytes = _clause_terms(pkg, meta, "blosc_gpu_where_clauses_packed", clauses)
     if not terms:
         raise ValueError("where_rows_clauses takes at least one comparison")
-    where = pkg.RowWhereClauses(row_bytes, lib=lib)
+    if zones is not None:
+        zones.check(meta)
+        pkg.declare_zones(lib)
+    where = pkg.RowWhereClauses(row_bytes, lib=lib) if zones is None else pkg.RowWhereZoned(row_bytes, lib=lib)
 
     def call(ptr, capacity):
-        if where.packed(container.data_ptr(), int(container.numel()), list(offsets), terms, ptr, capacity, stream) != 0:
+        if zones is None:
+            rc = where.packed(container.data_ptr(), int(container.numel()), list(offsets), terms, ptr, capacity, stream)
+        else:
+            rc = where.packed(container.data_ptr(), int(container.numel()), list(offsets), terms, zones.fields, zones.table(pkg), ptr, capacity, stream)
+        if rc != 0:
             raise RuntimeError(f"blosc_gpu_where_clauses_packed failed; rows per chunk (negative: the chunk's code): {where.chunk_rows()}")
         if where.chunk_rows() != [int(shape[0]) for _, shape in meta]:
             raise RuntimeError(f"the container does not hold this table: rows per chunk {where.chunk_rows()}")
@@ -370,15 +382,24 @@ def where_rows_clauses(lib, container, offsets, meta, clauses, max_matches=None,
     return keep[:min(total, capacity) * 8].view(torch.int64), total
 
 
-def aggregate_rows_clauses(lib, container, offsets, meta, column=0, clauses=None, mem=None, stream=None):
+def aggregate_rows_clauses(lib, container, offsets, meta, column=0, clauses=None, mem=None, stream=None, zones=None):
     """aggregate_rows over the rows that an AND of OR clauses lets through (clauses: where_rows_clauses'; None or empty: every row), by ONE
-    blosc_gpu_aggregate_clauses_packed (include/blosc_gpu_clauses.h).  Returns an Aggregated, as aggregate_rows does, and raises as it does."""
+    blosc_gpu_aggregate_clauses_packed (include/blosc_gpu_clauses.h).  Returns an Aggregated, as aggregate_rows does, and raises as it does.
+    zones: where_rows_clauses' - the chunks the map excludes are not decoded (blosc_gpu_aggregate_zoned_packed) and count no row."""
     import torch
     pkg = _sibling("", "__init__.py")
     pkg.declare_clauses(lib)
     terms, dtype, kind, element, row_bytes = _clause_terms(pkg, meta, "blosc_gpu_aggregate_clauses_packed", clauses, column)
-    agg = pkg.RowAggregateClauses(row_bytes, lib=lib)
-    if agg.packed(container.data_ptr(), int(container.numel()), list(offsets), pkg.field(kind, element, offset=column * element), terms, stream) != 0:
+    if zones is None:
+        agg = pkg.RowAggregateClauses(row_bytes, lib=lib)
+        rc = agg.packed(container.data_ptr(), int(container.numel()), list(offsets), pkg.field(kind, element, offset=column * element), terms, stream)
+    else:
+        zones.check(meta)
+        pkg.declare_zones(lib)
+        agg = pkg.RowAggregateZoned(row_bytes, lib=lib)
+        rc = agg.packed(container.data_ptr(), int(container.numel()), list(offsets), pkg.field(kind, element, offset=column * element), terms, zones.fields,
+                        zones.table(pkg), stream)
+    if rc != 0:
         raise RuntimeError(f"blosc_gpu_aggregate_clauses_packed failed; rows per chunk (negative: the chunk's code): {agg.chunk_rows()}")
     if agg.chunk_rows() != [int(shape[0]) for _, shape in meta]:
         raise RuntimeError(f"the container does not hold this table: rows per chunk {agg.chunk_rows()}")
@@ -396,13 +417,127 @@ def aggregate_rows_clauses(lib, container, offsets, meta, column=0, clauses=None
     return result(agg.total(), [result(c, None) for c in agg.chunks()])
 
 
-def put_rows(lib, container, offsets, meta, index, rows, mem=None, stream=None, align=256, **settings):
+def _aggregated(pkg, dtype, kind, element, a, chunks):
+    """one blosc_gpu_aggregate of a column of this dtype as an Aggregated"""
+    import torch
+    def scalar(raw):
+        return torch.tensor(list(raw[:element]), dtype=torch.uint8).view(dtype)[0].item()
+    total = a.sum.f if dtype.is_floating_point else (a.sum.i if kind == pkg.FIELD_INT else a.sum.u)
+    return Aggregated(int(a.count), int(a.nans), total, scalar(a.min) if a.min_row >= 0 else None, scalar(a.max) if a.max_row >= 0 else None,
+                      int(a.min_row) if a.min_row >= 0 else None, int(a.max_row) if a.max_row >= 0 else None, chunks)
+
+
+def _fields_call(pkg, lib, meta, columns, clauses, run):
+    """blosc_gpu_aggregate_fields_* for `columns`: run(agg, fields, terms) makes the call on a RowAggregateFields and returns its answer.
+    Returns (agg, fields, dtype, kind, element), the outputs checked as aggregate_rows checks them"""
+    pkg.declare_zones(lib)
+    columns = [int(c) for c in columns]
+    if not 1 <= len(columns) <= pkg.MAX_ZONE_FIELDS:
+        raise ValueError(f"{len(columns)} columns: a call takes 1 ... {pkg.MAX_ZONE_FIELDS}")
+    terms, dtype, kind, element, row_bytes = _clause_terms(pkg, meta, "blosc_gpu_aggregate_fields_packed", clauses, *columns)
+    fields = [pkg.field(kind, element, offset=c * element) for c in columns]
+    agg = pkg.RowAggregateFields(row_bytes, lib=lib)
+    if run(agg, fields, terms) != 0:
+        raise RuntimeError(f"blosc_gpu_aggregate_fields failed; rows per chunk (negative: the chunk's code): {agg.chunk_rows()}")
+    return agg, fields, dtype, kind, element
+
+
+def aggregate_rows_fields(lib, container, offsets, meta, columns, where=None, mem=None, stream=None):
+    """aggregate_rows for SEVERAL columns in one decode: ONE blosc_gpu_aggregate_fields_packed (include/blosc_gpu_zones.h) for up to 16
+    columns, which may repeat.  where: None (every row), one (op, value, column), or a clause list as where_rows_clauses takes it.
+    Returns a list with one Aggregated per column - each what aggregate_rows_clauses answers for that column alone, bit for bit - and raises
+    as aggregate_rows does."""
+    pkg = _sibling("", "__init__.py")
+    clauses = [where] if isinstance(where, tuple) else where
+    agg, fields, dtype, kind, element = _fields_call(pkg, lib, meta, columns, clauses, lambda a, f, t: a.packed(
+        container.data_ptr(), int(container.numel()), list(offsets), f, t, stream))
+    if agg.chunk_rows() != [int(shape[0]) for _, shape in meta]:
+        raise RuntimeError(f"the container does not hold this table: rows per chunk {agg.chunk_rows()}")
+    if agg.unread():
+        raise RuntimeError(f"{agg.unread()} of {sum(agg.chunk_rows())} rows were not read (chunks that do not decode: {agg.chunk_status()})")
+    per_chunk = agg.chunks()
+    return [_aggregated(pkg, dtype, kind, element, total, [_aggregated(pkg, dtype, kind, element, c[f], None) for c in per_chunk])
+            for f, total in enumerate(agg.totals())]
+
+
+def _zone_dtype():
+    import numpy as np
+    return np.dtype([("rows", "<u8"), ("count", "<u8"), ("nans", "<u8"), ("min_row", "<i8"), ("max_row", "<i8"), ("min", "u1", 8), ("max", "u1", 8),
+                     ("sum", "<u8")])      # blosc_gpu_aggregate, 64 bytes
+
+
+class Zones:
+    """A zone map of a table pack_rows packed: `columns`, their `fields` (the package's Field) and `entries`, a numpy array [chunks, columns]
+    of blosc_gpu_aggregate records (rows, count, nans, min_row, max_row, min, max, sum; min and max as the column's 8 bytes, zero-extended) -
+    what blosc_gpu_aggregate_fields_packed answers for every row of every chunk.  where_rows_clauses and aggregate_rows_clauses take it as
+    `zones=` and skip the chunks it excludes.  The map describes the container it was computed from: after put_rows, refresh() the chunks
+    that call rewrote (put_rows(..., return_rewritten=True)), or the zoned calls miss rows."""
+
+    def __init__(self, columns, fields, entries):
+        self.columns, self.fields, self.entries = list(columns), list(fields), entries
+
+    def check(self, meta):
+        if self.entries.shape != (len(meta), len(self.columns)):
+            raise ValueError(f"a zone map of {self.entries.shape[0]} chunks for a container of {len(meta)}")
+
+    def table(self, pkg):
+        """the entries as the ctypes array the zoned calls take"""
+        n = int(self.entries.size)
+        return (pkg.Aggregate * max(n, 1)).from_buffer_copy(self.entries.tobytes() if n else bytes(64))
+
+    def refresh(self, lib, container, offsets, meta, chunks):
+        """Recompute the entries of the chunks numbered in `chunks` from `container` - the one put_rows returned - by ONE
+        blosc_gpu_aggregate_fields_batch over those chunks' addresses: the others are neither decoded nor touched.  Returns self."""
+        import numpy as np
+        pkg = _sibling("", "__init__.py")
+        self.check(meta)
+        chunks = sorted({int(k) for k in chunks})
+        if any(not 0 <= k < len(meta) for k in chunks):
+            raise ValueError(f"chunks {chunks} of a container of {len(meta)}")
+        if not chunks:
+            return self
+        base = container.data_ptr()
+        agg, _, _, _, _ = _fields_call(pkg, lib, [meta[k] for k in chunks], self.columns, None,
+                                       lambda a, f, t: a.batch([base + int(offsets[k]) for k in chunks], f, t))
+        if agg.chunk_rows() != [int(meta[k][1][0]) for k in chunks] or agg.unread():
+            raise RuntimeError(f"the container does not hold these chunks: rows {agg.chunk_rows()}, unread {agg.unread()}")
+        fresh = np.frombuffer(bytes(agg.entries()), _zone_dtype())[:len(chunks) * len(self.columns)].reshape(len(chunks), len(self.columns)).copy()
+        first = np.concatenate([[0], np.cumsum([int(shape[0]) for _, shape in meta])])
+        at = 0      # the call numbered its rows from the first of ITS chunks: back to the table's numbers
+        for i, k in enumerate(chunks):
+            for name in ("min_row", "max_row"):
+                fresh[name][i] = np.where(fresh[name][i] >= 0, fresh[name][i] - at + int(first[k]), -1)
+            at += int(meta[k][1][0])
+            self.entries[k] = fresh[i]
+        return self
+
+
+def zone_map(lib, container, offsets, meta, columns, mem=None, stream=None):
+    """The zone map of `columns` (up to 16) of the table pack_rows packed: per chunk and column the minimum, the maximum, the NaNs and the
+    rest of a blosc_gpu_aggregate over every row, by ONE blosc_gpu_aggregate_fields_packed (include/blosc_gpu_zones.h) - one decode of the
+    container, whatever the number of columns.  Returns a Zones; raises as aggregate_rows does."""
+    import numpy as np
+    pkg = _sibling("", "__init__.py")
+    agg, fields, _, _, _ = _fields_call(pkg, lib, meta, columns, None, lambda a, f, t: a.packed(
+        container.data_ptr(), int(container.numel()), list(offsets), f, t, stream))
+    if agg.chunk_rows() != [int(shape[0]) for _, shape in meta]:
+        raise RuntimeError(f"the container does not hold this table: rows per chunk {agg.chunk_rows()}")
+    if agg.unread():
+        raise RuntimeError(f"{agg.unread()} of {sum(agg.chunk_rows())} rows were not read (chunks that do not decode: {agg.chunk_status()})")
+    n = len(meta) * len(fields)
+    entries = np.frombuffer(bytes(agg.entries()), _zone_dtype())[:n].reshape(len(meta), len(fields)).copy()
+    return Zones(columns, fields, entries)
+
+
+def put_rows(lib, container, offsets, meta, index, rows, mem=None, stream=None, align=256, return_rewritten=False, **settings):
     """table.index_copy_(0, index, rows) for the table pack_rows packed, by ONE blosc_gpu_put_packed (include/blosc_gpu_put.h): `index` is an
     int64 tensor on the device, `rows` a device tensor of the shape [len(index), *row shape] and the table's dtype; of an index that occurs
     several times the last occurrence wins.  Returns (new_container, new_offsets) - the container given is not written and `meta` stays what
     it is.  Only the chunks some row lands in are decoded and compressed again, with the typesize of the table's dtype and `settings`
     (cname / clevel / shuffle / blocksize / splitmode, pack_tensors' defaults); the others are copied.  Raises if any row failed (an index
-    outside the table, a chunk that does not decode), naming how many."""
+    outside the table, a chunk that does not decode), naming how many.
+    return_rewritten=True: returns (new_container, new_offsets, rewritten) - the numbers of the chunks that were decoded and compressed again,
+    which are the chunks whose entries of a zone map no longer hold (Zones.refresh)."""
     import torch
     pkg = _sibling("", "__init__.py")
     mem = mem if mem is not None else _sibling("blpk", "blpk.py").TorchMem()
@@ -438,4 +573,6 @@ def put_rows(lib, container, offsets, meta, index, rows, mem=None, stream=None, 
     if put.failed():
         raise RuntimeError(f"{put.failed()} of {n} rows failed (an index outside 0 ... {sum(put.chunk_rows()) - 1}, or a chunk that does not decode)")
     off = put.offsets()
+    if return_rewritten:
+        return keep[:off[-1]], off, [k for k, r in enumerate(put.rewritten()) if r == 1]
     return keep[:off[-1]], off
